@@ -10,9 +10,9 @@ Workload = BASELINE.json configs[2] ("SDXL RegionDiffusionXL 1024x1024, 4 region
 A "step" is one iteration of the loop at models/region_diffusion_sdxl.py:779 (all F forwards, mask combine,
 CFG, scheduler step).  Every forward the reference executes is executed (no dead-forward elision).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N > 1: one rank per GPU under torch.distributed.run - either launched that way by the caller (RANK / LOCAL_RANK / WORLD_SIZE in the
-environment) or, when `python bench.py --gpus N` is run bare, by re-executing itself under `python -m torch.distributed.run
+environment) or, when `python bench.py --gpus N` is run bare, by running itself in a child `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (launcher.self_launch).  Each rank runs an independent image (own seed,
 latents, masks, prompts) after ONE broadcast of the packed weight arena (RCCL); no per-step collectives;
 value = N*K / max-over-ranks time ("weak" scaling).
@@ -388,9 +388,16 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=[1, 2, 3, 5],
                     help="BASELINE.json configuration (SURVEY 8d numbering): 3 = the headline SDXL workload (default); "
                          "1 / 2 = SD-v1.5 (R=2 plain; R=4 + colour guidance); 5 = SDXL + colour guidance + background blend")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (rank 0's latents after the last timed step) as DIR/latents.npy, "
+                         "float32 [1, 4, 128, 128]; the inputs are seeded, so two builds can be compared output for output (config 3 only)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.config == 1 else 50
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.config != 3 or args.roofline_only or args.dry_launch):
+        ap.error("--dump-outputs needs the timed steps of config 3 (not --config 1/2/5, --roofline-only or --dry-launch)")
     if args.config != 3:
         return other_config(args)
 
@@ -485,6 +492,10 @@ def main():
     dt = launcher.max_over_ranks(dt_local, device=dev if (world > 1 and not gloo) else "cpu")
     final = eng.read_latents(hw, hw)
     finite = bool(torch.isfinite(final).all())
+    if args.dump_outputs is not None and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), final.cpu().numpy().astype(np.float32))
 
     # ---- roofline leg (outside the timed region): HIP events around every MFMA kernel launch on the engine
     # stream for one injected step (i=0) and one non-injected step (i=nsched-1)

@@ -81,10 +81,11 @@ def free_port():
 
 def self_launch(script, argv, nproc, require_gpus=True, module=None):
     """`python bench.py --gpus N` without a wrapper: when no torch.distributed.run environment is present (WORLD_SIZE unset) and
-    N > 1, replace this process by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
-    --master-port P script argv...` - one rank per GPU, LOCAL_RANK selects the device.  Returns None when nothing has to be done
-    (N == 1 or already inside a launch); returns an error string when the box has fewer than N GPUs (the caller reports it);
-    otherwise does not return.  `module`: launch `python -m <module>` instead of a script path."""
+    N > 1, run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P script argv...`
+    as a child process and exit with its status - one rank per GPU, LOCAL_RANK selects the device.  A child, not exec: the device
+    query below may already have opened the GPU runtime in this process.  Returns None when nothing has to be done (N == 1 or already
+    inside a launch); returns an error string when the box has fewer than N GPUs (the caller reports it); otherwise does not return.
+    `module`: launch `python -m <module>` instead of a script path."""
     import sys
     if nproc <= 1 or "WORLD_SIZE" in os.environ:
         return None
@@ -102,7 +103,8 @@ def self_launch(script, argv, nproc, require_gpus=True, module=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(env.get("MASTER_PORT") or free_port())] + target + list(argv)
     sys.stdout.flush(); sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def shard_round_robin(requests, rank, world):

@@ -56,10 +56,11 @@ def test_sdxl_prompt_encoding_rules(tok):
     assert pe.shape == (2, 77, 80) and pp.shape == (2, 40) and not ne.any() and not npool.any()       # zeroed negative (xl.py:363-366)
     pe2, ne2, pp2, np2 = enc(["the cat", "the dog"], [""])
     assert torch.equal(pe, pe2) and ne2.shape == (1, 77, 80) and ne2.abs().sum() > 0 and np2.shape == (1, 40)
-    ids = tok(["the cat"], padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids
+    # the same batch as the encoder ran: a batch-1 recomputation rounds the fp32 GEMMs differently on some hosts (1e-7 on values of 3e-3)
+    ids = tok(["the cat", "the dog"], padding="max_length", max_length=77, truncation=True, return_tensors="pt").input_ids
     with torch.no_grad():
         o1, o2 = e1(ids, output_hidden_states=True), e2(ids, output_hidden_states=True)
-    assert torch.allclose(pe[:1], torch.cat([o1.hidden_states[-2], o2.hidden_states[-2]], -1)) and torch.allclose(pp[:1], o2[0])
+    assert torch.allclose(pe, torch.cat([o1.hidden_states[-2], o2.hidden_states[-2]], -1)) and torch.allclose(pp, o2[0])
 
 
 def test_bpe_matches_the_hf_tokenizers_clip_recipe(tmp_path):
