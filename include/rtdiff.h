@@ -316,6 +316,20 @@ int rt_vae_decode(rt_vae* v, const float* latents, int h, int w, int divide_by_s
 int rt_vae_color_guidance(rt_vae* v, float* latents, const float* noise_pred, float alpha_t, int h, int w, const float* masks_img,
                           const float* target_rgb_host, int n_regions, float weight, const float* mask_all, float* grad_out,
                           float* loss_out_host);
+
+/* ---- VAE encoder: RegionDiffusion.encode_imgs (rd.py:238-246) ----
+ * AutoencoderKL.encoder + quant_conv + DiagonalGaussianDistribution (diffusers 0.18.2, restated in tests/vae_encoder_ref.py; parity
+ * unpinned against diffusers).  The same rt_vae handle type in the encoder role: weight names "encoder.*" / "quant_conv.*"; the
+ * weight-table, bind, arena, synchronize, destroy and last-error calls serve both roles.  latent_h / latent_w of the config size the
+ * workspace for images up to 8 latent_h x 8 latent_w.  Decode / guidance on an encoder handle and encode / sample on a decoder
+ * handle return RT_E_STATE. */
+int rt_vae_encoder_create(const rt_vae_config* cfg, int device, rt_vae** out);   /* device -1: weight table only */
+/* img [3,H,W] f32 (H, W multiples of 8, at most the plan's), x' = in_scale*x + in_shift;
+ * moments_out [8,H/8,W/8] = mean | clamp(logvar,-30,20) */
+int rt_vae_encode(rt_vae* v, const float* img, int H, int W, float in_scale, float in_shift, float* moments_out);
+/* latents [4,h,w] = scale * (mean + exp(0.5*logvar) * noise[4,h,w]) */
+int rt_vae_posterior_sample(rt_vae* v, const float* moments, const float* noise, int h, int w, float scale, float* latents_out);
+
 /* engine sampler state pointers for the guidance step: latents [4,h,w] and the CFG-combined noise prediction of the
  * last rt_region_step (noise_pred in rd.py:131-132 / xl.py:824-825) */
 int rt_get_state_ptrs(rt_engine* e, float** latents, float** noise_pred);

@@ -176,6 +176,18 @@ def load_guidance_vae(load_path, kind, device=0, latent_hw=None):
     return VaeDecoder(vae_cfg, hw[0], hw[1], device=device, state_dict=vae_sd, precise=False)
 
 
+def load_vae_encoder(vae_dir, kind="SD", device=0, latent_hw=None, precise=False):
+    """A VaeEncoder on the `encoder.*` / `quant_conv.*` weights of the AutoencoderKL directory `vae_dir` (rd.py:26-33 loads the whole
+    AutoencoderKL); `latent_hw` sizes its plan (images up to 8x that).  None when the weights there hold no encoder (decoder-only)."""
+    from .engine import SD_VAE_CONFIG, SDXL_VAE_CONFIG, VaeEncoder
+    sd = load_state_dict_dir(vae_dir)
+    if "encoder.conv_in.weight" not in sd:
+        return None
+    cfg = vae_config(vae_dir, SD_VAE_CONFIG if kind == "SD" else SDXL_VAE_CONFIG)
+    hw = latent_hw or ((64, 64) if kind == "SD" else (128, 128))
+    return VaeEncoder(cfg, hw[0], hw[1], device=device, state_dict=sd, precise=precise)
+
+
 def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=None, lora_scale=1.0, weights=True):
     """Everything the facade constructors need from a diffusers-layout directory (unet/, vae/, tokenizer[_2]/, text_encoder[_2]/) as
     keyword arguments of RegionDiffusion / RegionDiffusionXL.  `latent_hw` sizes the VAE plan (default: the model's native size).
@@ -197,7 +209,9 @@ def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=No
     tok = ClipBPETokenizer.from_pretrained(load_path, "tokenizer")
     if kind == "SD":
         enc = load_text_encoder(os.path.join(load_path, "text_encoder"), device, weights=weights)
-        return dict(unet_state_dict=unet_sd, config=unet_cfg, vae=vae, tokenizer=tok, text_encoder=ClipEncoderSD(enc, dev))
+        # vae_dir: RegionDiffusion.encode_imgs builds its VaeEncoder from it on first use (load_vae_encoder)
+        return dict(unet_state_dict=unet_sd, config=unet_cfg, vae=vae, tokenizer=tok, text_encoder=ClipEncoderSD(enc, dev),
+                    vae_dir=os.path.join(load_path, "vae"))
     tok2 = ClipBPETokenizer.from_pretrained(load_path, "tokenizer_2")
     enc1 = load_text_encoder(os.path.join(load_path, "text_encoder"), device, weights=weights)
     enc2 = load_text_encoder(os.path.join(load_path, "text_encoder_2"), device, with_projection=True, weights=weights)

@@ -103,7 +103,9 @@ static __device__ __forceinline__ void glds16_buf(const void* base, int voff_byt
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff_bytes, soff_bytes, 0, 0);
 }
 // ---------------------------------------------------------------- GEMM / implicit-GEMM conv
-enum { A_DENSE = 0, A_CONV3 = 1, A_CONV3_S2 = 2, A_CONV3_UP2 = 3 };
+// A_CONV3_S2P0: 3x3 stride-2 convolution with zero padding on the bottom / right only (diffusers Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1))
+// then stride 2, pad 0), the VAE encoder's downsamplers; Hin, Win even, Hout = Hin / 2, Wout = Win / 2
+enum { A_DENSE = 0, A_CONV3 = 1, A_CONV3_S2 = 2, A_CONV3_UP2 = 3, A_CONV3_S2P0 = 4 };
 enum { EPI_BF16 = 0, EPI_F32 = 1, EPI_BF16_TEMB = 2, EPI_GEGLU = 3, EPI_F16 = 4,   // EPI_F16: fp16 output (+ fp16 residual): the UNet trunk
        EPI_XATTN = 5 };   // gemm16.hip only: the to_q projection whose tile never leaves the CU - 77-key cross-attention on it, O written (launch_xattn_fused)
 typedef _Float16 f16_t;

@@ -259,6 +259,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                     } else if (MODE == A_CONV3_S2) {
                         yy = cy[i] * 2 + ky - 1; xx = cx[i] * 2 + kx - 1;
                         ok = yy >= 0 && yy < p.Hin && xx >= 0 && xx < p.Win;
+                    } else if (MODE == A_CONV3_S2P0) {
+                        yy = cy[i] * 2 + ky; xx = cx[i] * 2 + kx;
+                        ok = yy < p.Hin && xx < p.Win;
                     } else {   // nearest 2x upsample fused into the gather: conv runs on the (2Hin x 2Win) grid
                         yy = cy[i] + ky - 1; xx = cx[i] + kx - 1;
                         ok = yy >= 0 && yy < 2 * p.Hin && xx >= 0 && xx < 2 * p.Win;
@@ -472,6 +475,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_pp_kernel(GemmArgs p) {
                 } else if (MODE == A_CONV3_S2) {
                     yy = cy[i] * 2 + ky - 1; xx = cx[i] * 2 + kx - 1;
                     ok = yy >= 0 && yy < p.Hin && xx >= 0 && xx < p.Win;
+                } else if (MODE == A_CONV3_S2P0) {
+                    yy = cy[i] * 2 + ky; xx = cx[i] * 2 + kx;
+                    ok = yy < p.Hin && xx < p.Win;
                 } else {
                     yy = cy[i] + ky - 1; xx = cx[i] + kx - 1;
                     ok = yy >= 0 && yy < 2 * p.Hin && xx >= 0 && xx < 2 * p.Win;
@@ -678,6 +684,7 @@ __global__ __launch_bounds__((WM * WN + NL) * 64) void gemm_ws_kernel(GemmArgs p
                     int yy, xx; bool ok;
                     if (MODE == A_CONV3) { yy = cy[i] + ky - 1; xx = cx[i] + kx - 1; ok = yy >= 0 && yy < p.Hin && xx >= 0 && xx < p.Win; }
                     else if (MODE == A_CONV3_S2) { yy = cy[i] * 2 + ky - 1; xx = cx[i] * 2 + kx - 1; ok = yy >= 0 && yy < p.Hin && xx >= 0 && xx < p.Win; }
+                    else if (MODE == A_CONV3_S2P0) { yy = cy[i] * 2 + ky; xx = cx[i] * 2 + kx; ok = yy < p.Hin && xx < p.Win; }
                     else { yy = cy[i] + ky - 1; xx = cx[i] + kx - 1; ok = yy >= 0 && yy < 2 * p.Hin && xx >= 0 && xx < 2 * p.Win; yy >>= 1; xx >>= 1; }
                     if (ok) src = base[i] + ((size_t)yy * p.Win + xx) * p.Cin + c;
                 }
@@ -1230,6 +1237,7 @@ static void launch_with_cfg(const GemmArgs& a, int cfg, hipStream_t st) {
         case A_CONV3_S2 * 8 + EPI_F16: launch_me<A_CONV3_S2, EPI_F16>(a, cfg, st); break;
         case A_CONV3_UP2 * 8 + EPI_F32: launch_me<A_CONV3_UP2, EPI_F32>(a, cfg, st); break;
         case A_CONV3_UP2 * 8 + EPI_F16: launch_me<A_CONV3_UP2, EPI_F16>(a, cfg, st); break;
+        case A_CONV3_S2P0 * 8 + EPI_F32: launch_me<A_CONV3_S2P0, EPI_F32>(a, cfg, st); break;      // VAE encoder downsamplers (fp32 out only)
         default: throw rt_error(RT_E_UNSUPPORTED, "gemm: (operand mode, epilogue) combination not built");
     }
     HIP_CHECK(hipGetLastError());
@@ -1500,6 +1508,7 @@ static void launch_gemm_splitk(const GemmArgs& a, int S, hipStream_t st) {
             case A_DENSE: RT_SPLIT_LAUNCH(A_DENSE) break;
             case A_CONV3: RT_SPLIT_LAUNCH(A_CONV3) break;
             case A_CONV3_S2: RT_SPLIT_LAUNCH(A_CONV3_S2) break;
+            case A_CONV3_S2P0: RT_SPLIT_LAUNCH(A_CONV3_S2P0) break;
             default: RT_SPLIT_LAUNCH(A_CONV3_UP2) break;
         }
 #undef RT_SPLIT_LAUNCH
@@ -1540,6 +1549,8 @@ static void check_gemm_args(const GemmArgs& a) {
     } else {
         RT_REQUIRE(a.Cin % 8 == 0 && a.K == 9 * a.Cin && a.rows_per_batch == a.Hout * a.Wout, "conv: bad geometry");
         RT_REQUIRE((long)(a.M / a.rows_per_batch + 1) * a.Hin * a.Win * a.Cin < (1L << 31), "conv: input too large for 32-bit offsets");
+        if (a.mode == A_CONV3_S2P0)
+            RT_REQUIRE(a.Hin % 2 == 0 && a.Win % 2 == 0 && a.Hout == a.Hin / 2 && a.Wout == a.Win / 2, "conv (stride 2, bottom / right padding): Hin, Win even, Hout = Hin / 2, Wout = Win / 2");
     }
     if (a.epi == EPI_GEGLU) RT_REQUIRE(a.N % 64 == 0, "geglu: N must be a multiple of 64");
     RT_REQUIRE(a.N % 4 == 0, "gemm: N must be a multiple of 4");

@@ -15,6 +15,11 @@
 // (hi = bf16(v), lo = bf16(v - hi), together 16 mantissa bits) and every contraction is three passes, hi*hi + lo*hi + hi*lo,
 // accumulated in fp32 in the same output (the lo*lo term is 2^-18 relative and dropped).  Everything between contractions
 // (GroupNorm, SiLU, softmax, residual adds, the loss) already runs in fp32.  Three times the MFMA work of the default mode.
+//
+// ENCODER role (rt_vae_encoder_create): AutoencoderKL.encoder + quant_conv + DiagonalGaussianDistribution for
+// RegionDiffusion.encode_imgs (rd.py:238-246), restated like the decoder (tests/vae_encoder_ref.py; parity unpinned against diffusers).
+// Forward only: the same blocks (res_fwd / attn_fwd without a tape), forward weight packs only, the stride-2 downsamplers on the
+// implicit GEMM's A_CONV3_S2P0 gather (bottom / right zero padding).
 #include "common.h"
 #include "../../include/rtdiff.h"
 #include "vae.h"
@@ -58,6 +63,7 @@ struct rt_vae {
     char* ws_base = nullptr; size_t ws_cap = 0, ws_off = 0, ws_peak = 0;
     bool dry = false;
     bool precise = false;
+    bool encoder = false;            // role: encoder (forward packs only) or decoder
     bf16_t* zero = nullptr;
     std::vector<Slot> slots;
     std::map<std::string, int> slot_index;
@@ -70,6 +76,10 @@ struct rt_vae {
     std::vector<VConv> up_conv;      // size n-1
     NormW norm_out;
     int G = 32;
+    // encoder plan (conv_in / conv_out / mid0 / attn / mid1 / norm_out above hold the encoder's layers of the same names)
+    float* qc_w = nullptr; float* qc_b = nullptr;
+    std::vector<std::vector<VRes>> down_res;
+    std::vector<VConv> down_conv;    // size n-1
 
     // ---------------------------------------------------------------- memory
     void* walloc(size_t bytes) {
@@ -104,9 +114,16 @@ struct rt_vae {
         const int CoutN = (Cout + 3) & ~3, CinN = (Cin + 3) & ~3;      // GEMM N must be a multiple of 4
         c.f.N = CoutN; c.f.K = 9 * c.cinP; c.f.w = (bf16_t*)arena.alloc((size_t)CoutN * c.f.K * 2);
         c.f.b = (float*)arena.alloc((size_t)CoutN * 4);
-        c.b.N = CinN; c.b.K = 9 * c.coutP; c.b.w = (bf16_t*)arena.alloc((size_t)CinN * c.b.K * 2);
         PackArgs pf{}; pf.dst = c.f.w; pf.rows = Cout; pf.cols = c.f.K; pf.ld_dst = c.f.K; pf.row_map = PACK_ROWS_ID; pf.c_inner = c.cinP;
         pf.ci_valid = Cin; pf.s_r = (long)Cin * 9; pf.s_co = 1; pf.s_ci = 9; pf.scale = 1.f;
+        if (encoder) {                                               // forward only
+            std::vector<PackArgs> packs{pf};
+            if (precise) { c.f.w_lo = (bf16_t*)arena.alloc((size_t)CoutN * c.f.K * 2); PackArgs lf = pf; lf.dst = c.f.w_lo; lf.lo_part = 1; packs.push_back(lf); }
+            add_slot(n + ".weight", {Cout, Cin, 3, 3}, packs);
+            add_slot(n + ".bias", {Cout}, {pk_vec(c.f.b, Cout)});
+            return c;
+        }
+        c.b.N = CinN; c.b.K = 9 * c.coutP; c.b.w = (bf16_t*)arena.alloc((size_t)CinN * c.b.K * 2);
         PackArgs pb{}; pb.dst = c.b.w; pb.rows = Cin; pb.cols = c.b.K; pb.ld_dst = c.b.K; pb.row_map = PACK_ROWS_ID; pb.c_inner = c.coutP;
         pb.ci_valid = Cout; pb.s_r = 9; pb.s_co = -1; pb.s_ci = (long)Cin * 9; pb.s_base = 8; pb.scale = 1.f;
         std::vector<PackArgs> packs{pf, pb};
@@ -122,17 +139,22 @@ struct rt_vae {
     // Linear / 1x1 conv [N, K]: forward as is, backward-data transposed [K, N]
     VLin mk_lin(const std::string& n, int K, int N, bool conv1x1, bool bias = true) {
         VLin l; l.f.N = N; l.f.K = K; l.f.w = (bf16_t*)arena.alloc((size_t)N * K * 2);
-        l.b.N = K; l.b.K = N; l.b.w = (bf16_t*)arena.alloc((size_t)N * K * 2);
         PackArgs pf{}; pf.dst = l.f.w; pf.rows = N; pf.cols = K; pf.ld_dst = K; pf.row_map = PACK_ROWS_ID; pf.c_inner = K; pf.ci_valid = K;
         pf.s_r = K; pf.s_ci = 1; pf.scale = 1.f;
-        PackArgs pb{}; pb.dst = l.b.w; pb.rows = K; pb.cols = N; pb.ld_dst = N; pb.row_map = PACK_ROWS_ID; pb.c_inner = N; pb.ci_valid = N;
-        pb.s_r = 1; pb.s_ci = K; pb.scale = 1.f;
         std::vector<int64_t> shp = conv1x1 ? std::vector<int64_t>{N, K, 1, 1} : std::vector<int64_t>{N, K};
-        std::vector<PackArgs> packs{pf, pb};
-        if (precise) {
-            l.f.w_lo = (bf16_t*)arena.alloc((size_t)N * K * 2); l.b.w_lo = (bf16_t*)arena.alloc((size_t)N * K * 2);
-            PackArgs lf = pf; lf.dst = l.f.w_lo; lf.lo_part = 1; PackArgs lb = pb; lb.dst = l.b.w_lo; lb.lo_part = 1;
-            packs.push_back(lf); packs.push_back(lb);
+        std::vector<PackArgs> packs{pf};
+        if (encoder) {                                               // forward only
+            if (precise) { l.f.w_lo = (bf16_t*)arena.alloc((size_t)N * K * 2); PackArgs lf = pf; lf.dst = l.f.w_lo; lf.lo_part = 1; packs.push_back(lf); }
+        } else {
+            l.b.N = K; l.b.K = N; l.b.w = (bf16_t*)arena.alloc((size_t)N * K * 2);
+            PackArgs pb{}; pb.dst = l.b.w; pb.rows = K; pb.cols = N; pb.ld_dst = N; pb.row_map = PACK_ROWS_ID; pb.c_inner = N; pb.ci_valid = N;
+            pb.s_r = 1; pb.s_ci = K; pb.scale = 1.f;
+            packs.push_back(pb);
+            if (precise) {
+                l.f.w_lo = (bf16_t*)arena.alloc((size_t)N * K * 2); l.b.w_lo = (bf16_t*)arena.alloc((size_t)N * K * 2);
+                PackArgs lf = pf; lf.dst = l.f.w_lo; lf.lo_part = 1; PackArgs lb = pb; lb.dst = l.b.w_lo; lb.lo_part = 1;
+                packs.push_back(lf); packs.push_back(lb);
+            }
         }
         add_slot(n + ".weight", shp, packs);
         if (bias) { l.f.b = (float*)arena.alloc((size_t)N * 4); add_slot(n + ".bias", {N}, {pk_vec(l.f.b, N)}); }
@@ -147,10 +169,21 @@ struct rt_vae {
         if (r.has_sc) r.sc = mk_lin(n + ".conv_shortcut", cin, cout, true);
         return r;
     }
+    // the mid block (resnet, single-head attention, resnet) at `top` channels under `prefix` ("decoder" / "encoder")
+    void mk_mid(const std::string& prefix, int top) {
+        mid0 = mk_res(prefix + ".mid_block.resnets.0", top, top);
+        const std::string a = prefix + ".mid_block.attentions.0";
+        attn.C = top;
+        attn.gn = mk_norm(a + ".group_norm", top);
+        attn.q = mk_lin(a + ".to_q", top, top, false); attn.k = mk_lin(a + ".to_k", top, top, false);
+        attn.v = mk_lin(a + ".to_v", top, top, false); attn.o = mk_lin(a + ".to_out.0", top, top, false);
+        mid1 = mk_res(prefix + ".mid_block.resnets.1", top, top);
+    }
     void build_plan() {
-        slots.clear(); slot_index.clear(); up_res.clear(); up_conv.clear();
+        slots.clear(); slot_index.clear(); up_res.clear(); up_conv.clear(); down_res.clear(); down_conv.clear();
         G = cfg.norm_groups;
         precise = cfg.precise != 0;
+        if (encoder) { build_encoder_plan(); return; }
         const int n = cfg.n_blocks;
         zero = (bf16_t*)arena.alloc(256);
         pq_w = (float*)arena.alloc(16 * 4); pq_b = (float*)arena.alloc(4 * 4);
@@ -159,13 +192,7 @@ struct rt_vae {
         add_slot("post_quant_conv.bias", {4}, {pk_vec(pq_b, 4)});
         const int top = cfg.block_out_channels[n - 1];
         conv_in = mk_conv3("decoder.conv_in", 4, top);
-        mid0 = mk_res("decoder.mid_block.resnets.0", top, top);
-        const std::string a = "decoder.mid_block.attentions.0";
-        attn.C = top;
-        attn.gn = mk_norm(a + ".group_norm", top);
-        attn.q = mk_lin(a + ".to_q", top, top, false); attn.k = mk_lin(a + ".to_k", top, top, false);
-        attn.v = mk_lin(a + ".to_v", top, top, false); attn.o = mk_lin(a + ".to_out.0", top, top, false);
-        mid1 = mk_res("decoder.mid_block.resnets.1", top, top);
+        mk_mid("decoder", top);
         int out_c = top;
         for (int i = 0; i < n; ++i) {
             const int prev = out_c; out_c = cfg.block_out_channels[n - 1 - i];
@@ -177,6 +204,30 @@ struct rt_vae {
         }
         norm_out = mk_norm("decoder.conv_norm_out", cfg.block_out_channels[0]);
         conv_out = mk_conv3("decoder.conv_out", cfg.block_out_channels[0], 3);
+    }
+    // Encoder (diffusers 0.18.2 Encoder, restated): conv_in 3 -> boc[0]; down block i = layers_per_block resnets (+ Downsample2D(padding=0)
+    // but the last); mid block; GroupNorm + SiLU; conv_out boc[-1] -> 8; quant_conv 1x1 8 -> 8
+    void build_encoder_plan() {
+        const int n = cfg.n_blocks;
+        zero = (bf16_t*)arena.alloc(256);
+        conv_in = mk_conv3("encoder.conv_in", 3, cfg.block_out_channels[0]);
+        int out_c = cfg.block_out_channels[0];
+        for (int i = 0; i < n; ++i) {
+            const int prev = out_c; out_c = cfg.block_out_channels[i];
+            std::vector<VRes> rs;
+            for (int j = 0; j < cfg.layers_per_block; ++j)
+                rs.push_back(mk_res("encoder.down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), j == 0 ? prev : out_c, out_c));
+            down_res.push_back(rs);
+            if (i != n - 1) down_conv.push_back(mk_conv3("encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv", out_c, out_c));
+        }
+        const int top = cfg.block_out_channels[n - 1];
+        mk_mid("encoder", top);
+        norm_out = mk_norm("encoder.conv_norm_out", top);
+        conv_out = mk_conv3("encoder.conv_out", top, 8);
+        qc_w = (float*)arena.alloc(64 * 4); qc_b = (float*)arena.alloc(8 * 4);
+        { PackArgs p{}; p.dst = qc_w; p.dst_f32 = 1; p.rows = 8; p.cols = 8; p.ld_dst = 8; p.row_map = PACK_ROWS_ID; p.c_inner = 8; p.ci_valid = 8;
+          p.s_r = 8; p.s_ci = 1; p.scale = 1.f; add_slot("quant_conv.weight", {8, 8, 1, 1}, {p}); }
+        add_slot("quant_conv.bias", {8}, {pk_vec(qc_b, 8)});
     }
     void require_bound() { for (auto& s : slots) if (!s.bound) throw rt_error(RT_E_MISSING_WEIGHT, "vae weight not bound: " + s.name); }
 
@@ -194,6 +245,7 @@ struct rt_vae {
                const bf16_t* in_lo = nullptr, const bf16_t* W_lo = nullptr, bf16_t* pair_lo = nullptr) {
         int Ho = H, Wo = Wd;
         if (mode == A_CONV3_UP2) { Ho = 2 * H; Wo = 2 * Wd; }
+        if (mode == A_CONV3_S2P0) { Ho = H / 2; Wo = Wd / 2; }
         GemmArgs g{}; g.A = in; g.W = W; g.bias = bias; g.out = out; g.res = res; g.zero = zero; g.mode = mode; g.epi = epi;
         g.A_lo = in_lo; g.W_lo = W_lo; g.pair_lo = pair_lo;
         g.M = Ho * Wo; g.N = N; g.K = K; g.ldw = K; g.ldo = N; g.ldres = N; g.rows_per_batch = Ho * Wo; g.Hin = H; g.Win = Wd; g.Cin = CinP;
@@ -401,6 +453,33 @@ struct rt_vae {
         if (tp) { tp->last_x = x; tp->part_out = part; tp->Hi = H; tp->Wi = W; }
         return img;
     }
+    // ---------------------------------------------------------------- encoder forward: image [3, H, W] -> moments [8, H/8, W/8]
+    void encode_fwd(const float* img, int H, int W, float in_scale, float in_shift, float* moments) {
+        const size_t HW = (size_t)H * W;
+        BT x8 = bt(HW * 8);
+        if (!dry) launch_image_in(img, in_scale, in_shift, x8.hi, x8.lo, (int)HW, stream);
+        float* x = f32(HW * conv_in.f.N);
+        conv_f32(x8, A_CONV3, conv_in.f, H, W, 8, x);
+        for (size_t i = 0; i < down_res.size(); ++i) {
+            for (auto& r : down_res[i]) x = res_fwd(r, x, H, W, nullptr);
+            if (i + 1 < down_res.size()) {
+                const int C = down_conv[i].cin;
+                BT xb = castb(x, (size_t)H * W * C);
+                float* y = f32((size_t)(H / 2) * (W / 2) * C);
+                conv_f32(xb, A_CONV3_S2P0, down_conv[i].f, H, W, C, y);
+                H /= 2; W /= 2; x = y;
+            }
+        }
+        x = res_fwd(mid0, x, H, W, nullptr);
+        x = attn_fwd(x, H * W, nullptr);
+        x = res_fwd(mid1, x, H, W, nullptr);
+        const int top = attn.C;
+        BT hn = bt((size_t)H * W * top);
+        gn_fwd(x, false, top, H * W, norm_out, true, hn, BT{});
+        float* mo = f32((size_t)H * W * conv_out.f.N);            // [hw, 8]: mean | logvar before quant_conv
+        conv_f32(hn, A_CONV3, conv_out.f, H, W, top, mo);
+        if (!dry) launch_quant_moments(mo, qc_w, qc_b, moments, H * W, stream);
+    }
     // d(loss)/d(z1) where z1 = post_quant_conv output, given dimg (bf16 [HWi, 8])
     float* backward(const Tape& tp, BT dimg, int h, int w) {
         int H = tp.Hi, W = tp.Wi;
@@ -440,10 +519,19 @@ static thread_local std::string g_vae_create_error;
     catch (const std::exception& ex) { (v)->err = ex.what(); return RT_E_INVALID; }
 
 static void vae_need_device(rt_vae* v) { if (!v->arena_base) throw rt_error(RT_E_STATE, "vae engine has no device (weight-table-only)"); }
+static void vae_need_role(rt_vae* v, bool encoder) {
+    if (v->encoder != encoder) throw rt_error(RT_E_STATE, encoder ? "vae: encode on a decoder handle" : "vae: decode / guidance on an encoder handle");
+}
 
 // workspace estimate by a dry run of decode + guidance at the largest latent
 static size_t vae_measure(rt_vae* v) {
     v->dry = true; v->ws_off = 0; v->ws_peak = 0;
+    if (v->encoder) {                                            // encoder: one encode of the largest image
+        v->encode_fwd(nullptr, 8 * v->cfg.latent_h, 8 * v->cfg.latent_w, 1.f, 0.f, nullptr);
+        v->dry = false;
+        const size_t peak = v->ws_peak; v->ws_off = 0;
+        return peak + (1 << 20);
+    }
     rt_vae::Tape tp;
     float* img = v->forward(nullptr, nullptr, 1.f, 0.f, v->cfg.latent_h, v->cfg.latent_w, &tp);
     (void)img;
@@ -454,13 +542,12 @@ static size_t vae_measure(rt_vae* v) {
     return peak + (1 << 20);
 }
 
-extern "C" {
-int rt_vae_create(const rt_vae_config* cfg, int device, rt_vae** out) {
+static int vae_create(const rt_vae_config* cfg, int device, bool encoder, rt_vae** out) {
     rt_vae* v = nullptr;
     try {
         RT_REQUIRE(cfg && out, "rt_vae_create: null argument");
         RT_REQUIRE(cfg->n_blocks >= 2 && cfg->n_blocks <= 4 && cfg->layers_per_block >= 1, "rt_vae_create: bad config");
-        v = new rt_vae(); v->cfg = *cfg; v->device = device;
+        v = new rt_vae(); v->cfg = *cfg; v->device = device; v->encoder = encoder;
         v->arena = Arena2(); v->build_plan();
         v->arena_bytes = v->arena.off + 256;
         int ndev = 0;
@@ -475,6 +562,10 @@ int rt_vae_create(const rt_vae_config* cfg, int device, rt_vae** out) {
         *out = v; return RT_OK;
     } catch (const std::exception& ex) { g_vae_create_error = ex.what(); delete v; return RT_E_INVALID; }
 }
+
+extern "C" {
+int rt_vae_create(const rt_vae_config* cfg, int device, rt_vae** out) { return vae_create(cfg, device, false, out); }
+int rt_vae_encoder_create(const rt_vae_config* cfg, int device, rt_vae** out) { return vae_create(cfg, device, true, out); }
 int rt_vae_destroy(rt_vae* v) {
     if (!v) return RT_OK;
     if (v->arena_base) { (void)hipSetDevice(v->device); (void)hipStreamSynchronize(v->stream); (void)hipFree(v->arena_base); (void)hipFree(v->ws_base); (void)hipStreamDestroy(v->stream); }
@@ -516,7 +607,7 @@ int rt_vae_arena_mark_bound(rt_vae* v) { for (auto& s : v->slots) s.bound = true
 
 int rt_vae_decode(rt_vae* v, const float* latents, int h, int w, int divide_by_scaling, float* img_out) {
     VAE_TRY(v, {
-        vae_need_device(v); v->require_bound();
+        vae_need_device(v); vae_need_role(v, false); v->require_bound();
         v->ws_off = 0;
         const float c = divide_by_scaling ? 1.f / v->cfg.scaling_factor : 1.f;
         float* img = v->forward(latents, nullptr, c, 0.f, h, w, nullptr);
@@ -528,7 +619,7 @@ int rt_vae_decode(rt_vae* v, const float* latents, int h, int w, int divide_by_s
 int rt_vae_color_guidance(rt_vae* v, float* latents, const float* noise_pred, float alpha_t, int h, int w, const float* masks_img,
                           const float* target_rgb_host, int n_regions, float weight, const float* mask_all, float* grad_out, float* loss_out_host) {
     VAE_TRY(v, {
-        vae_need_device(v); v->require_bound();
+        vae_need_device(v); vae_need_role(v, false); v->require_bound();
         RT_REQUIRE(alpha_t > 0.f && alpha_t < 1.f, "rt_vae_color_guidance: alpha_t");
         v->ws_off = 0;
         // x0 = (lat - eps*sqrt(1-a))/sqrt(a); z0 = x0 / scaling   (predict_x0: rd.py:176-178, xl.py:955-957)
@@ -545,6 +636,28 @@ int rt_vae_color_guidance(rt_vae* v, float* latents, const float* noise_pred, fl
         float* dz = v->backward(tp, dimg, h, w);
         launch_pq_conv_bwd_update(dz, 4, v->pq_w, 1.f / (sa * sc), weight, mask_all, latents, grad_out, h * w, v->stream);
         if (loss_out_host) HIP_CHECK(hipMemcpyAsync(loss_out_host, c.loss_out, 4, hipMemcpyDeviceToHost, v->stream));
+        HIP_CHECK(hipStreamSynchronize(v->stream));
+    })
+}
+
+int rt_vae_encode(rt_vae* v, const float* img, int H, int W, float in_scale, float in_shift, float* moments_out) {
+    VAE_TRY(v, {
+        vae_need_device(v); vae_need_role(v, true); v->require_bound();
+        RT_REQUIRE(img && moments_out, "rt_vae_encode: null argument");
+        RT_REQUIRE(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H % (1 << (v->cfg.n_blocks - 1)) == 0 && W % (1 << (v->cfg.n_blocks - 1)) == 0,
+                   "rt_vae_encode: H and W must be positive multiples of 8");
+        RT_REQUIRE(H <= 8 * v->cfg.latent_h && W <= 8 * v->cfg.latent_w, "rt_vae_encode: image larger than the plan (8 latent_h x 8 latent_w)");
+        v->ws_off = 0;
+        v->encode_fwd(img, H, W, in_scale, in_shift, moments_out);
+        HIP_CHECK(hipStreamSynchronize(v->stream));
+    })
+}
+
+int rt_vae_posterior_sample(rt_vae* v, const float* moments, const float* noise, int h, int w, float scale, float* latents_out) {
+    VAE_TRY(v, {
+        vae_need_device(v); vae_need_role(v, true);
+        RT_REQUIRE(moments && noise && latents_out && h > 0 && w > 0, "rt_vae_posterior_sample: bad argument");
+        launch_posterior_sample(moments, noise, scale, latents_out, h * w, v->stream);
         HIP_CHECK(hipStreamSynchronize(v->stream));
     })
 }

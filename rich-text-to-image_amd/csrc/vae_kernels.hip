@@ -1,6 +1,7 @@
-// Kernels that exist only for the colour-guidance gradient through the VAE decoder:
+// Kernels of the VAE paths beyond the GEMMs.  The colour-guidance gradient through the decoder:
 // GroupNorm(+SiLU) backward, materialised single-head attention softmax forward/backward, 2x2 sum-pool (adjoint of
-// the nearest-2x upsample), the masked-mean colour loss and its gradient, and the tiny 1x1 post_quant_conv.
+// the nearest-2x upsample), the masked-mean colour loss and its gradient, and the tiny 1x1 post_quant_conv; for the VAE encoder
+// (encode_imgs): the image-in cast, quant_conv + the logvar clamp, and the posterior sample.
 // Every contraction (conv / linear forward and backward-data) reuses the MFMA GEMM of gemm.hip.
 #include "common.h"
 #include "vae.h"
@@ -367,5 +368,53 @@ __global__ void nhwc4_to_nchw3_kernel(const float* in, float* out, int HW) {
 }
 void launch_nhwc4_to_nchw3(const float* in, float* out, int HW, hipStream_t st) {
     hipLaunchKernelGGL(nhwc4_to_nchw3_kernel, dim3(min(4096, (HW + 255) / 256)), dim3(256), 0, st, in, out, HW);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- VAE encoder: image in, moments, posterior sample
+// image [3, HW] f32 (NCHW of one image) -> x' = a x + b as the bf16 NHWC operand [HW, 8] of encoder.conv_in (channels 3 - 7 zero);
+// out_lo: the low part of the pair (precise mode).  One 16-B store per pixel and plane.
+__global__ void image_in_kernel(const float* __restrict__ img, float a, float b, bf16_t* __restrict__ out, bf16_t* __restrict__ out_lo, int HW) {
+    for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < HW; pix += gridDim.x * blockDim.x) {
+        const float r = a * img[pix] + b, g = a * img[(size_t)HW + pix] + b, bl = a * img[(size_t)2 * HW + pix] + b;
+        uint4 q; q.x = pack_bf16x2(r, g); q.y = pack_bf16x2(bl, 0.f); q.z = 0; q.w = 0;
+        *(uint4*)(out + (size_t)pix * 8) = q;
+        if (out_lo) { uint4 l; l.x = pack_bf16x2_lo(r, g); l.y = pack_bf16x2_lo(bl, 0.f); l.z = 0; l.w = 0; *(uint4*)(out_lo + (size_t)pix * 8) = l; }
+    }
+}
+void launch_image_in(const float* img, float a, float b, bf16_t* out, bf16_t* out_lo, int HW, hipStream_t st) {
+    hipLaunchKernelGGL(image_in_kernel, dim3(min(4096, cdiv(HW, 256))), dim3(256), 0, st, img, a, b, out, out_lo, HW);
+    HIP_CHECK(hipGetLastError());
+}
+// quant_conv (1x1, 8 -> 8) in fp32 FMAs on encoder.conv_out's fp32 [HW, 8] output -> moments [8, HW] (NCHW): mean | clamp(logvar, -30, 20)
+// (DiagonalGaussianDistribution.__init__)
+__global__ void quant_moments_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b, float* __restrict__ mom, int HW) {
+    for (int pix = blockIdx.x * blockDim.x + threadIdx.x; pix < HW; pix += gridDim.x * blockDim.x) {
+        const float4 u = *(const float4*)(x + (size_t)pix * 8), v = *(const float4*)(x + (size_t)pix * 8 + 4);
+        const float z[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float o = b[k];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o += W[k * 8 + j] * z[j];
+            if (k >= 4) o = fminf(fmaxf(o, -30.f), 20.f);
+            mom[(size_t)k * HW + pix] = o;
+        }
+    }
+}
+void launch_quant_moments(const float* x, const float* W, const float* b, float* mom, int HW, hipStream_t st) {
+    hipLaunchKernelGGL(quant_moments_kernel, dim3(min(4096, cdiv(HW, 256))), dim3(256), 0, st, x, W, b, mom, HW);
+    HIP_CHECK(hipGetLastError());
+}
+// DiagonalGaussianDistribution.sample() * scale: latents [4, HW] = scale * (mean + exp(0.5 logvar) * noise), moments [8, HW]
+__global__ void posterior_sample_kernel(const float* __restrict__ mom, const float* __restrict__ noise, float scale, float* __restrict__ lat, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float std_ = expf(0.5f * mom[(size_t)n + i]);
+        const float s = __fadd_rn(mom[i], __fmul_rn(std_, noise[i]));          // (unfused: the rounding of torch's mean + std * eps)
+        lat[i] = __fmul_rn(s, scale);
+    }
+}
+void launch_posterior_sample(const float* mom, const float* noise, float scale, float* lat, int HW, hipStream_t st) {
+    hipLaunchKernelGGL(posterior_sample_kernel, dim3(min(4096, cdiv(4 * HW, 256))), dim3(256), 0, st, mom, noise, scale, lat, 4 * HW);
     HIP_CHECK(hipGetLastError());
 }

@@ -10,7 +10,7 @@ RT_MAX_LEVELS = 4
 RT_MAX_STREAMS = 16
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 SCHED_EULER, SCHED_PNDM = 0, 1
-A_DENSE, A_CONV3, A_CONV3_S2, A_CONV3_UP2 = 0, 1, 2, 3
+A_DENSE, A_CONV3, A_CONV3_S2, A_CONV3_UP2, A_CONV3_S2P0 = 0, 1, 2, 3, 4
 EPI_BF16, EPI_F32, EPI_BF16_TEMB, EPI_GEGLU, EPI_F16 = 0, 1, 2, 3, 4
 
 # UNet architectures of the two pipelines (models/region_diffusion.py:32, region_diffusion_sdxl.py:115;
@@ -73,7 +73,7 @@ _SYMBOLS = [
     "rt_op_cross_attn_block", "rt_op_gemm16_variant", "rt_op_gemm16_pick", "rt_op_split_plan", "rt_profile_read2", "rt_op_gemm_qk_vt", "rt_op_gemm_pair_pick",
     "rt_region_step_part", "rt_region_step_finish", "rt_eps_info", "rt_op_split_range",
     "rt_op_ln_gemm", "rt_op_gemm_emit_partials", "rt_op_ln_partials", "rt_op_probes_built", "rt_op_attention_units_plan",
-    "rt_plain_step_part", "rt_plain_step_finish",
+    "rt_plain_step_part", "rt_plain_step_finish", "rt_vae_encoder_create", "rt_vae_encode", "rt_vae_posterior_sample",
 ]
 
 
@@ -408,13 +408,12 @@ class RtVaeConfig(C.Structure):
                 ("precise", C.c_int)]
 
 
-class VaeDecoder:
-    """AutoencoderKL decoder on the engine: `.decode(z)` (same call surface as diffusers' `vae.decode(z).sample`) and
-    the colour-guidance update of the rich-text loop (rd.py:151-168 / xl.py:849-867).
+_VAE_ALIASES = ((".to_q.", ".query."), (".to_k.", ".key."), (".to_v.", ".value."), (".to_out.0.", ".proj_attn."))
 
-    `precise=True` runs every contraction as three bf16 MFMA passes over (hi, lo) operand pairs - fp32-class products - which is
-    what the SDXL pipeline of the reference asks of its VAE (xl.py:856 `.to(dtype=torch.float32)`); the SD pipeline decodes in the
-    checkpoint's dtype (rd.py:160) and keeps the single-pass default."""
+
+class _VaeHandle:
+    """ctypes plumbing shared by the two roles of an rt_vae handle (decoder / encoder): config, weight table, binding, lifetime."""
+    _create = "rt_vae_create"
 
     def __init__(self, cfg, latent_h, latent_w, device=0, state_dict=None, precise=False):
         self.lib = load_library()
@@ -432,7 +431,7 @@ class VaeDecoder:
         self.cfg, self.cfg_dict, self.device = c, dict(cfg), device
         self.scaling_factor = cfg["scaling_factor"]
         self.h = C.c_void_p()
-        rc = self.lib.rt_vae_create(C.byref(c), device, C.byref(self.h))
+        rc = getattr(self.lib, self._create)(C.byref(c), device, C.byref(self.h))
         if rc != 0:
             raise RtError(rc, self.lib.rt_vae_last_error(None).decode())
         if state_dict is not None:
@@ -464,10 +463,15 @@ class VaeDecoder:
         return out
 
     def load_state_dict(self, sd):
+        """Binds the handle's weights from `sd` (AutoencoderKL state-dict names; keys of the other role are ignored)."""
         import torch
         dev = f"cuda:{self.device}"
         for name, _ in self.weight_table():
-            t = sd[name].to(dev).contiguous()
+            key = name
+            if key not in sd:                       # pre-0.18 AttentionBlock names of older checkpoints
+                for new, old in _VAE_ALIASES:
+                    key = key.replace(new, old)
+            t = sd[key].to(dev).contiguous()
             dt = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}[t.dtype]
             shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
             self._chk(self.lib.rt_vae_bind_weight(self.h, name.encode(), _ptr(t), dt, shape, t.dim()))
@@ -483,6 +487,15 @@ class VaeDecoder:
 
     def synchronize(self):
         self._chk(self.lib.rt_vae_synchronize(self.h))
+
+
+class VaeDecoder(_VaeHandle):
+    """AutoencoderKL decoder on the engine: `.decode(z)` (same call surface as diffusers' `vae.decode(z).sample`) and
+    the colour-guidance update of the rich-text loop (rd.py:151-168 / xl.py:849-867).
+
+    `precise=True` runs every contraction as three bf16 MFMA passes over (hi, lo) operand pairs - fp32-class products - which is
+    what the SDXL pipeline of the reference asks of its VAE (xl.py:856 `.to(dtype=torch.float32)`); the SD pipeline decodes in the
+    checkpoint's dtype (rd.py:160) and keeps the single-pass default."""
 
     def decode(self, z, divide_by_scaling=False):
         """z [1,4,h,w] -> image [1,3,8h,8w] in [-1,1]"""
@@ -521,3 +534,59 @@ class VaeDecoder:
                                                  tgt_arr, n, C.c_float(float(weight)), _ptr(mall),
                                                  _ptr(grad), C.byref(loss)))
         return loss.value, grad
+
+
+class VaeEncoder(_VaeHandle):
+    """AutoencoderKL encoder + quant_conv on the engine (diffusers 0.18.2 call surface: `encode(x).latent_dist.sample()`), for
+    RegionDiffusion.encode_imgs (rd.py:238-246).  The plan takes images up to 8 latent_h x 8 latent_w (H, W multiples of 8);
+    `state_dict` may be a full AutoencoderKL state dict: only its `encoder.*` / `quant_conv.*` keys are read.  `precise` as VaeDecoder."""
+    _create = "rt_vae_encoder_create"
+
+    def __init__(self, cfg, latent_h, latent_w, device=0, state_dict=None, precise=False):
+        if cfg.get("latent_channels", 4) != 4:
+            raise ValueError("VaeEncoder: latent_channels must be 4")
+        self.factor = 2 ** (len(cfg["block_out_channels"]) - 1)
+        super().__init__(cfg, latent_h, latent_w, device, state_dict, precise)
+
+    def encode(self, x, in_scale=1.0, in_shift=0.0):
+        """x [B,3,H,W] -> object with `.latent_dist` (DiagonalGaussianDistribution of the moments of in_scale * x + in_shift).
+        One image per rt_vae_encode call."""
+        import torch
+        x = x.to(f"cuda:{self.device}").float().contiguous()
+        B, ch, H, W = x.shape
+        if ch != 3:
+            raise ValueError(f"VaeEncoder.encode: expected [B, 3, H, W], got {tuple(x.shape)}")
+        mom = torch.empty(B, 8, H // self.factor, W // self.factor, device=x.device)
+        for b in range(B):
+            self._chk(self.lib.rt_vae_encode(self.h, _ptr(x[b]), H, W, C.c_float(float(in_scale)), C.c_float(float(in_shift)), _ptr(mom[b])))
+        return EncoderOutput(DiagonalGaussianDistribution(self, mom))
+
+
+class DiagonalGaussianDistribution:
+    """diffusers' posterior over the moments [B, 8, h, w] (mean | logvar clamped to [-30, 20] by the encode kernel)."""
+
+    def __init__(self, encoder, moments):
+        self.encoder, self.moments = encoder, moments
+        self.mean, self.logvar = moments[:, :4], moments[:, 4:]
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, generator=None, scale=1.0):
+        """scale * (mean + exp(0.5 logvar) * eps), eps from ONE torch.randn call for the batch (diffusers' randn_tensor: drawn on the
+        generator's device and moved)."""
+        import torch
+        dev = self.moments.device
+        gdev = generator.device if generator is not None else dev
+        eps = torch.randn(self.mean.shape, generator=generator, device=gdev, dtype=torch.float32).to(dev).contiguous()
+        B, _, h, w = self.mean.shape
+        out = torch.empty(B, 4, h, w, device=dev)
+        for b in range(B):
+            self.encoder._chk(self.encoder.lib.rt_vae_posterior_sample(self.encoder.h, _ptr(self.moments[b]), _ptr(eps[b]), h, w,
+                                                                       C.c_float(float(scale)), _ptr(out[b])))
+        return out
+
+
+class EncoderOutput:
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist

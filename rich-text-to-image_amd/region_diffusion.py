@@ -9,12 +9,14 @@ from .unet import HipUNet2DConditionModel
 
 class RegionDiffusion:
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
-                 latent_hw=None):
+                 latent_hw=None, vae_dir=None, vae_encoder=None):
         """`RegionDiffusion(device)` as sample.py:26-27 calls it: the reference loads runwayml/stable-diffusion-v1-5 there
         (rd.py:26-33); here the same id is resolved to a local diffusers-layout directory (checkpoint.resolve_checkpoint:
         `load_path` directory / $RTDIFF_SD_PATH / the Hugging Face hub cache) and UNet, VAE decoder, tokenizer and text encoder are
         loaded from it.  Callers that hold the weights already pass `unet_state_dict` (reference key names) and, optionally, VAE /
-        CLIP objects with the diffusers / transformers call surface (`.decode(z).sample`, tokenizer(...), text_encoder(ids)[0])."""
+        CLIP objects with the diffusers / transformers call surface (`.decode(z).sample`, tokenizer(...), text_encoder(ids)[0]).
+        `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
+        `vae_dir` on its first call."""
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device(f"cuda:{self.device_index}")
         self.num_train_timesteps = 1000
@@ -23,7 +25,10 @@ class RegionDiffusion:
             comp = load_components(resolve_checkpoint(load_path, "SD"), "SD", self.device_index, latent_hw)
             unet_state_dict, config = comp["unet_state_dict"], config or comp["config"]
             vae, tokenizer, text_encoder = vae or comp["vae"], tokenizer or comp["tokenizer"], text_encoder or comp["text_encoder"]
+            vae_dir = vae_dir or comp["vae_dir"]
         self.vae, self.tokenizer, self.text_encoder = vae, tokenizer, text_encoder
+        self.vae_dir, self.vae_encoder = vae_dir, vae_encoder
+        self._lazy_encoder = None                  # (encoder built from vae_dir, or None: no encoder weights there)
         self.unet = HipUNet2DConditionModel(config or SD15_CONFIG, unet_state_dict, self.device_index)
         self.scheduler = PNDMTables(self.num_train_timesteps)          # rd.py:35-36
         self.alphas_cumprod = torch.tensor(self.scheduler.alphas_cumprod)
@@ -59,14 +64,33 @@ class RegionDiffusion:
                 out.append(self.text_encoder(ti.input_ids.to(self.device))[0])
         return out
 
-    # rd.py:238-246 - the VAE *encoder* is not on the rich-text path (nothing in the reference calls encode_imgs; only the
-    # decoder is built here): callers that pass a VAE object with `.encode` still get the reference behaviour
+    # rd.py:238-246.  In order: a VAE object with `.encode` (the reference behaviour), the `vae_encoder` given to the constructor, an
+    # encoder built from `vae_dir` on the first call (sized to the largest image seen: rebuilt when a larger one arrives; the rich-text
+    # flow never encodes, so it pays nothing for this), else NotImplementedError.  The 2x - 1 and the 0.18215 run in the HIP kernels.
     def encode_imgs(self, imgs):
-        if not hasattr(self.vae, "encode"):
-            raise NotImplementedError("encode_imgs needs a VAE with an encoder (diffusers AutoencoderKL call surface); the engine's "
-                                      "VaeDecoder covers decode + colour guidance only - encode_imgs is unused by the rich-text flow")
-        imgs = 2 * imgs - 1
-        return self.vae.encode(imgs).latent_dist.sample() * 0.18215
+        if hasattr(self.vae, "encode"):
+            imgs = 2 * imgs - 1
+            return self.vae.encode(imgs).latent_dist.sample() * 0.18215
+        enc = self.vae_encoder or self._encoder_from_dir(imgs.shape[-2], imgs.shape[-1])
+        if enc is None:
+            raise NotImplementedError("encode_imgs needs VAE encoder weights: a VAE with `.encode`, `vae_encoder=`, or an AutoencoderKL "
+                                      "directory whose weights hold `encoder.*` (this one is decoder-only)")
+        return enc.encode(imgs, in_scale=2.0, in_shift=-1.0).latent_dist.sample(scale=0.18215)
+
+    def _encoder_from_dir(self, H, W):
+        if self.vae_dir is None:
+            return None
+        lat = (-(-H // 8), -(-W // 8))
+        if self._lazy_encoder is not None:
+            enc = self._lazy_encoder[0]
+            if enc is None or (lat[0] <= enc.cfg.latent_h and lat[1] <= enc.cfg.latent_w):
+                return enc
+            lat = (max(lat[0], enc.cfg.latent_h), max(lat[1], enc.cfg.latent_w))
+            enc.close()
+        from .checkpoint import load_vae_encoder
+        enc = load_vae_encoder(self.vae_dir, "SD", self.device_index, lat, precise=getattr(self.vae, "precise", False))
+        self._lazy_encoder = (enc,)
+        return enc
 
     # rd.py:86-174
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
