@@ -31,7 +31,9 @@ extern "C" {
 #define RT_MAX_STREAMS 16
 
 enum { RT_DTYPE_F32 = 0, RT_DTYPE_F16 = 1, RT_DTYPE_BF16 = 2 };
-enum { RT_SCHED_EULER = 0, RT_SCHED_PNDM = 1 };
+/* RT_SCHED_DPMPP_1 / _2: DPM-Solver++ (multistep, midpoint, epsilon prediction, lower-order final step) of order 1 / 2; either
+ * UNet family, no input scaling, the x0 history of each stream kept in the engine */
+enum { RT_SCHED_EULER = 0, RT_SCHED_PNDM = 1, RT_SCHED_DPMPP_1 = 2, RT_SCHED_DPMPP_2 = 3 };
 
 /* Architecture of the UNet: the constructor arguments of UNet2DConditionModel that SD-v1.5 / SDXL use
  * (models/unet_2d_condition.py:160-215). */
@@ -82,7 +84,8 @@ int rt_set_prompts(rt_engine* e, const float* prompt_embeds, const float* pooled
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
 /* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables */
 int rt_set_fontsize(rt_engine* e, const int64_t* word_pos_host, const float* font_size_host, int n);
-/* scheduler tables (HOST arrays): Euler: sigmas[n+1], timesteps[n]; PNDM: alphas_cumprod[1000], timesteps[n_iter] */
+/* scheduler tables (HOST arrays): Euler: sigmas[n+1], timesteps[n]; PNDM: alphas_cumprod[1000], timesteps[n_iter];
+ * DPM-Solver++: alphas_cumprod[1000], timesteps[n] (integers, descending) */
 int rt_set_schedule(rt_engine* e, int kind, const float* timesteps_host, int n_timesteps, const float* table_host,
                     int n_table, int num_inference_steps);
 /* sampler state: latents [1,4,h,w] f32 (copied in); the reference stream starts as a clone (rd.py:93, xl.py:774) */

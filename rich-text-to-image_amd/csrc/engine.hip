@@ -134,6 +134,9 @@ static inline bool g_store_own_stats_flag() { return g_store_own_stats != 0; }
 // step epilogue kernels (defined in step.hip)
 struct StepArgs;
 void launch_step_epilogue(const StepArgs& a, hipStream_t st);
+struct DpmArgs;
+void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st);
+static inline bool rt_sched_is_dpm(int kind) { return kind == RT_SCHED_DPMPP_1 || kind == RT_SCHED_DPMPP_2; }
 void launch_gather_add_rows(const float* base, const float* table, const int* /*host*/ idx, float* out, int B, int C, hipStream_t st);
 void launch_inject_add(f16_t* out, const f16_t* sc, const float* hres, const int* /*host*/ src, int B, size_t per_batch, hipStream_t st);
 void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_t st);
@@ -190,13 +193,14 @@ struct rt_engine {
     float* lat_ref = nullptr;
     float* noise_pred = nullptr;     // [4, HW] CFG-combined prediction of the last step (guidance input)
     float* eps = nullptr;            // [maxB, HW, 4]
-    float* ets = nullptr;            // PNDM history [4][2][4*HW]
+    float* ets = nullptr;            // PNDM history [4][2][4*HW]; DPM-Solver++ uses slots 0 / 1 as the x0 history of the two streams
     float* cur_sample = nullptr;     // PNDM [2][4*HW]
     int lat_h = 0, lat_w = 0;
     // schedule (host)
     int sched_kind = 0, num_inference_steps = 0;
     std::vector<float> timesteps, table;
     int pndm_counter = 0, pndm_nets = 0, pndm_head = 0;
+    int dpm_lower_order_nums = 0, dpm_head = 0;     // DPM-Solver++: steps taken (capped at 2), history slot this step writes
     int steps_done = 0;
 
     // optional per-launch HIP-event profiling of the MFMA kernels (bench.py roofline leg)
@@ -1129,11 +1133,18 @@ int rt_set_masks(rt_engine* e, const float* m, int R, int h, int w) {
 int rt_set_fontsize(rt_engine* e, const int64_t* wp, const float* fs, int n) { RT_TRY(e, { need_device(e); e->set_fontsize(wp, fs, n); }) }
 int rt_set_schedule(rt_engine* e, int kind, const float* ts, int nts, const float* table, int ntab, int nsteps) {
     RT_TRY(e, {
-        RT_REQUIRE(kind == RT_SCHED_EULER || kind == RT_SCHED_PNDM, "rt_set_schedule: kind");
+        RT_REQUIRE(kind == RT_SCHED_EULER || kind == RT_SCHED_PNDM || rt_sched_is_dpm(kind), "rt_set_schedule: kind");
+        if (kind == RT_SCHED_EULER) RT_REQUIRE(ntab == nts + 1, "euler: need n+1 sigmas");
+        if (rt_sched_is_dpm(kind)) {
+            RT_REQUIRE(ntab == 1000 && nts >= 1, "dpm-solver++: need alphas_cumprod[1000] and at least one timestep");
+            for (int k = 0; k < nts; ++k)
+                RT_REQUIRE(ts[k] >= 0.f && ts[k] < 1000.f && ts[k] == (float)(int)ts[k] && (k == 0 || ts[k] < ts[k - 1]),
+                           "dpm-solver++: timesteps must be distinct integers in [0, 1000), descending");
+        }
         e->sched_kind = kind; e->num_inference_steps = nsteps;
         e->timesteps.assign(ts, ts + nts); e->table.assign(table, table + ntab);
-        if (kind == RT_SCHED_EULER) RT_REQUIRE(ntab == nts + 1, "euler: need n+1 sigmas");
         e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
+        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
     })
 }
 int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
@@ -1145,6 +1156,7 @@ int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
         HIP_CHECK(hipMemcpyAsync(e->lat_ref, l, n, hipMemcpyDeviceToDevice, e->stream));
         e->lat_h = h; e->lat_w = w;
         e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
+        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
     })
 }
 int rt_get_latents(rt_engine* e, float* out, float* out_ref) {

@@ -1,6 +1,6 @@
 // a11 + a12 + a14 of SURVEY.md section 8a: mask-weighted region combine (models/region_diffusion.py:119-132,
 // models/region_diffusion_sdxl.py:810-825), classifier-free guidance, scheduler update (third-party
-// diffusers 0.18.2 PNDM/PLMS and Euler restated, see oracle/schedulers.py) and background blend
+// diffusers 0.18.2 PNDM/PLMS and Euler restated, see oracle/schedulers.py; DPM-Solver++ in a second kernel) and background blend
 // (rd.py:171-173, xl.py:870-872) fused into one elementwise launch over 4*h*w elements.
 // The arithmetic follows the reference's fp32 operation order so that the epilogue itself is exact.
 #include "step.h"
@@ -84,8 +84,96 @@ __global__ void step_epilogue_kernel(StepArgs p) {
         if (has_ref) p.lat_ref[li] = lr;
     }
 }
+// DPM-Solver++ epilogue (diffusers 0.18.2 DPMSolverMultistepScheduler: dpmsolver++, midpoint, epsilon; [memory], see
+// tests/dpm_solver_ref.py).  A kernel of its own so that step_epilogue_kernel above keeps its code unchanged (an inlined shared body
+// reorders its instructions and moves its SGPR count; profiles/dpm_epilogue_isa_diff.txt): the combine + CFG head and the blend / store
+// tail below are step_epilogue_kernel's, only the scheduler update differs.
+__device__ __forceinline__ bool step_combine(const StepArgs& p, int pix, float (&e)[4], float (&er)[4]) {
+    auto ld4 = [&](int s) { return *(const float4*)(p.eps + ((size_t)s * p.HW + pix) * 4); };
+    const float4 eu = ld4(p.s_uncond), eb = ld4(p.s_base);
+    const float euv[4] = {eu.x, eu.y, eu.z, eu.w}, ebv[4] = {eb.x, eb.y, eb.z, eb.w};
+    if (p.plain) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = euv[c] + p.g * (ebv[c] - euv[c]);
+    } else {
+        float nu[4], nt[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float ml = p.masks[((size_t)(p.R - 1) * 4 + c) * p.HW + pix];
+            nu[c] = euv[c] * ml; nt[c] = ebv[c] * ml;
+        }
+        for (int r = 0; r < p.R - 1; ++r) {
+            const float4 q = ld4(p.s_region[r]);
+            const float qv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float m = p.masks[((size_t)r * 4 + c) * p.HW + pix];
+                nu[c] = nu[c] + euv[c] * m; nt[c] = nt[c] + qv[c] * m;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = nu[c] + p.g * (nt[c] - nu[c]);
+    }
+    if (p.noise_pred) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) p.noise_pred[(size_t)c * p.HW + pix] = e[c];
+    }
+    const bool has_ref = p.s_uref >= 0 && p.step_ref;
+    if (has_ref) {
+        const float4 a = ld4(p.s_uref), b = ld4(p.s_tref);
+        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) er[c] = av[c] + p.g * (bv[c] - av[c]);
+    }
+    return has_ref;
+}
+__device__ __forceinline__ void step_store(const StepArgs& p, int pix, const float (&newv)[2][4], bool has_ref) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const size_t li = (size_t)c * p.HW + pix;
+        float l = newv[0][c];
+        const float lr = has_ref ? newv[1][c] : p.lat_ref[li];
+        if (p.blend) {
+            const float ml = p.masks[((size_t)(p.R - 1) * 4 + c) * p.HW + pix];
+            l = lr * ml + l * (1.f - ml);
+        }
+        p.lat[li] = l;
+        if (has_ref) p.lat_ref[li] = lr;
+    }
+}
+// Per stream, in diffusers' fp32 operation order: this step's x0 goes to the stream's history slot ets[0]; m1 (the stream's x0 of the
+// previous step) comes from ets[1] in the same pass.
+__global__ void step_epilogue_dpm_kernel(StepArgs p, DpmArgs d) {
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= p.HW) return;
+    float e[4], er[4];
+    const bool has_ref = step_combine(p, pix, e, er);
+    float newv[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (s == 1 && !has_ref) break;
+        const float* x = s == 0 ? p.lat : p.lat_ref;
+        const float* ee = s == 0 ? e : er;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const size_t li = (size_t)c * p.HW + pix;
+            const size_t hi = (size_t)s * 4 * p.HW + li;
+            const float sample = x[li];
+            const float x0 = (sample - d.sigma_s0 * ee[c]) / d.alpha_s0;
+            float v = d.ratio * sample - d.c1 * x0;
+            if (d.order == 2) v = v - d.c2 * (d.inv_r0 * (x0 - p.ets[1][hi]));
+            p.ets[0][hi] = x0;
+            newv[s][c] = v;
+        }
+    }
+    step_store(p, pix, newv, has_ref);
+}
 void launch_step_epilogue(const StepArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(step_epilogue_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st) {
+    hipLaunchKernelGGL(step_epilogue_dpm_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -32,6 +32,40 @@ static void pndm_coeffs(rt_engine* e, int i, StepArgs& a) {
     e->pndm_counter++;
 }
 
+static void dpm_coeffs(rt_engine* e, int i, StepArgs& a, DpmArgs& d) {
+    // DPMSolverMultistepScheduler (diffusers 0.18.2, [memory]: dpmsolver++, midpoint, epsilon, lower_order_final, no thresholding);
+    // see tests/dpm_solver_ref.py.  fp32 scalars in diffusers' tensor order: alpha = sqrt(ac), sigma = sqrt(1 - ac),
+    // lambda = log(alpha) - log(sigma); s0 = t_i, s1 = t_{i-1}, p = t_{i+1} (0 after the last step).
+    RT_REQUIRE((int)e->table.size() >= 1000, "dpm-solver++: alphas_cumprod table missing");
+    const int n = (int)e->timesteps.size();
+    RT_REQUIRE(i >= 0 && i < n, "dpm-solver++: step index out of range");
+    auto alpha = [&](int t) { return std::sqrt(e->table[t]); };
+    auto sigma = [&](int t) { return std::sqrt(1.f - e->table[t]); };
+    auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
+    const int s0 = (int)e->timesteps[i], p = i == n - 1 ? 0 : (int)e->timesteps[i + 1];
+    const bool lower_order_final = i == n - 1 && n < 15;
+    const bool first = e->sched_kind == RT_SCHED_DPMPP_1 || e->dpm_lower_order_nums < 1 || lower_order_final || i == 0;
+    const float h = lambda(p) - lambda(s0);
+    d.alpha_s0 = alpha(s0); d.sigma_s0 = sigma(s0);
+    d.ratio = sigma(p) / sigma(s0);
+    d.c1 = alpha(p) * (std::exp(-h) - 1.f);
+    d.c2 = 0.5f * d.c1;
+    d.order = first ? 1 : 2;
+    d.inv_r0 = 0.f;
+    if (!first) {
+        const int s1 = (int)e->timesteps[i - 1];
+        const float r0 = (lambda(s0) - lambda(s1)) / h;
+        d.inv_r0 = 1.f / r0;
+    }
+    // two history slots per stream in the PNDM buffer ([slot][stream][4*HW]): this step writes x0 into one and reads m1 from the other.
+    // A stream that is not stepped (the reference pair once it stops) leaves its half of both slots alone and is never stepped again.
+    const size_t per = (size_t)2 * 4 * e->lat_h * e->lat_w;
+    a.ets[0] = e->ets + (size_t)e->dpm_head * per;
+    a.ets[1] = e->ets + (size_t)(e->dpm_head ^ 1) * per;
+    e->dpm_head ^= 1;
+    if (e->dpm_lower_order_nums < 2) e->dpm_lower_order_nums++;
+}
+
 // The streams of rich-text step i and the flags of its epilogue (everything of region_step that is a pure function of the schedule
 // position): `in` = the F batched forwards with their mode words, `a` = the epilogue's arguments without the scheduler coefficients
 // (PNDM's are stateful: region_finish computes them once).
@@ -42,7 +76,8 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     RT_REQUIRE(i >= 0 && i < n, "region_step: step index out of range");
     RT_REQUIRE(R >= 1 && n_prompts == R + 1, "region_step: need R masks and R+1 prompts (rd.py:96-97)");
     RT_REQUIRE(mask_hw == lat_h * lat_w && lat_h > 0, "region_step: masks/latents shape mismatch");
-    RT_REQUIRE((sched_kind == RT_SCHED_EULER) == xl, "region_step: SD uses PNDM, SDXL uses Euler");
+    RT_REQUIRE(rt_sched_is_dpm(sched_kind) || (sched_kind == RT_SCHED_EULER) == xl,
+               "region_step: SD uses PNDM or DPM-Solver++, SDXL uses Euler or DPM-Solver++");
     const float t = timesteps[i];
     const bool use_ref = isa > 0 || ibg > 0;
     // `t > (1-inject_selfattn)*1000`: torch compares a float32 / int64 tensor element with a Python float in float32
@@ -64,7 +99,7 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     if (!run_ref) step_ref = false;
 
     in = FwdIn{}; in.h = lat_h; in.w = lat_w; in.t = t; in.eps_out = eps;
-    const float scale = xl ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;
+    const float scale = sched_kind == RT_SCHED_EULER ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;   // Euler's scale_model_input
     a = StepArgs{};
     int F = 0;
     auto add = [&](const float* x, int prompt, int fs) {
@@ -93,6 +128,13 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
 // region_diffusion_sdxl.py:810-846)
 void rt_engine::region_finish(int i, StepArgs& a, bool blend_deferred) {
     pending_blend = blend_deferred;
+    if (rt_sched_is_dpm(sched_kind)) {
+        DpmArgs d{};
+        dpm_coeffs(this, i, a, d);
+        launch_step_epilogue_dpm(a, d, stream);
+        steps_done++;
+        return;
+    }
     if (sched_kind == RT_SCHED_EULER) a.dsigma = table[i + 1] - table[i];
     else pndm_coeffs(this, i, a);
     launch_step_epilogue(a, stream);
@@ -177,6 +219,13 @@ void rt_engine::plain_finish(int i, float g) {
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
     a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.sched = sched_kind; a.step_ref = 0; a.blend = 0;
+    if (rt_sched_is_dpm(sched_kind)) {
+        DpmArgs d{};
+        dpm_coeffs(this, i, a, d);
+        launch_step_epilogue_dpm(a, d, stream);
+        steps_done++;
+        return;
+    }
     if (xl) a.dsigma = table[i + 1] - table[i];
     else pndm_coeffs(this, i, a);
     launch_step_epilogue(a, stream);

@@ -3,20 +3,21 @@ on the HIP engine.  Same method names / argument meaning / attributes as the ref
 import torch
 
 from .engine import SD15_CONFIG
-from .schedulers import PNDMTables
+from .schedulers import DPMSolverTables, PNDMTables
 from .unet import HipUNet2DConditionModel
 
 
 class RegionDiffusion:
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
-                 latent_hw=None, vae_dir=None, vae_encoder=None):
+                 latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None):
         """`RegionDiffusion(device)` as sample.py:26-27 calls it: the reference loads runwayml/stable-diffusion-v1-5 there
         (rd.py:26-33); here the same id is resolved to a local diffusers-layout directory (checkpoint.resolve_checkpoint:
         `load_path` directory / $RTDIFF_SD_PATH / the Hugging Face hub cache) and UNet, VAE decoder, tokenizer and text encoder are
         loaded from it.  Callers that hold the weights already pass `unet_state_dict` (reference key names) and, optionally, VAE /
         CLIP objects with the diffusers / transformers call surface (`.decode(z).sample`, tokenizer(...), text_encoder(ids)[0]).
         `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
-        `vae_dir` on its first call."""
+        `vae_dir` on its first call.  `scheduler`: PNDMTables (the default, rd.py:35-36) or DPMSolverTables; assigning
+        `self.scheduler` later works the same way (the diffusers idiom)."""
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device(f"cuda:{self.device_index}")
         self.num_train_timesteps = 1000
@@ -30,7 +31,7 @@ class RegionDiffusion:
         self.vae_dir, self.vae_encoder = vae_dir, vae_encoder
         self._lazy_encoder = None                  # (encoder built from vae_dir, or None: no encoder weights there)
         self.unet = HipUNet2DConditionModel(config or SD15_CONFIG, unet_state_dict, self.device_index)
-        self.scheduler = PNDMTables(self.num_train_timesteps)          # rd.py:35-36
+        self.scheduler = scheduler if scheduler is not None else PNDMTables(self.num_train_timesteps)          # rd.py:35-36
         self.alphas_cumprod = torch.tensor(self.scheduler.alphas_cumprod)
         self.masks = []
         self.attention_maps = None
@@ -92,6 +93,12 @@ class RegionDiffusion:
         self._lazy_encoder = (enc,)
         return enc
 
+    def _schedule_kind(self):
+        """The engine's schedule kind of self.scheduler: SD-v1.5 runs PNDM (the reference) or DPM-Solver++, nothing else."""
+        if not isinstance(self.scheduler, (PNDMTables, DPMSolverTables)):
+            raise ValueError(f"RegionDiffusion: scheduler must be PNDMTables or DPMSolverTables, got {type(self.scheduler).__name__}")
+        return self.scheduler.kind
+
     # rd.py:86-174
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, use_guidance=False, text_format_dict={}, inject_selfattn=0, inject_background=0,
@@ -110,7 +117,7 @@ class RegionDiffusion:
         eng.set_masks([m.to(self.device) for m in self.masks])
         tfd = text_format_dict or {}
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
-        eng.set_schedule(1, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_latents(latents.to(self.device))
         for i, t in enumerate(self.scheduler.timesteps):
             if getattr(self, "split_image", False):      # intra-image split over the ranks of the process group (launcher.split_region_step)
@@ -161,7 +168,7 @@ class RegionDiffusion:
         eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts)      # R+1 forwards, +2 reference forwards
         self.scheduler.set_timesteps(num_inference_steps)
         eng.set_prompts(text_embeddings.to(self.device))
-        eng.set_schedule(1, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_latents(latents.to(self.device))
         hooks = getattr(self, "_tokenmap_hooks", False)
         if hooks:

@@ -5,7 +5,7 @@ import types
 import torch
 
 from .engine import SDXL_CONFIG
-from .schedulers import EulerTables
+from .schedulers import DPMSolverTables, EulerTables
 from .unet import HipUNet2DConditionModel
 
 
@@ -17,11 +17,12 @@ class StableDiffusionXLPipelineOutput(dict):
 
 class RegionDiffusionXL:
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
-                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None):
+                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None):
         """`RegionDiffusionXL(load_path="stabilityai/stable-diffusion-xl-base-1.0")` as sample.py:28-30 calls it (xl.py:105-120
         loads every component from `load_path`): a diffusers-layout directory, or a hub id resolved to one without a network
         (checkpoint.resolve_checkpoint: $RTDIFF_SDXL_PATH for the default id, then the Hugging Face hub cache).  Callers that hold
-        the weights pass `unet_state_dict` (+ optional vae / text_encoders / tokenizer) and `load_path` is not read."""
+        the weights pass `unet_state_dict` (+ optional vae / text_encoders / tokenizer) and `load_path` is not read.
+        `scheduler`: EulerTables (the default, xl.py:120) or DPMSolverTables; assigning `self.scheduler` later works the same way."""
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device(f"cuda:{self.device_index}")
         self.device_type = "cuda"
@@ -42,7 +43,7 @@ class RegionDiffusionXL:
         self.vae_scaling_factor = vae_scaling_factor
         self.vae_scale_factor = 8
         self.default_sample_size = 128
-        self.scheduler = EulerTables()
+        self.scheduler = scheduler if scheduler is not None else EulerTables()
         self.masks = []
         self.selfattn_maps = self.crossattn_maps = self.n_maps = None
         self.attention_maps = None                                   # xl.py:132 (only the evaluation hooks ever set it)
@@ -90,6 +91,8 @@ class RegionDiffusionXL:
             raise NotImplementedError                                                              # xl.py:827-830
         if use_guidance and not hasattr(self.vae, "color_guidance"):
             raise RuntimeError("use_guidance=True needs a rich_text_to_image_amd.engine.VaeDecoder as `vae` (xl.py:849-867)")
+        if not isinstance(self.scheduler, (EulerTables, DPMSolverTables)):
+            raise ValueError(f"RegionDiffusionXL: scheduler must be EulerTables or DPMSolverTables, got {type(self.scheduler).__name__}")
         self.scheduler.set_timesteps(num_inference_steps)
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         if latents is None:
@@ -100,7 +103,7 @@ class RegionDiffusionXL:
         pooled = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], 0).to(self.device).float()
         eng = self.unet.engine(h, w, streams=embeds.shape[0] + 2 if run_rich_text else 2, prompts=embeds.shape[0])
         eng.set_prompts(embeds, pooled, add_time_ids)
-        eng.set_schedule(0, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_latents(latents)
         n = len(self.scheduler.timesteps)
         if run_rich_text:
@@ -124,7 +127,7 @@ class RegionDiffusionXL:
                                     defer_blend=use_guidance)
                 if use_guidance:
                     t = float(self.scheduler.timesteps[i])
-                    if t < tfd['guidance_start_step']:                   # xl.py:849; predict_x0 on the unscaled Euler latents (quirk 4)
+                    if t < tfd['guidance_start_step']:                   # xl.py:849; predict_x0 on the unscaled Euler latents (quirk 4; DPM: unscaled anyway)
                         lat_ptr, eps_ptr = eng.state_ptrs()
 
                         def guide(lat_ptr=lat_ptr, eps_ptr=eps_ptr, t=t):

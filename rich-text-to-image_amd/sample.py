@@ -9,6 +9,7 @@ import json
 import os
 import sys
 import time
+import types
 
 import torch
 import torch.nn.functional as F
@@ -155,13 +156,13 @@ def build_model(a, rank=0, local_rank=0, world=1):
     hw = ((a.height or res) // 8, (a.width or res) // 8)
     if world == 1:
         if a.model == 'SD':
-            return RegionDiffusion(torch.device('cuda'), load_path=a.load_path, latent_hw=hw), 0.0
+            return apply_scheduler(RegionDiffusion(torch.device('cuda'), load_path=a.load_path, latent_hw=hw), a), 0.0
         xl_path = a.load_path or ("stabilityai/stable-diffusion-xl-base-1.0" if a.model == 'SDXL' else "Linaqruf/animagine-xl")
         model = RegionDiffusionXL(load_path=xl_path, latent_hw=hw)
         if getattr(a, 'guidance_precision', 'fp32') == 'bf16':
             from .checkpoint import load_guidance_vae, resolve_checkpoint
             model.guidance_vae = load_guidance_vae(resolve_checkpoint(xl_path, 'SDXL'), 'SDXL', 0, hw)
-        return model, 0.0
+        return apply_scheduler(model, a), 0.0
     from . import launcher
     from .checkpoint import load_components, resolve_checkpoint
     kind = 'SD' if a.model == 'SD' else 'SDXL'
@@ -175,7 +176,26 @@ def build_model(a, rank=0, local_rank=0, world=1):
         encoders = list(comp["text_encoders"].encoders)
     eng = model.unet.engine(hw[0], hw[1])                            # the engine (and its arena) must exist on every rank before the broadcast
     seconds = launcher.broadcast_pipeline(eng, model.vae, encoders, src=0)
-    return model, seconds
+    return apply_scheduler(model, a), seconds
+
+
+def make_scheduler(a):
+    """--scheduler / --solver_order -> the scheduler object to put on the pipeline (None: the pipeline's default, PNDM for SD and
+    Euler for SDXL).  A flag that cannot be honoured is an error, never ignored."""
+    from .schedulers import DPMSolverTables
+    order = getattr(a, 'solver_order', None)
+    if getattr(a, 'scheduler', 'default') == 'dpmsolver++':
+        return DPMSolverTables(solver_order=2 if order is None else order)
+    if order is not None:
+        raise SystemExit("sample: --solver_order needs --scheduler dpmsolver++")
+    return None
+
+
+def apply_scheduler(model, a):
+    sched = make_scheduler(a)
+    if sched is not None:
+        model.scheduler = sched
+    return model
 
 
 def dist_backend_is_gloo():
@@ -183,12 +203,8 @@ def dist_backend_is_gloo():
     return dist.is_initialized() and dist.get_backend() == "gloo"
 
 
-def main(argv=None):
-    """Flags of sample.py:118-133 (+ --load_path), and the seed-parallel form the reference does not have (SURVEY 8e, BASELINE
-    configs 4 / 5): `--gpus N` with several requests (`--rich_text_json A B ...`, `--seeds ...`, `--requests FILE`) re-executes itself
-    as N ranks under torch.distributed.run, rank 0 loads the checkpoint, ONE pipeline broadcast, requests dealt round-robin, every
-    rank writes its own images.  With one GPU and one request this is the reference's main()."""
-    import sys
+def build_parser():
+    """The flags of main()."""
     p = argparse.ArgumentParser()
     p.add_argument('--run_dir', type=str, default='results/')
     p.add_argument('--height', type=int, default=None)
@@ -208,6 +224,10 @@ def main(argv=None):
                    help='SDXL colour guidance: fp32 = the fp32-class VAE the reference guides with (xl.py:856; default), bf16 = the guidance pass '
                         'alone on a one-pass bf16 VAE engine (same trajectory within the bf16 noise of the UNet, 37 instead of 80 ms per step); '
                         'the final decode stays fp32-class either way')
+    p.add_argument('--scheduler', type=str, default='default', choices=['default', 'dpmsolver++'],
+                   help='default: the reference\'s sampler (PNDM for SD, Euler for SDXL / AnimeXL); dpmsolver++: DPM-Solver++ multistep '
+                        '(diffusers DPMSolverMultistepScheduler), usually run at 20-25 --sample_steps. Holds on every rank of --gpus N')
+    p.add_argument('--solver_order', type=int, default=None, choices=[1, 2], help='DPM-Solver++ order (default 2); needs --scheduler dpmsolver++')
     p.add_argument('--load_path', type=str, default=None,
                    help='diffusers-layout checkpoint directory; default: the hub ids of sample.py:26-30 resolved locally '
                         '(checkpoint.resolve_checkpoint: $RTDIFF_SD_PATH / $RTDIFF_SDXL_PATH / the Hugging Face hub cache)')
@@ -222,8 +242,19 @@ def main(argv=None):
     p.add_argument('--dry_launch', action='store_true',
                    help='exercise the launch / sharding / broadcast control path on the gloo backend with stand-in arenas and print '
                         'one JSON line per rank - no GPU, no checkpoint (tests/test_distributed_cpu.py)')
+    return p
+
+
+def main(argv=None):
+    """Flags of sample.py:118-133 (+ --load_path), and the seed-parallel form the reference does not have (SURVEY 8e, BASELINE
+    configs 4 / 5): `--gpus N` with several requests (`--rich_text_json A B ...`, `--seeds ...`, `--requests FILE`) re-executes itself
+    as N ranks under torch.distributed.run, rank 0 loads the checkpoint, ONE pipeline broadcast, requests dealt round-robin, every
+    rank writes its own images.  With one GPU and one request this is the reference's main()."""
+    import sys
+    p = build_parser()
     argv = list(sys.argv[1:] if argv is None else argv)
     a = p.parse_args(argv)
+    make_scheduler(a)                 # an unusable --scheduler / --solver_order combination fails here, before any rank starts
     from . import launcher
     err = launcher.self_launch(None, argv, a.gpus, require_gpus=not a.dry_launch, module=__spec__.name if __spec__ else "rich_text_to_image_amd.sample")
     if err is not None:
@@ -310,13 +341,16 @@ def _dry_launch(a, rank, world, reqs, mine):
     encs = [_StandInEncoder(rank == 0), _StandInEncoder(rank == 0)]
     seconds = launcher.broadcast_pipeline(unet, vae, encs, src=0)
     ref = _StandInEncoder(True)
+    sched = apply_scheduler(types.SimpleNamespace(scheduler=None), a).scheduler        # what build_model puts on this rank's pipeline
     ok = bool((unet.t == 0xA5).all() and (vae.t == 0x3C).all() and unet.bound and vae.bound and
               all(torch.equal(x, y) for e in encs for x, y in zip(e.p, ref.p)))
     # ONE write per rank (line + newline together): the ranks share the launcher's stdout pipe, and print()'s separate newline write let two
     # ranks' lines run into each other once in ~25 runs
     sys.stdout.write(json.dumps({"rank": rank, "world": world, "requests_total": len(reqs), "requests_mine": [r["index"] for r in mine],
                                  "seeds_mine": [r["seed"] for r in mine], "pipeline_received": ok, "broadcast_collectives": launcher.LAST_BROADCAST_CALLS,
-                                 "broadcast_s": seconds}) + "\n")
+                                 "broadcast_s": seconds,
+                                 "scheduler": None if sched is None else {"class": type(sched).__name__, "kind": sched.kind,
+                                                                          "solver_order": sched.solver_order}}) + "\n")
     sys.stdout.flush()
     launcher.barrier()
     if world > 1:

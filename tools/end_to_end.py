@@ -10,6 +10,9 @@
                             embeddings (no CLIP vocabulary or weights offline: the text encoders are NOT in these timings).
   two_requests(eng, ...)    two independent requests on one GPU (two engines, one HIP stream each): aggregate steps/s and per-image
                             latency, reported beside the one-request headline, never instead of it.
+
+As a command, one whole image per scheduler (`--scheduler euler dpmsolver++ --steps 50 20`: each scheduler with its step count, one
+JSON line each): `python tools/end_to_end.py --scheduler dpmsolver++ --steps 20`.
 """
 import math
 import time
@@ -133,8 +136,9 @@ RICH_TEXT = {"ops": [{"insert": "a "}, {"attributes": {"font": "slabo"}, "insert
                      {"attributes": {"link": "a wooden fence covered in snow"}, "insert": "fence"}, {"insert": "\n"}]}
 
 
-def end_to_end(eng, hw=128, steps=41, seed=6, inject_selfattn=0.5, num_segments=9, use_guidance=True, one_pass_guidance=False):
-    """sample.generate on the full SDXL architecture (the bench engine is handed to the facade: same weights, no second arena)."""
+def end_to_end(eng, hw=128, steps=41, seed=6, inject_selfattn=0.5, num_segments=9, use_guidance=True, one_pass_guidance=False, scheduler=None):
+    """sample.generate on the full SDXL architecture (the bench engine is handed to the facade: same weights, no second arena).
+    `scheduler`: the pipeline's scheduler object (None: Euler, the reference's)."""
     import sys
     import os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -149,6 +153,8 @@ def end_to_end(eng, hw=128, steps=41, seed=6, inject_selfattn=0.5, num_segments=
     m = RegionDiffusionXL(device=eng.device, unet_state_dict="random0", config=SDXL_CONFIG, vae=vae, vae_scaling_factor=SDXL_VAE_CONFIG["scaling_factor"],
                           tokenizer=_WordTokenizer(), text_encoders=_synthetic_text_encoders(dev))
     m.unet._engines[(hw, hw)] = eng
+    if scheduler is not None:
+        m.scheduler = scheduler
     if one_pass_guidance:                                            # opt-in: the guidance pass alone on a one-pass bf16 engine (LABNOTES R6.6)
         m.guidance_vae = random_vae(SDXL_VAE_CONFIG, hw, hw, precise=False)
     param = {"text_input": RICH_TEXT, "height": 8 * hw, "width": 8 * hw, "guidance_weight": 5.0, "steps": steps, "noise_index": seed, "negative_prompt": ""}
@@ -185,7 +191,9 @@ def end_to_end(eng, hw=128, steps=41, seed=6, inject_selfattn=0.5, num_segments=
     m.unet._engines = {}                                             # the engine belongs to the caller
     if m.guidance_vae is not None:
         m.guidance_vae.close(); m.guidance_vae = None
-    return dict(seconds_total=total, one_pass_guidance=bool(one_pass_guidance), plain_pass_s=t["plain"], token_maps_x2_s=t["token_maps"], rich_pass_s=t["rich"],
+    # denoising = both passes without their final decode (the colour-guidance VAE passes of the rich loop are per step: they stay in)
+    denoise = t["plain"] + t["rich"] - 2 * t_dec
+    out = dict(seconds_total=total, one_pass_guidance=bool(one_pass_guidance), plain_pass_s=t["plain"], token_maps_x2_s=t["token_maps"], rich_pass_s=t["rich"],
                 spectral_clustering_s=spent["spectral_s"], spectral_clustering_calls=spent["calls"], vae_decode_s=t_dec,
                 steps=steps, regions=n_regions, finite=fin,
                 workload=f"sample.generate (sample.py:56-113): SDXL 1024^2, {steps} steps, CFG 5.0, inject_selfattn={inject_selfattn}, "
@@ -193,6 +201,9 @@ def end_to_end(eng, hw=128, steps=41, seed=6, inject_selfattn=0.5, num_segments=
                          "include their final precise-VAE decode and the uint8 / PIL hand-off",
                 not_included="CLIP tokenizer / text encoders (no vocabulary or weights offline: synthetic embeddings), model construction "
                              f"(precise VAE build {t_vae_build:.2f} s)")
+    if scheduler is not None:              # only then: bench.py's end_to_end entry keeps its keys
+        out.update(scheduler=type(scheduler).__name__, denoising_s=denoise, denoising_share=denoise / total)
+    return out
 
 
 def two_requests(eng, make_inputs, hw, nsched, steps, gs, isa, sched_index, ts, sig, init_sigma):
@@ -244,3 +255,37 @@ def two_requests(eng, make_inputs, hw, nsched, steps, gs, isa, sched_index, ts, 
     return dict(requests=2, aggregate_steps_per_s=2 * steps / dt, per_image_ms_per_step=dt / steps * 1e3, steps=steps, finite=fin,
                 how="two engines (second weight arena = device copy of the first), one HIP stream each, stepped alternately from one host thread; "
                     "same workload per request as the headline line")
+
+
+def main(argv=None):
+    """One whole image (plain pass, token maps, rich pass, decodes) per --scheduler entry on a random-init SDXL engine; the i-th
+    scheduler runs --steps[i] steps (one value: all of them).  One JSON line per image."""
+    import argparse
+    import json
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from rich_text_to_image_amd.engine import SDXL_CONFIG, Engine
+    from rich_text_to_image_amd.schedulers import DPMSolverTables, EulerTables
+    p = argparse.ArgumentParser()
+    p.add_argument("--scheduler", nargs="+", default=["euler"], choices=["euler", "dpmsolver++"])
+    p.add_argument("--steps", type=int, nargs="+", default=[50])
+    p.add_argument("--solver_order", type=int, default=2, choices=[1, 2])
+    p.add_argument("--hw", type=int, default=128, help="latent size (128: 1024^2 images)")
+    p.add_argument("--inject_selfattn", type=float, default=0.5)
+    p.add_argument("--no_guidance", action="store_true", help="colour guidance off (on by default, as in the RICH_TEXT request)")
+    a = p.parse_args(argv)
+    if len(a.steps) not in (1, len(a.scheduler)):
+        raise SystemExit("end_to_end: give one --steps value, or one per --scheduler entry")
+    steps = a.steps * len(a.scheduler) if len(a.steps) == 1 else a.steps
+    eng = Engine(SDXL_CONFIG, a.hw, a.hw, device=0, max_streams=8, max_prompts=8)
+    eng.init_random_weights(seed=0)
+    for name, n in zip(a.scheduler, steps):
+        sched = DPMSolverTables(solver_order=a.solver_order) if name == "dpmsolver++" else EulerTables()
+        r = end_to_end(eng, a.hw, steps=n, inject_selfattn=a.inject_selfattn, use_guidance=not a.no_guidance, scheduler=sched)
+        print(json.dumps(dict(r, scheduler_flag=name)), flush=True)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
