@@ -215,6 +215,7 @@ void rt_engine::plain_forward(int i, int first, int count) {
     unet_forward(in);
 }
 void rt_engine::plain_finish(int i, float g) {
+    RT_REQUIRE(i >= 0 && i < (int)timesteps.size(), "plain_step: step index out of range");     // PNDM / Euler index their tables with it
     const bool xl = sched_kind == RT_SCHED_EULER;
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
