@@ -10,7 +10,11 @@ Workload = BASELINE.json configs[2] ("SDXL RegionDiffusionXL 1024x1024, 4 region
 A "step" is one iteration of the loop at models/region_diffusion_sdxl.py:779 (all F forwards, mask combine,
 CFG, scheduler step).  Every forward the reference executes is executed (no dead-forward elision).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does what the headline figure needs and nothing else: set up, warm up, time the K steps, write --dump-outputs, print the
+line.  `--full` adds everything else the line has carried (roofline / per-kernel profile, dead-forward elision timing,
+cross_attention_block, CPU baseline and parity, full-schedule pixel parity, the secondary legs of tools/end_to_end.py) and is required
+by --config 1 / 2 / 5, --elide and --roofline-only.
 N > 1: one rank per GPU under torch.distributed.run - either launched that way by the caller (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) or, when `python bench.py --gpus N` is run bare, by running itself in a child `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (launcher.self_launch).  Each rank runs an independent image (own seed,
@@ -391,11 +395,18 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed (rank 0's latents after the last timed step) as DIR/latents.npy, "
                          "float32 [1, 4, 128, 128]; the inputs are seeded, so two builds can be compared output for output (config 3 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline figure: the roofline / per-kernel profile leg, the dead-forward "
+                         "elision timing, cross_attention_block, the CPU baseline with its parity check, the full-schedule pixel parity and "
+                         "the secondary legs (--no-cpu-baseline / --no-extras trim them); needed by --config 1/2/5, --elide and --roofline-only. "
+                         "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.config == 1 else 50
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.config != 3 or args.elide or args.roofline_only):
+        ap.error("--config 1/2/5, --elide and --roofline-only are measurements of --full")
     if args.dump_outputs is not None and (args.config != 3 or args.roofline_only or args.dry_launch):
         ap.error("--dump-outputs needs the timed steps of config 3 (not --config 1/2/5, --roofline-only or --dry-launch)")
     if args.config != 3:
@@ -433,7 +444,7 @@ def main():
     # ---- weights: rank 0 draws + packs them, everyone else receives the packed bf16 arena (one broadcast)
     sd_cpu = None
     if rank == 0:
-        keep_cpu = world == 1 and not args.no_cpu_baseline          # the CPU baseline is an N=1, rank-0 leg only
+        keep_cpu = world == 1 and args.full and not args.no_cpu_baseline          # the CPU baseline is an N=1, rank-0 leg of --full only
         g = torch.Generator(device=dev).manual_seed(0)
         sd_cpu = {} if keep_cpu else None
         for name, shape in eng.weight_table():
@@ -497,12 +508,13 @@ def main():
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "latents.npy"), final.cpu().numpy().astype(np.float32))
 
+    # ---- the legs below run with --full only: a plain run goes straight to its line
     # ---- roofline leg (outside the timed region): HIP events around every MFMA kernel launch on the engine
     # stream for one injected step (i=0) and one non-injected step (i=nsched-1)
     roof = None
     prof = None
     step_flops = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reset()
         per_step = []
         for i_prof in (0, nsched - 1):                       # one injected (t > 500) and one non-injected step
@@ -550,7 +562,7 @@ def main():
     # the background-blend step the uncond_ref / text_ref forwards are dead in the reference too).  Same
     # final latents; NOT the headline value (the reference runs those forwards).
     elided = None
-    if not args.elide and not args.roofline_only:
+    if args.full and not args.elide and not args.roofline_only:
         reset()
         for i in range(min(2, nsched)):
             eng.region_step(i, gs, isa, ibg, xl=True, elide=True)
@@ -566,7 +578,7 @@ def main():
         elided = dict(value=world * args.steps / dt_e, ms_per_step=dt_e / args.steps * 1e3, identical_latents=same)
 
     xblock = None
-    if rank == 0 and not args.roofline_only:
+    if rank == 0 and args.full and not args.roofline_only:
         try:
             xblock = cross_attention_block(dev)
         except Exception as ex:          # the headline line must still print
@@ -574,7 +586,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and not args.no_cpu_baseline and not args.roofline_only and sd_cpu is not None:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not args.roofline_only and sd_cpu is not None:
         threads = physical_cores()
         # one engine stream on the oracle's inputs: prompt 0 (negative), t = 801, unscaled latents
         gp = torch.Generator().manual_seed(4242)
@@ -589,7 +601,7 @@ def main():
 
     # ---- the full schedule against the committed oracle trajectory, in latents and in pixels (config 3: all 50 Euler steps)
     pixels = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.roofline_only:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.roofline_only:
         try:
             # the benched workload's own 50-step schedule (+ the 10-step one that crosses the injection boundary between two checkpoints)
             pixels = pixel_parity("config3_50", also=("config3", "config3_unit")) if os.path.exists(os.path.join(ROOT, "tests", "golden", "fullschedule", "config3_50.pt")) else pixel_parity("config3")
@@ -599,7 +611,7 @@ def main():
     # ---- the other half of an image and the secondary modes (N = 1, rank 0, outside every timed region; tools/end_to_end.py).
     # They re-program the engine (prompts, schedule, capture), so they come after everything that reads the headline state.
     extras = {}
-    if rank == 0 and world == 1 and not args.roofline_only and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.roofline_only and not args.no_extras:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import end_to_end as e2e
 
@@ -668,8 +680,8 @@ def main():
 
     if rank == 0:
         value = None if args.roofline_only else world * args.steps / dt
-        # executed MFMA FLOPs per step (profile leg) rather than 7 x the nominal forward: injected steps skip the region streams' Q|K GEMMs
-        step_tflop = step_flops["mean"] / 1e12 if step_flops else 7 * SDXL_FWD_GFLOP / 1e3
+        # executed MFMA FLOPs per step (profile leg, --full) rather than 7 x the nominal forward: injected steps skip the region streams' Q|K GEMMs
+        step_tflops = None if args.roofline_only or step_flops is None else step_flops["mean"] / 1e12 / (dt / args.steps)
         line = {
             "metric": "denoising steps/sec (SDXL 1024^2, 50-step, 4 regions)",
             "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -679,8 +691,9 @@ def main():
                                    "CFG 5.0, 7 UNet forwards/step batched, random-init SDXL-base weights",
                        "global_batch": world, "parallelism": f"seed-parallel x{world} (1 weight broadcast, no per-step collectives)",
                        "elide_dead_forwards": bool(args.elide)},
-            "whole_step_tflops_per_gpu": None if args.roofline_only else step_tflop / (dt / args.steps),
-            "whole_step_mfma_frac": None if args.roofline_only else step_tflop / (dt / args.steps) / PEAK_BF16_TFLOPS,
+            "full": bool(args.full),
+            "whole_step_tflops_per_gpu": step_tflops,
+            "whole_step_mfma_frac": None if step_tflops is None else step_tflops / PEAK_BF16_TFLOPS,
             "executed_flops_per_step": step_flops, "nominal_tflop_per_step": 7 * SDXL_FWD_GFLOP / 1e3,
             "weight_broadcast_s": bcast_s, "weight_broadcast_calls": launcher.LAST_BROADCAST_CALLS, "collective_check": collective_check, "finite": finite,
             "roofline": roof, "cpu_baseline": cpu, "parity": parity, "pixel_parity": pixels, "cross_attention_block": xblock, "elide_dead_forwards_timing": elided,

@@ -9,7 +9,7 @@ run() { # name, counters...
     local name=$1; shift
     local out=$ROOT/gpurun_out/pmc_${TAG}_$name
     mkdir -p $out
-    (cd /tmp && rocprofv3 --kernel-trace --pmc "$@" -d $out -o $name -- python $ROOT/bench.py --roofline-only --warmup 2 > $out/bench.json 2> $out/rocprof.log) || { tail -5 $out/rocprof.log; exit 1; }
+    (cd "$TMPDIR" && rocprofv3 --kernel-trace --pmc "$@" -d $out -o $name -- python $ROOT/bench.py --full --roofline-only --warmup 2 > $out/bench.json 2> $out/rocprof.log) || { tail -5 $out/rocprof.log; exit 1; }
     ls $out/*.db | head -1
 }
 F=$(run fetch FETCH_SIZE)
