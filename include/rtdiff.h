@@ -189,6 +189,7 @@ int rt_op_attention_units_plan(const int* q_src, const int* k_src, int B, int to
  * {0,1,9} / {6,7,12} / -1) never depends on `streams`; inside a class the tile shape follows the batch. */
 int rt_op_gemm16_pick(int conv3x3, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int weights_on_rows, int* w_stationary);
 /* Host-only query of the split rule of csrc/gemm.hip for problems that cannot fill the chip (no device needed; tests/test_split_plan.py):
+ * the route launch_gemm takes (csrc/gemm.hip, gemm_route).
  * *route 0: one launch | 1: K slices of the 128x128 (implicit) GEMM + reduction launch | 2 (round 6): the 16x16-patch convolution kernel
  * split over its input-channel chunks + reduction launch; *slices: how many.  conv3x3: 0 dense (K_or_Cin = K), 1 stride-1 3x3 convolution,
  * 3 the nearest-2x up-sample folded in (rows_per_stream = OUTPUT pixels, a square map).  Route and slice count are functions of ONE
@@ -276,13 +277,28 @@ const char* rt_op_last_error(void);
 int rt_op_probes_built(void);      /* 1: the library was built with `make PROBES=1` and contains the measured-and-rejected kernels (xblock_kernel,
                                     * EPI_XATTN, gemm16 variant 13) that rt_op_gemm_debug bits 16 / 4 and variant 13 select; 0: the shipped build */
 int rt_op_gemm_force_config(int cfg);
-/* A/B switches (benchmarks; the engine wrapper reads RTDIFF_DEBUG_FLAGS once at load): bit 0 patch-eligible 3x3 convs through the
- * implicit-GEMM kernels; bit 1 keep gemm16.hip out; bit 2 no split-K; bit 3 stride-1 3x3 convs stay on the patch kernel (not on the
- * gemm16 main loop); bit 4 cross-attention as to_q GEMM + attention launch instead of the fused kernel;
- * bit 5 token-map accumulation on the round-1 two-pass kernel (csrc/attn_store.hip); bit 6 large maps on the one-pass kernel instead of
- * the statistics + key-split apply pair; bit 7 the precise VAE's hi / lo contractions as three launches instead of one;
- * bit 13 attn1's Q|K and V^T projections as two launches instead of one grouped launch; bit 14 no raised wave priority (s_setprio) in the
- * MFMA phases of the attention kernel; bit 15 the precise VAE's DENSE hi / lo contractions as three launches */
+/* A/B switches (benchmarks; the engine wrapper reads RTDIFF_DEBUG_FLAGS once at load); csrc/common.h (DebugBit) names them.  0 = default.
+ *  bit 0  patch-eligible 3x3 convs through the implicit-GEMM kernels     bit 1  keep gemm16.hip out
+ *  bit 2  no split-K (no K slices, no input-channel chunks)               bit 3  stride-1 3x3 convs stay on the patch kernel (not on gemm16)
+ *  bit 4  cross-attention as to_q GEMM + attention launch instead of the fused kernel (probe builds)
+ *  bit 5  token-map accumulation on the round-1 two-pass kernel (csrc/attn_store.hip)
+ *  bit 6  large token maps on the one-pass kernel instead of the statistics + key-split apply pair
+ *  bit 7  the precise VAE's hi / lo contractions as three launches instead of one; bit 8 only those on the gemm16 convolution route,
+ *         bit 9 only those on the patch kernel, bit 15 only the DENSE ones
+ *  bit 10 chunk-split patch convolutions keep 160-channel column tiles where N % 160 == 0
+ *  bit 11 GroupNorm chunks of 128 rows instead of 64                     bit 12 no 5-slot ring for gemm16's 64 x 160 tiles
+ *  bit 13 attn1's Q|K and V^T projections as two launches instead of one grouped launch
+ *  bit 14 no raised wave priority (s_setprio) in the MFMA phases of the attention kernel
+ *  bit 16 the 640-channel cross-attention block as one launch (xblock.hip, opt-in, probe builds)
+ *  bit 17 the token-map store computes its softmax statistics itself     bit 18 round 4's token-map apply kernel for every head dim
+ *  bit 19 cross-attention on the round-4 kernels instead of cross77_kernel
+ *  bit 20 cross77_kernel: one 16-query tile per wave for every shape    bit 21 cross77_kernel: two heads per workgroup
+ *  bit 22 LayerNorm launches + bf16 projections instead of the LayerNorm fold
+ *  bit 23 GroupNorm always in its two-launch form
+ *  bits 24 - 26 shared-probability units of the self-attention launches (rt_op_attention_units_plan's mode)
+ *  bit 27 GEGLU launches that cannot take the W-stationary order run groups of 8 tile rows
+ *  bit 28 under-filled 3x3 convs on the split-K implicit GEMM instead of the chunk-split patch kernel
+ *  bit 29 no two-halves chunk split for the 32x32 maps                  bit 30 the split rule counts streams of < 128 rows as whole tiles */
 int rt_op_gemm_debug(int flags);
 
 /* ---- VAE decoder: colour guidance (rd.py:151-168, xl.py:849-867) and plain decode (rd.py:227-236) ----

@@ -167,7 +167,6 @@ struct GemmArgs {
     float* ln_emit;
 };
 // LayerNorm fold plumbing (host-only predicates are pure functions of the shape, like every routing decision)
-int gemm_route16(const GemmArgs& a);                    // variant of the 16x16x32 family launch_gemm would take for this problem, -1: another route
 int gemm_ln_emit_bn(const GemmArgs& a);                 // column-tile width (160 / 320) of the partials launch_gemm(a) with a.ln_emit set would leave; 0: this route has no such epilogue
 bool gemm_ln_fold_ok(const GemmArgs& a);                // launch_gemm(a) with a.ln_part set has a folded instantiation
 bool gemm16_ln_variant_ok(const GemmArgs& a, int v);    // gemm16.hip: variant v has the LayerNorm-fold instantiation a.ln_part / a.ln_emit ask for
@@ -194,11 +193,56 @@ struct XBlockArgs {
 bool xblock_supported(int C, int H, int DP, int tokens);
 void launch_xblock(const XBlockArgs& a, hipStream_t st);
 void launch_gemm(const GemmArgs& a, hipStream_t st);
-bool gemm_pair_output_ok(const GemmArgs& a);            // host-only: launch_gemm would run this problem on a kernel that can write GemmArgs.pair_lo
-void gemm_split_plan(const GemmArgs& a, int* route, int* slices);      // host-only: 0 one launch / 1 K slices + reduction / 2 chunk-split patch convolution + reduction
+// What launch_gemm does with a problem, host-only: a pure function of the arguments and the switches (gemm_set_debug, gemm_force_config).
+// It reads the shape and also A_lo / W_lo / pair_lo / ln_part / ln_emit / prefer_patch_conv / weights_on_rows / split_tiles /
+// rows_per_stream, so this and every query below must be asked with the arguments as they will be launched.
+struct GemmRoute {
+    enum Kind { G16, PATCH, PATCH_SPLIT, KSPLIT, TILE, TRIPLE };
+    Kind kind = TILE;  // G16: gemm16.hip | PATCH: conv3p_kernel | PATCH_SPLIT: conv3p_kernel over input-channel chunks + reduction |
+                       // KSPLIT: K slices of the 128x128 kernel + reduction | TILE: a gemm.hip tile configuration |
+                       // TRIPLE: hi / lo contraction as three launches of the single-pass problem
+    int variant = -1, wstat = 0;   // G16: tile variant, W-stationary tile order
+    int slices = 1;                // PATCH_SPLIT / KSPLIT
+    int cfg = -1;                  // TILE
+};
+GemmRoute gemm_route(const GemmArgs& a);
+bool gemm_pair_output_ok(const GemmArgs& a);            // launch_gemm would run this problem on a kernel that can write GemmArgs.pair_lo
 size_t gemm_splitk_scratch_floats(const GemmArgs& a);   // fp32 partial sums launch_gemm needs for this problem (0: not split)
 void gemm_force_config(int cfg);   // -1: shape-based choice; 0..8: force a gemm.hip tile configuration (also keeps gemm16.hip out)
-void gemm_set_debug(int d);        // bit 0: eligible 3x3 convolutions through the implicit-GEMM kernels; bit 1: keep gemm16.hip out; bit 4: no fused cross-attention
+// rt_op_gemm_debug's A/B switches (benchmarks, tests, RTDIFF_DEBUG_FLAGS): bit positions, part of the interface - callers pass raw numbers
+enum DebugBit {
+    DBG_CONV_IMPLICIT = 0,        // patch-eligible 3x3 convolutions through the implicit-GEMM kernels
+    DBG_NO_GEMM16 = 1,            // keep gemm16.hip out
+    DBG_NO_SPLIT = 2,             // no split-K (neither K slices nor input-channel chunks)
+    DBG_CONV_NO_GEMM16 = 3,       // stride-1 3x3 convolutions stay on the patch kernel instead of gemm16.hip's implicit GEMM
+    DBG_NO_XATTN_FUSED = 4,       // cross-attention as to_q GEMM + attention launch instead of the fused kernel (probe builds)
+    DBG_STORE_TWO_PASS = 5,       // token-map accumulation on the round-1 two-pass single-wave kernel for every shape (attn_store.hip)
+    DBG_STORE_ONE_PASS = 6,       // large token maps on the one-pass kernel instead of the statistics + key-split apply pair
+    DBG_TRIPLE = 7,               // the precise VAE's hi / lo contractions as three launches (round 3) instead of one
+    DBG_TRIPLE_GEMM16 = 8,        // ... only those on the gemm16 convolution route
+    DBG_TRIPLE_PATCH = 9,         // ... only those on the patch kernel
+    DBG_CONV3P_NO_TN4 = 10,       // chunk-split patch convolutions keep 160-channel column tiles where N % 160 == 0
+    DBG_GN_CHUNK_128 = 11,        // GroupNorm chunks of 128 rows (norm.hip) instead of 64
+    DBG_G16_NO_DEEP = 12,         // no 5-slot ring for gemm16.hip's 64 x 160 tiles
+    DBG_NO_PAIR = 13,             // attn1's Q|K and V^T projections as two launches instead of one grouped launch
+    DBG_ATTN_NO_PRIO = 14,        // no raised wave priority in the MFMA phases of the attention kernel
+    DBG_TRIPLE_DENSE = 15,        // the precise VAE's DENSE hi / lo contractions as three launches
+    DBG_XBLOCK = 16,              // the 640-channel cross-attention block as xblock.hip's one launch (opt-in, probe builds)
+    DBG_STORE_OWN_STATS = 17,     // the token-map store computes the softmax statistics itself although the attention launch could leave them
+    DBG_STORE_APPLY_V1 = 18,      // round 4's apply kernel of the token-map store for every head dim
+    DBG_NO_CROSS77 = 19,          // cross-attention on the round-4 kernels instead of cross77_kernel
+    DBG_C77_ONE_TILE = 20,        // cross77_kernel: one 16-query tile per wave for every shape
+    DBG_C77_TWO_HEADS = 21,       // cross77_kernel: two heads per workgroup
+    DBG_NO_LNFOLD = 22,           // LayerNorm launches + bf16 projections (rounds 1 - 5) instead of the folded form
+    DBG_GN_TWO_LAUNCH = 23,       // GroupNorm always in its two-launch form
+    DBG_ATTN_UNITS = 24,          // bits 24 - 26: shared-probability units mode of the self-attention launches (0: the shape rule)
+    DBG_G16_TALL = 27,            // GEGLU launches that cannot take the W-stationary order run groups of 8 tile rows
+    DBG_NO_CHUNK_SPLIT = 28,      // under-filled 3x3 convolutions on the split-K implicit GEMM instead of the chunk-split patch kernel
+    DBG_NO_CHUNK_HALVES = 29,     // no two-halves chunk split for the 32x32 maps
+    DBG_SPLIT_NO_SMALL_ROWS = 30, // the split rule counts streams of < 128 rows as whole 128-row tiles
+};
+static inline int debug_bit(int flags, int bit) { return (flags >> bit) & 1; }
+void gemm_set_debug(int flags);    // decodes the routing bits above
 bool gemm_lnfold_enabled();       // LayerNorm folded into its consumers (debug bit 22 clear, gemm16 on, no forced configuration)
 bool gemm_xblock_enabled();       // the one-launch cross-attention block (xblock.hip) is switched on (debug bit 16 SET - opt-in; gemm16 on, no forced configuration)
 bool gemm_xattn_enabled();         // the fused to_q + cross-attention kernel is allowed (debug bit 4 clear, gemm16 on, no forced configuration)
@@ -207,9 +251,10 @@ bool gemm_xattn_enabled();         // the fused to_q + cross-attention kernel is
 bool gemm16_supported(const GemmArgs& a);
 int gemm16_pick(const GemmArgs& a, int weights_on_rows, int* wstat);      // variant id or -1; pure function of the shape
 void launch_gemm16_variant(const GemmArgs& a, int variant, int wstat, hipStream_t st);
-int gemm16_pair_variant(const GemmArgs& a, const GemmArgs& b);                   // host-only: id of the grouped instantiation (0..3), -1: none
-bool launch_gemm16_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t st);   // grouped launch (gemm16.hip); false: not launched, no grouped form
-bool gemm_pair_is_grouped(const GemmArgs& a, const GemmArgs& b);                // host-only: would launch_gemm_pair take the grouped launch?
+int gemm16_pair_variant(const GemmArgs& a, int va, int wa, const GemmArgs& b, int vb, int wb);     // id of the grouped instantiation of tiles
+                                                                                                  // va / vb (gemm16_pick) (0..3), -1: none
+void launch_gemm16_pair(const GemmArgs& a, const GemmArgs& b, int pair, hipStream_t st);          // grouped launch of instantiation `pair` (gemm16.hip)
+int gemm_pair_grouped(const GemmArgs& a, const GemmArgs& b);    // host-only: grouped instantiation launch_gemm_pair takes, -1: two launches
 void launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t st);     // gemm.hip: the grouped launch where it exists (debug bit 13 clear), else two launch_gemm calls
 
 // ---------------------------------------------------------------- attention

@@ -1334,7 +1334,16 @@ int rt_op_attention_units_plan(const int* q_src, const int* k_src, int B, int to
     if (!q_src || !k_src || !launch_of || !unit_of || !members_of || B < 1 || B > RT_MAXB) return -1;
     return attention_units_plan_host(q_src, k_src, B, tokens, DP, mode, launch_of, unit_of, members_of);
 }
-int rt_op_gemm_debug(int d) { gemm_set_debug(d); g_store_own_stats = (d >> 17) & 1; g_store_apply_v1 = (d >> 18) & 1; g_c77_t1 = (d >> 20) & 3; g_store_legacy = ((d & 32) ? 1 : 0) | ((d & 64) ? 2 : 0); attention_set_prio(((d >> 14) & 1) ^ 1); attention_set_units((d >> 24) & 7); gemm16_set_tall((d >> 27) & 1); groupnorm_set_fused(((d >> 23) & 1) ^ 1); groupnorm_set_chunk_div(((d >> 11) & 1) ? 128 : 64); gemm16_set_deep(((d >> 12) & 1) ^ 1); return RT_OK; }
+int rt_op_gemm_debug(int d) {
+    auto on = [d](int bit) { return debug_bit(d, bit); };
+    gemm_set_debug(d);
+    g_store_legacy = on(DBG_STORE_TWO_PASS) | on(DBG_STORE_ONE_PASS) << 1; g_store_own_stats = on(DBG_STORE_OWN_STATS); g_store_apply_v1 = on(DBG_STORE_APPLY_V1);
+    g_c77_t1 = on(DBG_C77_ONE_TILE) | on(DBG_C77_TWO_HEADS) << 1;
+    attention_set_prio(!on(DBG_ATTN_NO_PRIO)); attention_set_units((d >> DBG_ATTN_UNITS) & 7);
+    gemm16_set_tall(on(DBG_G16_TALL)); gemm16_set_deep(!on(DBG_G16_NO_DEEP));
+    groupnorm_set_fused(!on(DBG_GN_TWO_LAUNCH)); groupnorm_set_chunk_div(on(DBG_GN_CHUNK_128) ? 128 : 64);
+    return RT_OK;
+}
 int rt_op_probes_built(void) {
 #ifdef RT_PROBES
     return 1;
@@ -1424,41 +1433,42 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
         else launch_attention(a, (hipStream_t)stream);
     })
 }
-// The shape rule of csrc/gemm16.hip as a host-only query (no device needed): which tile variant a problem takes (-1: stays on gemm.hip /
-// the patch convolution) and whether it uses the W-stationary tile -> XCD order.  `streams` images / streams of rows_per_stream rows each.
+// The arguments of a host-only shape query as the engine launches them: `streams` streams / images of rows_per_stream rows each
+// (3x3 convolution modes: a square map of rows_per_stream OUTPUT pixels, K_or_Cin input channels); N = the weight rows.  false: not a square map.
+static bool query_args(GemmArgs& g, int mode, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int weights_on_rows) {
+    g = GemmArgs{};
+    g.mode = mode; g.epi = epi; g.M = streams * rows_per_stream; g.N = N; g.weights_on_rows = weights_on_rows;
+    if (mode != A_DENSE) {
+        int side = 1; while (side * side < rows_per_stream) ++side;
+        if (side * side != rows_per_stream) return false;
+        g.Cin = K_or_Cin; g.K = 9 * K_or_Cin; g.ldw = g.K;
+        g.Hout = g.Wout = side; g.Hin = g.Win = mode == A_CONV3_UP2 ? side / 2 : side; g.rows_per_batch = rows_per_stream;
+    } else {
+        g.K = K_or_Cin; g.lda = g.K; g.ldw = g.K; g.rows_per_stream = rows_per_stream;
+        if (weights_on_rows) { g.M = N; g.N = streams * rows_per_stream; }
+    }
+    g.ldo = g.N;
+    g.split_tiles = cdiv(rows_per_stream, 128) * cdiv(N, 128);                  // what the engine passes (engine.hip: conv3 / gemm)
+    return true;
+}
+// The route launch_gemm takes for problems that cannot fill the chip (gemm_route) as a host-only query (no device needed).
 int rt_op_split_plan(int conv3x3, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int* route, int* slices) {
     try {
-        GemmArgs g{};
-        g.epi = epi; g.N = N;
-        if (conv3x3) {
-            int side = 1; while (side * side < rows_per_stream) ++side;
-            if (side * side != rows_per_stream) return RT_E_INVALID;                // square maps only in this query
-            g.mode = conv3x3 == 3 ? A_CONV3_UP2 : A_CONV3; g.Cin = K_or_Cin; g.K = 9 * K_or_Cin; g.ldw = g.K; g.ldo = N;
-            g.Hout = g.Wout = side; g.Hin = g.Win = conv3x3 == 3 ? side / 2 : side; g.rows_per_batch = rows_per_stream; g.M = streams * rows_per_stream;
-        } else {
-            g.mode = A_DENSE; g.K = K_or_Cin; g.lda = g.K; g.ldw = g.K; g.rows_per_stream = rows_per_stream; g.M = streams * rows_per_stream;
-        }
-        g.split_tiles = cdiv(rows_per_stream, 128) * cdiv(N, 128);                  // what the engine passes (engine.hip: conv3 / gemm)
-        int r = 0, sl = 1;
-        gemm_split_plan(g, &r, &sl);
-        if (route) *route = r;
-        if (slices) *slices = sl;
+        GemmArgs g;
+        if (!query_args(g, conv3x3 == 3 ? A_CONV3_UP2 : conv3x3 ? A_CONV3 : A_DENSE, epi, streams, rows_per_stream, N, K_or_Cin, 0)) return RT_E_INVALID;
+        const GemmRoute r = gemm_route(g);
+        const int kind = r.kind == GemmRoute::KSPLIT ? 1 : r.kind == GemmRoute::PATCH_SPLIT ? 2 : 0;
+        if (route) *route = kind;
+        if (slices) *slices = kind ? r.slices : 1;
         return RT_OK;
     } catch (...) { return RT_E_INVALID; }
 }
+// The shape rule of csrc/gemm16.hip as a host-only query (no device needed): which tile variant a problem takes (-1: stays on gemm.hip /
+// the patch convolution) and whether it uses the W-stationary tile -> XCD order.  `streams` images / streams of rows_per_stream rows each.
 int rt_op_gemm16_pick(int conv3x3, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int weights_on_rows, int* w_stationary) {
     try {
-        GemmArgs g{};
-        g.epi = epi; g.N = N; g.weights_on_rows = weights_on_rows;
-        if (conv3x3) {
-            int side = 1; while (side * side < rows_per_stream) ++side;
-            if (side * side != rows_per_stream) return -2;                      // square maps only in this query
-            g.mode = A_CONV3; g.Cin = K_or_Cin; g.K = 9 * K_or_Cin; g.ldw = g.K; g.ldo = N;
-            g.Hin = g.Hout = g.Win = g.Wout = side; g.rows_per_batch = rows_per_stream; g.M = streams * rows_per_stream;
-        } else {
-            g.mode = A_DENSE; g.K = K_or_Cin; g.lda = g.K; g.ldw = g.K; g.rows_per_stream = rows_per_stream;
-            if (weights_on_rows) { g.M = N; g.N = streams * rows_per_stream; } else g.M = streams * rows_per_stream;
-        }
+        GemmArgs g;
+        if (!query_args(g, conv3x3 ? A_CONV3 : A_DENSE, epi, streams, rows_per_stream, N, K_or_Cin, weights_on_rows)) return -2;     // square maps only
         int ws = 0;
         const int v = gemm16_pick(g, weights_on_rows, &ws);
         if (w_stationary) *w_stationary = ws;
@@ -1480,11 +1490,10 @@ int rt_op_gemm16_variant(const void* A, const void* W, const float* bias, void* 
 // V^T tile) - or -1: two launches.
 int rt_op_gemm_pair_pick(int streams_qk, int streams, int rows_per_stream, int Nqk, int Nv, int K) {
     try {
-        GemmArgs a{}; a.mode = A_DENSE; a.epi = EPI_BF16; a.M = streams_qk * rows_per_stream; a.N = Nqk; a.K = K; a.lda = K; a.ldw = K; a.ldo = Nqk;
-        GemmArgs b{}; b.mode = A_DENSE; b.epi = EPI_BF16; b.M = Nv; b.N = streams * rows_per_stream; b.K = K; b.lda = K; b.ldw = K; b.ldo = b.N; b.weights_on_rows = 1;
-        a.rows_per_stream = b.rows_per_stream = rows_per_stream;
-        a.split_tiles = cdiv(rows_per_stream, 128) * cdiv(Nqk, 128); b.split_tiles = cdiv(Nv, 128) * cdiv(rows_per_stream, 128);
-        return gemm_pair_is_grouped(a, b) ? gemm16_pair_variant(a, b) : -1;
+        GemmArgs a, b;
+        query_args(a, A_DENSE, EPI_BF16, streams_qk, rows_per_stream, Nqk, K, 0);
+        query_args(b, A_DENSE, EPI_BF16, streams, rows_per_stream, Nv, K, 1);
+        return gemm_pair_grouped(a, b);
     } catch (...) { return -3; }
 }
 // attn1's two projections of one LayerNorm output X [M, K] as the engine launches them (launch_gemm_pair): qk[Mqk, Nqk] = X[:Mqk] Wqk^T + bqk
@@ -1500,7 +1509,7 @@ int rt_op_gemm_qk_vt(const void* X, int ldx, int K, int rows_per_stream, const v
             a.rows_per_stream = b.rows_per_stream = rows_per_stream;
             a.split_tiles = cdiv(rows_per_stream, 128) * cdiv(Nqk, 128); b.split_tiles = cdiv(Nv, 128) * cdiv(rows_per_stream, 128);
         }
-        if (grouped) *grouped = gemm_pair_is_grouped(a, b) ? 1 : 0;
+        if (grouped) *grouped = gemm_pair_grouped(a, b) >= 0 ? 1 : 0;
         launch_gemm_pair(a, b, (hipStream_t)stream);
     })
 }

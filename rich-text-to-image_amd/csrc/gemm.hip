@@ -1243,44 +1243,43 @@ static void launch_with_cfg(const GemmArgs& a, int cfg, hipStream_t st) {
     HIP_CHECK(hipGetLastError());
 }
 
-// Tile configuration choice: measured per problem shape on the real launches (see the in-situ tuner below).  Because all
-// configurations are bit-identical in their results, tuning never changes outputs.
-static int g_force_cfg = -1;
-static int g_conv_patch = 1;
-static int g_use16 = 1;
-static int g_splitk = 1;
-static int g_conv16 = 1;
-static int g_xattn = 1;
-static int g_no_triple = 0;
-static int g_pair = 1;
-static int g_cross77 = 1;
-static int g_xblock = 0;      // measured slower than the separate launches (LABNOTES R5.2): opt-in
-static int g_split_small_rows = 1;      // (A/B, debug bit 30)
-static int g_conv3p_tn4 = 1;     // (A/B, debug bit 10)
-static int g_conv3p_split = 3;   // round 6: under-filled patch-eligible 3x3 convolutions split over their channel chunks on the patch kernel; debug bit 28: on the split-K implicit GEMM (rounds 2 - 5)
-static int g_lnfold = 1;      // round 6: LayerNorm folded into its consumers (gemm16.hip, "LNF"); debug bit 22 restores the LayerNorm launches
+// Routing switches: the A/B bits of rt_op_gemm_debug (DebugBit, common.h: gemm_set_debug) and rt_op_gemm_force_config.  gemm_route and the
+// engine's own choices read them; the defaults are the shipped routes.
+static struct GemmSwitches {
+    int force_cfg = -1;           // >= 0: this gemm.hip tile configuration for everything the patch kernel does not take (keeps gemm16.hip out)
+    bool conv_patch = true;       // patch-eligible 3x3 convolutions on conv3p_kernel (else: the implicit-GEMM kernels)
+    bool use16 = true;            // the 16x16x32 family (gemm16.hip)
+    bool splitk = true;           // split the problems that cannot fill the chip
+    bool conv16 = true;           // stride-1 3x3 convolutions on gemm16.hip's implicit GEMM where it has a tile
+    bool xattn = true;            // the fused to_q + cross-attention kernel (gemm16.hip, EPI_XATTN)
+    bool triple = false, triple16 = false, triple_patch = false, triple_dense = false;    // hi / lo contractions as three launches: all of
+                                  // them / those of the gemm16 convolution route / of the patch kernel / the dense ones
+    bool pair = true;             // attn1's Q|K and V^T projections as one grouped launch
+    bool cross77 = true;          // cross-attention on cross77_kernel (else the round-4 kernels)
+    bool xblock = false;          // the 640-channel cross-attention block as xblock.hip's ONE launch (measured slower, LABNOTES R5.2: opt-in)
+    bool split_small_rows = true; // streams of < 128 rows share 128-row tiles in the split rule
+    bool conv3p_tn4 = true;       // chunk-split launches take 128-channel column tiles at any multiple of 128
+    bool chunk_split = true;      // round 6: under-filled patch-eligible 3x3 convolutions split over their input-channel chunks on the patch
+                                  // kernel (else on the split-K implicit GEMM, rounds 2 - 5)
+    bool chunk_halves = true;     // ... and the two-halves rule of the 32x32 maps
+    bool lnfold = true;           // round 6: LayerNorm folded into its consumers (gemm16.hip, "LNF")
+} g_sw;
 #ifdef RT_PROBE
 int g_conv3p_tn = 0;          // probe override of the patch kernel's column-tile count
 #endif
-// bit 0: route eligible convs through the implicit-GEMM kernels; bit 1: keep the 16x16x32 family (gemm16.hip) out (A/B tests)
-// bit 2: no split-K; bit 3: stride-1 3x3 convolutions stay on the patch kernel (conv3p_kernel) instead of gemm16.hip's implicit GEMM
-// bit 4: cross-attention as to_q GEMM + attention launch instead of the fused kernel (gemm16.hip, EPI_XATTN)
 void gemm_set_debug(int flags) {
-    g_conv_patch = (flags & 1) ? 0 : 1; g_use16 = (flags & 2) ? 0 : 1; g_splitk = (flags & 4) ? 0 : 1; g_conv16 = (flags & 8) ? 0 : 1;
-    g_xattn = (flags & 16) ? 0 : 1;
-    g_xblock = (flags & 65536) ? 1 : 0;                               // bit 16: the 640-channel cross-attention block as xblock.hip's ONE launch (opt-in: measured slower, LABNOTES R5.2)
-    g_cross77 = (flags & 524288) ? 0 : 1;                             // bit 19: cross-attention on the round-4 kernels (EPI_XATTN / attn_kernel<CROSS>) instead of cross77_kernel
-    g_split_small_rows = (flags & 1073741824) ? 0 : 1;
-    g_conv3p_tn4 = (flags & 1024) ? 0 : 1;
-    g_conv3p_split = (flags & 268435456) ? 0 : ((flags & 536870912) ? 1 : 3); /* bit 29: no two-halves rule for the 32x32 maps */                     // bit 28: under-filled 3x3 convolutions on the split-K implicit GEMM instead of the chunk-split patch kernel
-    g_lnfold = (flags & 4194304) ? 0 : 1;                             // bit 22: LayerNorm launches + bf16 projections (rounds 1 - 5) instead of the folded form
-    g_pair = (flags & 8192) ? 0 : 1;                                  // bit 13: attn1's Q|K and V^T projections as two launches instead of one grouped launch
-    g_no_triple = ((flags & 128) ? 1 : 0) | ((flags & 256) ? 2 : 0) | ((flags & 512) ? 4 : 0) | ((flags & 32768) ? 8 : 0);   // bit 15: dense hi / lo contractions as three launches   // (bits 8 / 9: only the gemm16 / only the patch-kernel route)              // bit 7: the precise VAE's contractions as three launches (round 3) instead of one
+    auto on = [flags](int bit) { return debug_bit(flags, bit); };
+    g_sw.conv_patch = !on(DBG_CONV_IMPLICIT); g_sw.use16 = !on(DBG_NO_GEMM16); g_sw.splitk = !on(DBG_NO_SPLIT); g_sw.conv16 = !on(DBG_CONV_NO_GEMM16);
+    g_sw.xattn = !on(DBG_NO_XATTN_FUSED); g_sw.xblock = on(DBG_XBLOCK); g_sw.cross77 = !on(DBG_NO_CROSS77); g_sw.pair = !on(DBG_NO_PAIR);
+    g_sw.triple = on(DBG_TRIPLE); g_sw.triple16 = on(DBG_TRIPLE_GEMM16); g_sw.triple_patch = on(DBG_TRIPLE_PATCH); g_sw.triple_dense = on(DBG_TRIPLE_DENSE);
+    g_sw.split_small_rows = !on(DBG_SPLIT_NO_SMALL_ROWS); g_sw.conv3p_tn4 = !on(DBG_CONV3P_NO_TN4);
+    g_sw.chunk_split = !on(DBG_NO_CHUNK_SPLIT); g_sw.chunk_halves = !on(DBG_NO_CHUNK_HALVES); g_sw.lnfold = !on(DBG_NO_LNFOLD);
 }
-bool gemm_cross77_enabled() { return g_cross77 != 0; }
-bool gemm_lnfold_enabled() { return g_lnfold != 0 && g_use16 != 0 && g_force_cfg < 0; }
-bool gemm_xblock_enabled() { return g_xblock != 0 && g_use16 != 0 && g_force_cfg < 0; }
-bool gemm_xattn_enabled() { return g_xattn != 0 && g_use16 != 0 && g_force_cfg < 0; }
+void gemm_force_config(int cfg) { g_sw.force_cfg = cfg; }
+bool gemm_cross77_enabled() { return g_sw.cross77; }
+bool gemm_lnfold_enabled() { return g_sw.lnfold && g_sw.use16 && g_sw.force_cfg < 0; }
+bool gemm_xblock_enabled() { return g_sw.xblock && g_sw.use16 && g_sw.force_cfg < 0; }
+bool gemm_xattn_enabled() { return g_sw.xattn && g_sw.use16 && g_sw.force_cfg < 0; }
 
 template <int EPI, bool UP2, int TN>
 static void launch_conv3p_tn(const GemmArgs& a, int ntm, int slices, hipStream_t st) {
@@ -1312,7 +1311,7 @@ static void launch_conv3p(const GemmArgs& a, hipStream_t st, int slices = 1) {
     // 128-channel column tiles where the channel count is a multiple of 128 but not of 160 (the VAE's 128 / 256 / 512-wide layers: a
     // 160-wide tile would multiply 20 - 37 % clamped duplicate columns); round 4, same k order as every other TN
     // (round 6: chunk-split launches may take them at any multiple of 128 - 3 images x 8 slices x 10 tiles of 128 channels are 240 workgroups where 160-channel tiles give 192)
-    if (a.N % 128 == 0 && (a.N % 160 != 0 || (slices > 1 && g_conv3p_tn4))) { const double c4 = cost(4, 0.86); if (c4 < best * 0.97) { tn = 4; best = c4; } }
+    if (a.N % 128 == 0 && (a.N % 160 != 0 || (slices > 1 && g_sw.conv3p_tn4))) { const double c4 = cost(4, 0.86); if (c4 < best * 0.97) { tn = 4; best = c4; } }
     if (c3 < best * 0.97) { tn = 3; best = c3; }
     if (c2 < best * 0.97) { tn = 2; best = c2; }
 #ifdef RT_PROBE
@@ -1324,13 +1323,11 @@ static void launch_conv3p(const GemmArgs& a, hipStream_t st, int slices = 1) {
     else launch_conv3p_tn<EPI, UP2, 5>(a, ntm / slices, slices, st);
 }
 static bool conv_patch_eligible(const GemmArgs& a) {
-    if (!g_conv_patch || a.mode == A_DENSE || a.rows_per_batch <= 0 || a.Hout % 16 || a.Wout % 16 || a.Cin % 64 || a.M % a.rows_per_batch) return false;
+    if (!g_sw.conv_patch || a.mode == A_DENSE || a.rows_per_batch <= 0 || a.Hout % 16 || a.Wout % 16 || a.Cin % 64 || a.M % a.rows_per_batch) return false;
     if (a.mode == A_CONV3) return a.Hin == a.Hout && a.Win == a.Wout && (a.epi == EPI_BF16 || a.epi == EPI_F32 || a.epi == EPI_F16 || a.epi == EPI_BF16_TEMB);
     if (a.mode == A_CONV3_UP2) return a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && (a.epi == EPI_F32 || a.epi == EPI_F16);
     return false;
 }
-void gemm_force_config(int cfg) { g_force_cfg = cfg; }
-
 // ---------------------------------------------------------------------------------------------- tile choice (gemm.hip kernels)
 // A pure function of the problem shape - no timing, no state (round 2 ranked the configurations in situ with HIP events on the
 // caller's stream: different runs / batch sizes ran different kernels, events were recorded on foreign devices' streams, and a
@@ -1343,7 +1340,7 @@ static bool cfg_admissible(const GemmArgs& a, int c) {
     return true;
 }
 static int pick_config(const GemmArgs& a) {
-    if (g_force_cfg >= 0) return cfg_admissible(a, g_force_cfg) ? g_force_cfg : 0;
+    if (g_sw.force_cfg >= 0) return cfg_admissible(a, g_sw.force_cfg) ? g_sw.force_cfg : 0;
     if ((long)a.M * a.N < 256L * 256 * 64) return 0;                  // small problems: 128x128 tiles, two workgroups per CU
     auto wgs = [&](int c) { return (long)cdiv(a.M, kCfg[c].BM) * cdiv(a.N, kCfg[c].BN); };
     int c;
@@ -1414,7 +1411,7 @@ static int splitk_slices(const GemmArgs& a) {
     // streams of fewer than 128 rows (SD-v1.5's 8x8 maps: 64 tokens) SHARE 128-row tiles: four of them are two row tiles, not four -
     // the nominal count above halved the slices such problems need to fill the chip (3 x 8^2 x 1280 -> 1280: 120 workgroups)
     const int rows1 = a.mode == A_DENSE ? a.rows_per_stream : a.rows_per_batch;
-    if (g_split_small_rows && a.split_tiles > 0 && !a.weights_on_rows && rows1 > 0 && rows1 < 128) tiles = (long)cdiv(4 * rows1, 128) * cdiv(a.N, 128);
+    if (g_sw.split_small_rows && a.split_tiles > 0 && !a.weights_on_rows && rows1 > 0 && rows1 < 128) tiles = (long)cdiv(4 * rows1, 128) * cdiv(a.N, 128);
     const int nk = cdiv(a.K, BK);
     if (tiles > 96 || nk < 8) return 1;
     // Round 6 (tools/small_gemm_bench.py): at 256 tokens per stream a K <= 1280 projection is better off unsplit on the 64-row tiles of the
@@ -1432,35 +1429,78 @@ static int splitk_slices(const GemmArgs& a) {
 // bounds its workgroups (0.8 us per K tile whatever the MFMA rate: 3 x 16^2 x 2560 -> 1280 took 91 us for 45 GFLOP), the patch kernel
 // 24.6 KB per 256x160x64 step.  Slices = chunks / ceil(chunks / 8): ~8 slices of equal length, a function of Cin alone, so a stream's
 // sum order does not depend on the batch.  0: the problem does not take this route.
-static int conv3p_split_slices(const GemmArgs& a) {
-    if (!g_conv3p_split || !g_splitk || a.A_lo || a.W_lo || a.pair_lo || !(a.mode == A_CONV3 || a.mode == A_CONV3_UP2) || !conv_patch_eligible(a)) return 0;
+static int conv3p_split_slices(const GemmArgs& a, int ksl) {       // ksl: splitk_slices(a)
+    if (!g_sw.chunk_split || !g_sw.splitk || a.A_lo || a.W_lo || a.pair_lo || !(a.mode == A_CONV3 || a.mode == A_CONV3_UP2) || !conv_patch_eligible(a)) return 0;
     const int nc1 = a.Cin >> 6;
     // (measured and dropped: the VAE's single-image layers - SD's 64^2 x 512: 16 patches - sliced to fill 256 CUs: 10.80 vs 10.81 ms per guidance call)
-    if (splitk_slices(a) <= 1) {
+    if (ksl <= 1) {
         // one level up (SD-v1.5's 32x32 maps: 4 patches per image, 640 output channels): even the 64-channel column tiles give a nominal
         // batch of four 160 workgroups (120 at config 1's three streams); two halves over the chunks fill the chip
         const long u2 = 4L * (a.Hout >> 4) * (a.Wout >> 4) * cdiv(a.N, 64);
-        return (g_conv3p_split & 2) && u2 <= 192 && nc1 >= 8 ? 2 : 0;
+        return g_sw.chunk_halves && u2 <= 192 && nc1 >= 8 ? 2 : 0;
     }
     const int per = cdiv(nc1, 8);
     const int s = cdiv(nc1, per);
     return s >= 2 ? s : 0;
 }
 
-// host-only: what launch_gemm does with an under-filled problem.  route 0: one launch, 1: K slices of the 128x128 implicit GEMM / dense GEMM
-// + reduction, 2: the patch kernel split over input-channel chunks + reduction
-void gemm_split_plan(const GemmArgs& a, int* route, int* slices) {
-    const int sp = conv3p_split_slices(a);
-    if (sp > 1) { *route = 2; *slices = sp; return; }
-    const int s = g_splitk ? splitk_slices(a) : 1;
-    *route = s > 1 ? 1 : 0; *slices = s;
+// The route of one launch_gemm call, in the order of precedence of its rules.  Split-K is a function of the shape only (not of a forced
+// tile configuration, not of stream capture): the same problem always takes the same path.
+GemmRoute gemm_route(const GemmArgs& a) {
+    const GemmSwitches& s = g_sw;
+    const bool by_shape = s.force_cfg < 0, hilo = a.A_lo || a.W_lo;
+    const int ksl = s.splitk ? splitk_slices(a) : 1;
+    GemmRoute r{};
+    // precise VAE contraction A W + A_lo W + A W_lo.  One launch where the kernel runs the three passes as one K loop (3x3 convolutions
+    // on the gemm16 main loop and on the patch kernel, dense problems on the 16x16x32 family; fp32 output); everywhere else three
+    // launches that accumulate in the fp32 output, as round 3 did.
+    if (hilo && (!by_shape || ksl > 1 || s.triple)) { r.kind = GemmRoute::TRIPLE; return r; }
+    // stride-1 3x3 convolutions with Cin % 64 == 0 that take no K slices: implicit GEMM on the 16x16x32 family's main loop (gemm16.hip,
+    // MODE = A_CONV3) where it has a tile
+    const bool conv16 = a.mode == A_CONV3 && ksl == 1 && by_shape && s.use16 && s.conv16 && s.conv_patch && !a.prefer_patch_conv &&
+                        (r.variant = gemm16_pick(a, 0, &r.wstat)) >= 0;
+    if (hilo) {
+        bool fused;
+        if (conv16) fused = !s.triple16;
+        else if (a.mode == A_DENSE) fused = s.use16 && !s.triple_dense && gemm16_pick(a, a.weights_on_rows, &r.wstat) >= 0;
+        else fused = conv_patch_eligible(a) && !s.triple_patch;
+        if (!fused) { r.kind = GemmRoute::TRIPLE; return r; }
+    }
+    if (conv16) { r.kind = GemmRoute::G16; return r; }
+    // patch convolutions that cannot fill the chip (K slices) are split over their input-channel chunks on the patch kernel, or go through the
+    // split-K implicit GEMM; only the patch kernel's epilogue writes GemmArgs.pair_lo (pair_output_ok)
+    const int chunks = by_shape ? conv3p_split_slices(a, ksl) : 0;
+    if (chunks > 1) { r.kind = GemmRoute::PATCH_SPLIT; r.slices = chunks; return r; }
+    if (conv_patch_eligible(a) && ksl == 1) { r.kind = GemmRoute::PATCH; return r; }
+    if (ksl > 1) { r.kind = GemmRoute::KSPLIT; r.slices = ksl; return r; }
+    // the 16x16x32 family: tile = pure function of the shape (class from the weight side, row tiling from M), no timing involved
+    if (by_shape && s.use16 && (r.variant = gemm16_pick(a, a.weights_on_rows, &r.wstat)) >= 0) { r.kind = GemmRoute::G16; return r; }
+    r.kind = GemmRoute::TILE; r.cfg = pick_config(a);
+    return r;
 }
 
+static GemmArgs single_pass(const GemmArgs& a) { GemmArgs b = a; b.A_lo = nullptr; b.W_lo = nullptr; return b; }
+static size_t split_floats(const GemmArgs& a, const GemmRoute& r) {
+    return r.kind == GemmRoute::PATCH_SPLIT || r.kind == GemmRoute::KSPLIT ? (size_t)r.slices * a.M * ((a.N + 3) & ~3) : 0;
+}
 size_t gemm_splitk_scratch_floats(const GemmArgs& a) {
-    const int SP = conv3p_split_slices(a);
-    if (SP > 1) return (size_t)SP * a.M * ((a.N + 3) & ~3);
-    const int S = splitk_slices(a);
-    return S > 1 ? (size_t)S * a.M * ((a.N + 3) & ~3) : 0;
+    const GemmRoute r = gemm_route(a);
+    return r.kind == GemmRoute::TRIPLE ? gemm_splitk_scratch_floats(single_pass(a)) : split_floats(a, r);
+}
+// pair output (GemmArgs.pair_lo) exists in the patch convolution's fp32 epilogue only (and not under a forced configuration)
+static bool pair_output_ok(const GemmArgs& a, const GemmRoute& r) { return r.kind == GemmRoute::PATCH && a.epi == EPI_F32 && g_sw.force_cfg < 0; }
+bool gemm_pair_output_ok(const GemmArgs& a) { return pair_output_ok(a, gemm_route(a)); }
+// LayerNorm fold (gemm16.hip, "LNF"): the variant a single-pass dense problem takes on the 16x16x32 family, -1: another route.  The engine
+// asks beforehand whether a producer would leave the partials / a consumer has the folded instantiation - and keeps the LayerNorm launch otherwise.
+static int ln_variant(const GemmArgs& a, const GemmRoute& r) { return r.kind == GemmRoute::G16 && !a.A_lo && !a.W_lo && !a.pair_lo ? r.variant : -1; }
+int gemm_ln_emit_bn(const GemmArgs& a_in) {
+    GemmArgs a = a_in; a.ln_part = nullptr; a.ln_emit = (float*)(uintptr_t)256;          // (any non-null value: host-side shape test only)
+    const int v = ln_variant(a, gemm_route(a));
+    return a.epi == EPI_F16 && gemm16_ln_variant_ok(a, v) ? gemm16_variant_bn(v) : 0;
+}
+bool gemm_ln_fold_ok(const GemmArgs& a_in) {
+    GemmArgs a = a_in; a.ln_emit = nullptr; a.ln_part = (const float*)(uintptr_t)256;
+    return gemm16_ln_variant_ok(a, ln_variant(a, gemm_route(a)));
 }
 
 // Partial-sum scratch.  An engine hands in its own buffer (GemmArgs.splitk_ws, sized by the dry pass of its plan: nothing is
@@ -1485,13 +1525,17 @@ static float* splitk_fallback_buffer(size_t need, hipStream_t st) {
     return b.p;
 }
 
-static void launch_gemm_splitk(const GemmArgs& a, int S, hipStream_t st) {
-    const int ldp = (a.N + 3) & ~3;
-    const size_t slice = (size_t)a.M * ldp, need = slice * S;
+// Partial sums of the split routes into fp32 scratch - KSPLIT: K slices on the 128x128 kernel, PATCH_SPLIT: input-channel chunks on the
+// patch kernel, gridDim.y = slices either way - then one reduction launch that applies the epilogue of `a`.
+static void launch_split(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+    const int S = r.slices, ldp = (a.N + 3) & ~3;
+    const size_t slice = (size_t)a.M * ldp, need = split_floats(a, r);
     float* buf = (a.splitk_ws && a.splitk_ws_floats >= need) ? a.splitk_ws : splitk_fallback_buffer(need, st);
     GemmArgs g = a;
     g.epi = EPI_F32; g.bias = nullptr; g.res = nullptr; g.temb = nullptr; g.out = buf; g.ldo = ldp;
-    {
+    if (r.kind == GemmRoute::PATCH_SPLIT) {
+        if (a.mode == A_CONV3_UP2) launch_conv3p<EPI_F32, true>(g, st, S); else launch_conv3p<EPI_F32, false>(g, st, S);
+    } else {
         // 4-deep ring: a slice's workgroup runs alone on its CU and streams cold weights, so the K tiles in flight (3 instead of 1)
         // are what hides the HBM latency (config 1, 2-deep ring: the 8x8 / 16x16 convolutions ran at 0.4 TB/s of weight traffic;
         // 99.9 -> 108.7 steps/s with 4 slots, same with 3 slots or with twice the slices on 2 slots)
@@ -1513,30 +1557,12 @@ static void launch_gemm_splitk(const GemmArgs& a, int S, hipStream_t st) {
         }
 #undef RT_SPLIT_LAUNCH
     }
-    ReduceArgs r{};
-    r.part = buf; r.S = S; r.slice = slice; r.M = a.M; r.N = a.N; r.ldp = ldp; r.epi = a.epi; r.bias = a.bias; r.res = a.res; r.ldres = a.ldres;
-    r.temb = a.temb; r.temb_ld = a.temb_ld; r.rows_per_batch = a.rows_per_batch; r.out = a.out; r.ldo = a.ldo;
+    ReduceArgs p{};
+    p.part = buf; p.S = S; p.slice = slice; p.M = a.M; p.N = a.N; p.ldp = ldp; p.epi = a.epi; p.bias = a.bias; p.res = a.res; p.ldres = a.ldres;
+    p.temb = a.temb; p.temb_ld = a.temb_ld; p.rows_per_batch = a.rows_per_batch; p.out = a.out; p.ldo = a.ldo;
     const size_t work = (size_t)a.M * ((a.epi == EPI_GEGLU ? a.N / 2 : a.N) / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<size_t>(cdiv((int)std::min<size_t>(work, 1u << 30), 256), 2048)), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<size_t>(cdiv((int)std::min<size_t>(work, 1u << 30), 256), 2048)), dim3(256), 0, st, p);
     HIP_CHECK(hipGetLastError());
-}
-
-static void launch_splitk_reduce(const GemmArgs& a, float* buf, int S, size_t slice, int ldp, hipStream_t st) {
-    ReduceArgs r{};
-    r.part = buf; r.S = S; r.slice = slice; r.M = a.M; r.N = a.N; r.ldp = ldp; r.epi = a.epi; r.bias = a.bias; r.res = a.res; r.ldres = a.ldres;
-    r.temb = a.temb; r.temb_ld = a.temb_ld; r.rows_per_batch = a.rows_per_batch; r.out = a.out; r.ldo = a.ldo;
-    const size_t work = (size_t)a.M * ((a.epi == EPI_GEGLU ? a.N / 2 : a.N) / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<size_t>(cdiv((int)std::min<size_t>(work, 1u << 30), 256), 2048)), dim3(256), 0, st, r);
-    HIP_CHECK(hipGetLastError());
-}
-static void launch_conv3p_splitk(const GemmArgs& a, int S, hipStream_t st) {
-    const int ldp = (a.N + 3) & ~3;
-    const size_t slice = (size_t)a.M * ldp, need = slice * S;
-    float* buf = (a.splitk_ws && a.splitk_ws_floats >= need) ? a.splitk_ws : splitk_fallback_buffer(need, st);
-    GemmArgs g = a;
-    g.epi = EPI_F32; g.bias = nullptr; g.res = nullptr; g.temb = nullptr; g.out = buf; g.ldo = ldp;
-    if (a.mode == A_CONV3_UP2) launch_conv3p<EPI_F32, true>(g, st, S); else launch_conv3p<EPI_F32, false>(g, st, S);
-    launch_splitk_reduce(a, buf, S, slice, ldp, st);
 }
 
 static void check_gemm_args(const GemmArgs& a) {
@@ -1562,120 +1588,55 @@ static void check_gemm_args(const GemmArgs& a) {
     if (a.res) RT_REQUIRE(a.ldres % 4 == 0 && ((uintptr_t)a.res & 15) == 0, "gemm: residual must be 16-B aligned");
     if (a.bias) RT_REQUIRE(((uintptr_t)a.bias & 15) == 0, "gemm: bias must be 16-B aligned");
     if (a.temb) RT_REQUIRE(a.temb_ld % 4 == 0 && ((uintptr_t)a.temb & 15) == 0, "gemm: temb must be 16-B aligned");
+    if (a.A_lo || a.W_lo) RT_REQUIRE(a.A_lo && a.W_lo && a.epi == EPI_F32, "gemm: a hi / lo contraction needs both low parts and an fp32 output");
 }
 
-// pair output (GemmArgs.pair_lo) exists in the patch convolution's epilogue only: true when launch_gemm takes this problem there
-bool gemm_pair_output_ok(const GemmArgs& a) {
-    if (a.epi != EPI_F32 || !(a.mode == A_CONV3 || a.mode == A_CONV3_UP2) || g_force_cfg >= 0 || !conv_patch_eligible(a)) return false;
-    if ((g_splitk ? splitk_slices(a) : 1) != 1) return false;
-    if (a.A_lo || a.W_lo) {                                          // hi / lo contraction: only as ONE launch on the patch kernel
-        if (!(a.A_lo && a.W_lo) || (g_no_triple & 1) || (g_no_triple & 4)) return false;
-        int ws = 0;
-        if (a.mode == A_CONV3 && g_use16 && g_conv16 && g_conv_patch && !a.prefer_patch_conv && gemm16_pick(a, 0, &ws) >= 0) return false;
-        return true;
-    }
-    int ws = 0;
-    return !(a.mode == A_CONV3 && g_use16 && g_conv16 && g_conv_patch && !a.prefer_patch_conv && gemm16_pick(a, 0, &ws) >= 0);
-}
-
-// LayerNorm fold (gemm16.hip, "LNF"): which route launch_gemm takes is a pure function of the shape, so the engine can ask beforehand
-// whether a producer would leave the partials / a consumer has the folded instantiation - and keep the LayerNorm launch otherwise.
-int gemm_route16(const GemmArgs& a) {
-    if (a.mode != A_DENSE || a.A_lo || a.W_lo || a.pair_lo || g_force_cfg >= 0 || !g_use16) return -1;
-    if ((g_splitk ? splitk_slices(a) : 1) != 1) return -1;
-    int wstat = 0;
-    return gemm16_pick(a, a.weights_on_rows, &wstat);
-}
-int gemm_ln_emit_bn(const GemmArgs& a_in) {
-    GemmArgs a = a_in; a.ln_part = nullptr; a.ln_emit = (float*)(uintptr_t)256;          // (any non-null value: host-side shape test only)
-    const int v = gemm_route16(a);
-    return a.epi == EPI_F16 && gemm16_ln_variant_ok(a, v) ? gemm16_variant_bn(v) : 0;
-}
-bool gemm_ln_fold_ok(const GemmArgs& a_in) {
-    GemmArgs a = a_in; a.ln_emit = nullptr; a.ln_part = (const float*)(uintptr_t)256;
-    return gemm16_ln_variant_ok(a, gemm_route16(a));
-}
-
-void launch_gemm(const GemmArgs& a, hipStream_t st) {
-    check_gemm_args(a);
-    if (a.ln_part || a.ln_emit) RT_REQUIRE(gemm16_ln_variant_ok(a, gemm_route16(a)), "gemm: LayerNorm fold asked of a route without it (gemm_ln_fold_ok / gemm_ln_emit_bn)");
-    if (a.pair_lo) RT_REQUIRE(gemm_pair_output_ok(a) && a.ldo % 4 == 0 && ((uintptr_t)a.pair_lo & 7) == 0, "gemm: pair output is only built into the patch convolution (gemm_pair_output_ok)");
+// launch_gemm after the argument check, on the route of `a`
+static void launch_routed(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+    if (a.ln_part || a.ln_emit) RT_REQUIRE(gemm16_ln_variant_ok(a, ln_variant(a, r)), "gemm: LayerNorm fold asked of a route without it (gemm_ln_fold_ok / gemm_ln_emit_bn)");
+    if (a.pair_lo) RT_REQUIRE(pair_output_ok(a, r) && ((uintptr_t)a.pair_lo & 7) == 0, "gemm: pair output is only built into the patch convolution (gemm_pair_output_ok)");
     // In-place residual (out == res) is safe: every element is read and written by the same thread.
-    // split-K is a function of the shape only (not of a forced tile configuration, not of stream capture): the same problem
-    // always takes the same path.  Debug bit 2 (rt_op_gemm_debug(4)) switches it off for A/B tests.
-    if (a.A_lo || a.W_lo) {
-        // precise VAE contraction A W + A_lo W + A W_lo.  One launch where the kernel runs the three passes as one K loop (3x3
-        // convolutions on the gemm16 main loop and on the patch kernel, fp32 output); everywhere else three launches that accumulate
-        // in the fp32 output, as round 3 did.
-        RT_REQUIRE(a.A_lo && a.W_lo && a.epi == EPI_F32, "gemm: a hi / lo contraction needs both low parts and an fp32 output");
-        bool fused = false;
-        if ((a.mode == A_CONV3 || a.mode == A_CONV3_UP2) && g_force_cfg < 0 && (g_splitk ? splitk_slices(a) : 1) == 1 && !(g_no_triple & 1)) {
-            int ws = 0;
-            const bool to16 = a.mode == A_CONV3 && g_use16 && g_conv16 && g_conv_patch && !a.prefer_patch_conv && gemm16_pick(a, 0, &ws) >= 0;
-            fused = (to16 && !(g_no_triple & 2)) || (!to16 && conv_patch_eligible(a) && !(g_no_triple & 4));        // exactly the two routes below that take these problems
-        }
-        if (a.mode == A_DENSE && g_force_cfg < 0 && g_use16 && (g_splitk ? splitk_slices(a) : 1) == 1 && !(g_no_triple & 1) && !(g_no_triple & 8)) {
-            int ws = 0;
-            fused = gemm16_pick(a, a.weights_on_rows, &ws) >= 0;     // dense on the 16x16x32 family (round 4): the route at the bottom of this function
-        }
-        if (!fused) {
-            RT_REQUIRE(!a.pair_lo, "gemm: pair output on a route without it");      // (unreachable: gemm_pair_output_ok mirrors this routing; kept as a guard)
-            GemmArgs b = a; b.A_lo = nullptr; b.W_lo = nullptr;
+    switch (r.kind) {
+        case GemmRoute::TRIPLE: {
+            GemmArgs b = single_pass(a);
             launch_gemm(b, st);
             b.bias = nullptr; b.res = a.out; b.ldres = a.ldo;
             b.A = a.A_lo; launch_gemm(b, st);
             b.A = a.A; b.W = a.W_lo; launch_gemm(b, st);
             return;
         }
+        case GemmRoute::G16: launch_gemm16_variant(a, r.variant, r.wstat, st); return;
+        case GemmRoute::PATCH:
+            if (a.mode == A_CONV3_UP2) { if (a.epi == EPI_F16) launch_conv3p<EPI_F16, true>(a, st); else launch_conv3p<EPI_F32, true>(a, st); }
+            else switch (a.epi) {
+                case EPI_BF16: launch_conv3p<EPI_BF16, false>(a, st); break;
+                case EPI_F32: launch_conv3p<EPI_F32, false>(a, st); break;
+                case EPI_F16: launch_conv3p<EPI_F16, false>(a, st); break;
+                default: launch_conv3p<EPI_BF16_TEMB, false>(a, st); break;
+            }
+            return;
+        case GemmRoute::PATCH_SPLIT:
+        case GemmRoute::KSPLIT: launch_split(a, r, st); return;
+        case GemmRoute::TILE: launch_with_cfg(a, r.cfg, st); return;
     }
-    const int ksl = g_splitk ? splitk_slices(a) : 1;
-    // patch convolutions that cannot fill the chip (< 128 workgroups) go through the split-K implicit GEMM as well
-    const bool patch_underfilled = ksl > 1 && a.mode != A_DENSE;
-    if (a.mode == A_CONV3 && ksl == 1 && g_force_cfg < 0 && g_use16 && g_conv16 && g_conv_patch && !a.prefer_patch_conv) {
-        // stride-1 3x3 convolutions with Cin % 64 == 0: implicit GEMM on the 16x16x32 family's main loop (gemm16.hip, MODE = A_CONV3)
-        int wstat = 0;
-        const int v = gemm16_pick(a, 0, &wstat);
-        if (v >= 0) { RT_REQUIRE(!a.pair_lo, "gemm: pair output on a route without it"); launch_gemm16_variant(a, v, 0, st); return; }
-    }
-    // only the patch kernel's epilogue writes GemmArgs.pair_lo: every other route below and above would store fp32 into the bf16 hi plane
-    const bool to_patch = conv_patch_eligible(a) && !patch_underfilled;
-    if (a.pair_lo && !to_patch) throw rt_error(RT_E_INVALID, "gemm: pair output on a route without it");
-    if (g_force_cfg < 0 && (patch_underfilled || to_patch)) {
-        const int sp = conv3p_split_slices(a);
-        if (sp > 1) { launch_conv3p_splitk(a, sp, st); return; }
-    }
-    if (to_patch) {
-        if (a.mode == A_CONV3_UP2) { if (a.epi == EPI_F16) launch_conv3p<EPI_F16, true>(a, st); else launch_conv3p<EPI_F32, true>(a, st); }
-        else switch (a.epi) {
-            case EPI_BF16: launch_conv3p<EPI_BF16, false>(a, st); break;
-            case EPI_F32: launch_conv3p<EPI_F32, false>(a, st); break;
-            case EPI_F16: launch_conv3p<EPI_F16, false>(a, st); break;
-            default: launch_conv3p<EPI_BF16_TEMB, false>(a, st); break;
-        }
-        return;
-    }
-    if (ksl > 1) { launch_gemm_splitk(a, ksl, st); return; }
-    if (g_force_cfg < 0 && g_use16) {
-        // the 16x16x32 family: tile = pure function of the shape (class from the weight side, row tiling from M), no timing involved
-        int wstat = 0;
-        const int v = gemm16_pick(a, a.weights_on_rows, &wstat);
-        if (v >= 0) { launch_gemm16_variant(a, v, wstat, st); return; }
-    }
-    launch_with_cfg(a, pick_config(a), st);
+}
+void launch_gemm(const GemmArgs& a, hipStream_t st) {
+    check_gemm_args(a);
+    launch_routed(a, gemm_route(a), st);
 }
 
 // Two independent dense problems that read the same activations (attn1: the stacked Q|K projection and V^T = Wv X^T): ONE grouped
 // launch of the 16x16x32 family where both take it and a grouped instantiation exists (gemm16.hip, gemm16_dual_kernel: the same tile
 // bodies, bit-identical results), otherwise one launch each.  Like every routing decision here a function of the shapes only.
-bool gemm_pair_is_grouped(const GemmArgs& a, const GemmArgs& b) {
-    return g_pair && g_force_cfg < 0 && g_use16 && a.mode == A_DENSE && b.mode == A_DENSE && (g_splitk ? splitk_slices(a) : 1) == 1 &&
-           (g_splitk ? splitk_slices(b) : 1) == 1 && gemm16_pair_variant(a, b) >= 0;
+static int pair_grouped(const GemmArgs& a, const GemmRoute& ra, const GemmArgs& b, const GemmRoute& rb) {
+    return g_sw.pair && ra.kind == GemmRoute::G16 && rb.kind == GemmRoute::G16 ? gemm16_pair_variant(a, ra.variant, ra.wstat, b, rb.variant, rb.wstat) : -1;
 }
+int gemm_pair_grouped(const GemmArgs& a, const GemmArgs& b) { return pair_grouped(a, gemm_route(a), b, gemm_route(b)); }
 void launch_gemm_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
-    if (gemm_pair_is_grouped(a, b)) {
-        check_gemm_args(a); check_gemm_args(b);
-        if (launch_gemm16_pair(a, b, st)) return;
-    }
-    launch_gemm(a, st);
-    launch_gemm(b, st);
+    check_gemm_args(a); check_gemm_args(b);
+    const GemmRoute ra = gemm_route(a), rb = gemm_route(b);
+    const int pair = pair_grouped(a, ra, b, rb);
+    if (pair >= 0) { launch_gemm16_pair(a, b, pair, st); return; }
+    launch_routed(a, ra, st);
+    launch_routed(b, rb, st);
 }

@@ -596,14 +596,13 @@ static void launch_dual_v(const GemmArgs& a, const GemmArgs& b, hipStream_t st) 
     hipLaunchKernelGGL((gemm16_dual_kernel<TMW_A, TNW_A, S_A, TMW_B, TNW_B, LN>), dim3(nwg_a + nwg_b), dim3(512), LDS, st, a, b, nwg_a);
     HIP_CHECK(hipGetLastError());
 }
-// Grouped launch of (a: tokens on the rows, class A) + (b: weights on the rows, class B transposed).  Returns false - nothing launched -
-// when the pair of tiles gemm16_pick gives the two problems has no grouped instantiation; the caller then launches them one by one.
-int gemm16_pair_variant(const GemmArgs& a_in, const GemmArgs& b_in) {            // id of the grouped instantiation (0..3), -1: none
+// Grouped launch of (a: tokens on the rows, class A) + (b: weights on the rows, class B transposed) for the pair of tiles va / vb that
+// gemm16_pick gives the two problems (wa / wb: their W-stationary orders).  -1: no grouped instantiation; the caller then launches them
+// one by one.
+int gemm16_pair_variant(const GemmArgs& a_in, int va, int wa, const GemmArgs& b_in, int vb, int wb) {            // id of the grouped instantiation (0..3), -1: none
     if (a_in.mode != A_DENSE || b_in.mode != A_DENSE || a_in.epi != EPI_BF16 || b_in.epi != EPI_BF16 || a_in.weights_on_rows || !b_in.weights_on_rows) return -1;
     if (a_in.res || b_in.res || a_in.A_lo || b_in.A_lo) return -1;
     if ((a_in.ln_part != nullptr) != (b_in.ln_part != nullptr) || a_in.ln_emit || b_in.ln_emit) return -1;       // both fold the same LayerNorm or neither
-    int wa = 0, wb = 0;
-    const int va = gemm16_pick(a_in, 0, &wa), vb = gemm16_pick(b_in, 1, &wb);
     if (wa || wb) return -1;
     // instantiated pairs (Q|K tile, V^T tile): 7 / 4 streams of a rich-text step at both SDXL attention levels; the 2-stream plain pass
     if (vb == 6 && va == 4) return 0;                                 // 224 x 320 + 160 x 224
@@ -612,27 +611,24 @@ int gemm16_pair_variant(const GemmArgs& a_in, const GemmArgs& b_in) {           
     if (vb == 7 && va == 2) return 3;                                 // 224 x 256 + 160 x 128 (2 x 4096 tokens x 640 channels: 185 + 256)
     return -1;
 }
-bool launch_gemm16_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t st) {
-    const int va = gemm16_pair_variant(a_in, b_in);
-    if (va < 0) return false;
+void launch_gemm16_pair(const GemmArgs& a_in, const GemmArgs& b_in, int pair, hipStream_t st) {
     if (a_in.ln_part) {
         RT_REQUIRE(a_in.ln_s && b_in.ln_s && (a_in.ln_npair == 1 || a_in.ln_npair == 2 || a_in.ln_npair == 4) && b_in.ln_npair == a_in.ln_npair && a_in.ln_inv_c > 0.f &&
                    a_in.ln_ld >= a_in.M && b_in.ln_ld >= b_in.N, "gemm16 pair: LayerNorm-fold consumer arguments");
-        switch (va) {
+        switch (pair) {
             case 0: launch_dual_v<7, 5, 2, 5, 7, true>(a_in, b_in, st); break;
             case 1: launch_dual_v<7, 4, 2, 5, 7, true>(a_in, b_in, st); break;
             case 2: launch_dual_v<4, 4, 3, 5, 2, true>(a_in, b_in, st); break;
             default: launch_dual_v<7, 4, 2, 5, 4, true>(a_in, b_in, st); break;
         }
-        return true;
+        return;
     }
-    switch (va) {
+    switch (pair) {
         case 0: launch_dual_v<7, 5, 2, 5, 7>(a_in, b_in, st); break;
         case 1: launch_dual_v<7, 4, 2, 5, 7>(a_in, b_in, st); break;
         case 2: launch_dual_v<4, 4, 3, 5, 2>(a_in, b_in, st); break;
         default: launch_dual_v<7, 4, 2, 5, 4>(a_in, b_in, st); break;
     }
-    return true;
 }
 
 // Tile choice, a pure function of the shape (no timing): the CLASS (A / B, i.e. the accumulation order of an output element) follows

@@ -1,5 +1,4 @@
-"""Host logic of the split rule for problems that cannot fill the chip (csrc/gemm.hip::splitk_slices / conv3p_split_slices through
-rt_op_split_plan; no GPU): route and slice count are pure functions of ONE stream's shape - never of the batch - so a stream's k order
+"""Host logic of the split rule for problems that cannot fill the chip (csrc/gemm.hip::gemm_route through rt_op_split_plan; no GPU): route and slice count are pure functions of ONE stream's shape - never of the batch - so a stream's k order
 is the same alone and inside any batch, and the SD-v1.5 shapes take the routes LABNOTES R6.10 documents."""
 import ctypes as C
 
@@ -54,3 +53,15 @@ def test_sd15_shapes_take_the_documented_routes(plan):
     assert plan(0, EPI_F16, 3, 64, 1280, 1280)[0] == KSLICES
     assert plan(0, EPI_F16, 3, 64, 1280, 5120) == (KSLICES, 12)
     assert plan(0, EPI_F16, 7, 1024, 1280, 5120) == (ONE, 1)
+
+
+def test_plan_is_the_route_launch_gemm_takes(plan):
+    lib = load_library()
+    # a one-slice stride-1 3x3 conv that gemm16.hip has a tile for runs there: the two-halves chunk split comes after that route
+    assert plan(1, EPI_F16, 3, 256, 2560, 512) == (ONE, 1)
+    assert lib.rt_op_gemm_force_config(0) == 0
+    try:
+        # a forced tile configuration keeps the chunk split out: the K slices of the 128x128 implicit GEMM
+        assert plan(1, EPI_TEMB, 3, 256, 1280, 1280) == (KSLICES, 3)
+    finally:
+        lib.rt_op_gemm_force_config(-1)
