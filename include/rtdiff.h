@@ -91,6 +91,17 @@ int rt_set_schedule(rt_engine* e, int kind, const float* timesteps_host, int n_t
 /* sampler state: latents [1,4,h,w] f32 (copied in); the reference stream starts as a clone (rd.py:93, xl.py:774) */
 int rt_set_latents(rt_engine* e, const float* latents, int h, int w);
 int rt_get_latents(rt_engine* e, float* latents_out, float* latents_ref_out /* may be NULL */);
+/* image start (no counterpart in the reference, whose loops start from noise: rd.py:91-93, xl.py:766-774).  x0 [4,h,w] f32 (encoded
+ * image, already scaled), noise [4,h,w] f32, keep [h,w] f32 in [0,1] or NULL (nothing pinned): copied into buffers the engine owns,
+ * allocated here and never inside a step.  x0 == NULL clears the source. */
+int rt_set_source(rt_engine* e, const float* x0, const float* noise, const float* keep, int h, int w);
+/* latents = a*x0 + b*noise, the reference stream the same values (as rt_set_latents clones); resets the sampler state like rt_set_latents.
+ * (a, b) = the scheduler's start level (schedulers.py start_level()).  RT_E_STATE without a source. */
+int rt_noise_latents(rt_engine* e, float a, float b);
+/* latents = keep*(a*x0 + b*noise) + (1 - keep)*latents: pins the kept pixels to the source at the level the step just reached
+ * (schedulers.py source_levels()).  One elementwise launch on the engine's stream (hipGraph-capturable), touches the latents only, not the
+ * reference stream.  RT_E_STATE without a source; a no-op when the source has no keep mask.  fp32 order: csrc/step.hip. */
+int rt_source_blend(rt_engine* e, float a, float b);
 
 /* hot path ---------------------------------------------------------------------------------------- */
 /* one iteration of the rich-text loop (rd.py:99-173 / xl.py:779-872 without colour guidance):

@@ -220,7 +220,7 @@ def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=No
     if os.path.exists(mi):
         fz = json.load(open(mi)).get("force_zeros_for_empty_prompt", True)
     return dict(unet_state_dict=unet_sd, config=unet_cfg, vae=vae, tokenizer=tok, vae_scaling_factor=vae_cfg["scaling_factor"],
-                text_encoders=ClipEncodersXL([tok, tok2], [enc1, enc2], dev, fz))
+                text_encoders=ClipEncodersXL([tok, tok2], [enc1, enc2], dev, fz), vae_dir=os.path.join(load_path, "vae"))
 
 
 def load_pipeline(load_path, kind="SD", device=0, latent_hw=None, lora_path=None, lora_scale=1.0):

@@ -142,6 +142,8 @@ void launch_inject_add(f16_t* out, const f16_t* sc, const float* hres, const int
 void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_t st);
 void launch_pad_ctx(const float* ctx, bf16_t* out, int P, int D, hipStream_t st);
 void launch_background_blend(float* lat, const float* lat_ref, const float* mask_last, int n, hipStream_t st);
+void launch_noise_latents(float* lat, float* lat_ref, const float* x0, const float* noise, float a, float b, int n, hipStream_t st);
+void launch_source_blend(float* lat, const float* x0, const float* noise, const float* keep, float a, float b, int HW, hipStream_t st);
 
 #include "step.h"
 
@@ -959,6 +961,11 @@ struct rt_engine {
     void region_step_part(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend, int part, int nparts, int* first, int* count, int* plan_info);
     void region_step_finish(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend);
     bool pending_blend = false;
+    // the source image of an image start (rt_set_source): device copies owned by the engine, one allocation at the plan's latent size
+    float* src_buf = nullptr;                    // x0 [4, HW] | noise [4, HW] | keep [HW]
+    float *src_x0 = nullptr, *src_noise = nullptr, *src_keep = nullptr;
+    bool has_source = false, has_keep = false;
+    int src_h = 0, src_w = 0;
     void plain_step(int i, float g);
     void plain_forward(int i, int first, int count);
     void plain_finish(int i, float g);
@@ -1070,7 +1077,7 @@ int rt_destroy(rt_engine* e) {
     if (e->arena_base) {
         (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->stream);
         for (auto& r : e->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->temb_tab_dev); (void)hipFree(e->splitk_buf); (void)hipStreamDestroy(e->own_stream);
+        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->temb_tab_dev); (void)hipFree(e->splitk_buf); (void)hipFree(e->src_buf); (void)hipStreamDestroy(e->own_stream);
     }
     delete e;
     return RT_OK;
@@ -1157,6 +1164,42 @@ int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
         e->lat_h = h; e->lat_w = w;
         e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
         e->dpm_lower_order_nums = 0; e->dpm_head = 0;
+    })
+}
+int rt_set_source(rt_engine* e, const float* x0, const float* noise, const float* keep, int h, int w) {
+    RT_TRY(e, {
+        need_device(e);
+        if (!x0) { e->has_source = e->has_keep = false; return RT_OK; }
+        RT_REQUIRE(noise, "rt_set_source: noise is NULL");
+        RT_REQUIRE(h >= 1 && w >= 1 && h <= e->cfg.latent_h && w <= e->cfg.latent_w, "rt_set_source: bad shape");
+        const size_t cap = (size_t)e->cfg.latent_h * e->cfg.latent_w, hw = (size_t)h * w;
+        if (!e->src_buf) {
+            HIP_CHECK(hipSetDevice(e->device));
+            HIP_CHECK(hipMalloc((void**)&e->src_buf, 9 * cap * 4));
+            e->src_x0 = e->src_buf; e->src_noise = e->src_buf + 4 * cap; e->src_keep = e->src_buf + 8 * cap;
+        }
+        HIP_CHECK(hipMemcpyAsync(e->src_x0, x0, 4 * hw * 4, hipMemcpyDeviceToDevice, e->stream));
+        HIP_CHECK(hipMemcpyAsync(e->src_noise, noise, 4 * hw * 4, hipMemcpyDeviceToDevice, e->stream));
+        if (keep) HIP_CHECK(hipMemcpyAsync(e->src_keep, keep, hw * 4, hipMemcpyDeviceToDevice, e->stream));
+        e->has_source = true; e->has_keep = keep != nullptr; e->src_h = h; e->src_w = w;
+    })
+}
+int rt_noise_latents(rt_engine* e, float a, float b) {
+    RT_TRY(e, {
+        need_device(e);
+        if (!e->has_source) throw rt_error(RT_E_STATE, "rt_noise_latents: no source (rt_set_source)");
+        launch_noise_latents(e->lat, e->lat_ref, e->src_x0, e->src_noise, a, b, 4 * e->src_h * e->src_w, e->stream);
+        e->lat_h = e->src_h; e->lat_w = e->src_w;
+        e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
+        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
+    })
+}
+int rt_source_blend(rt_engine* e, float a, float b) {
+    RT_TRY(e, {
+        need_device(e);
+        if (!e->has_source) throw rt_error(RT_E_STATE, "rt_source_blend: no source (rt_set_source)");
+        if (e->src_h != e->lat_h || e->src_w != e->lat_w) throw rt_error(RT_E_STATE, "rt_source_blend: source and latents differ in shape");
+        if (e->has_keep) launch_source_blend(e->lat, e->src_x0, e->src_noise, e->src_keep, a, b, e->lat_h * e->lat_w, e->stream);
     })
 }
 int rt_get_latents(rt_engine* e, float* out, float* out_ref) {

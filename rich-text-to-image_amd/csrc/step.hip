@@ -251,3 +251,36 @@ void launch_background_blend(float* lat, const float* lat_ref, const float* mask
     hipLaunchKernelGGL(background_blend_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, lat, lat_ref, mask_last, n);
     HIP_CHECK(hipGetLastError());
 }
+
+// Image start and source pinning (rt_noise_latents / rt_source_blend): kernels of their own, nothing of the step epilogues changes.
+// x0, noise [4, HW]; keep [HW], one value per pixel for all four channels.  fp32 operation order, every line one rounding:
+//   p = a * x0
+//   s = fma(b, noise, p)                        the source at level (a, b)
+// noise_latents:  lat = lat_ref = s
+// source_blend:
+//   q = 1 - keep
+//   r = q * lat
+//   lat = fma(keep, s, r)
+// keep == 0 leaves lat's bits alone (fma(0, s, 1 * lat)); keep == 1 at the level (1, 0) gives x0's bits (fma(1, fma(0, noise, x0), 0 * lat)).
+__global__ void noise_latents_kernel(float* lat, float* lat_ref, const float* x0, const float* noise, float a, float b, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float s = __fmaf_rn(b, noise[i], __fmul_rn(a, x0[i]));
+    lat[i] = s; lat_ref[i] = s;
+}
+__global__ void source_blend_kernel(float* lat, const float* x0, const float* noise, const float* keep, float a, float b, int HW) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 4 * HW) return;
+    const float k = keep[i % HW];
+    const float s = __fmaf_rn(b, noise[i], __fmul_rn(a, x0[i]));
+    const float r = __fmul_rn(__fsub_rn(1.f, k), lat[i]);
+    lat[i] = __fmaf_rn(k, s, r);
+}
+void launch_noise_latents(float* lat, float* lat_ref, const float* x0, const float* noise, float a, float b, int n, hipStream_t st) {
+    hipLaunchKernelGGL(noise_latents_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, lat, lat_ref, x0, noise, a, b, n);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_source_blend(float* lat, const float* x0, const float* noise, const float* keep, float a, float b, int HW, hipStream_t st) {
+    hipLaunchKernelGGL(source_blend_kernel, dim3(cdiv(4 * HW, 256)), dim3(256), 0, st, lat, x0, noise, keep, a, b, HW);
+    HIP_CHECK(hipGetLastError());
+}

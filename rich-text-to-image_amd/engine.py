@@ -74,6 +74,7 @@ _SYMBOLS = [
     "rt_region_step_part", "rt_region_step_finish", "rt_eps_info", "rt_op_split_range",
     "rt_op_ln_gemm", "rt_op_gemm_emit_partials", "rt_op_ln_partials", "rt_op_probes_built", "rt_op_attention_units_plan",
     "rt_plain_step_part", "rt_plain_step_finish", "rt_vae_encoder_create", "rt_vae_encode", "rt_vae_posterior_sample",
+    "rt_set_source", "rt_noise_latents", "rt_source_blend",
 ]
 
 
@@ -279,6 +280,27 @@ class Engine:
         assert l.shape[0] == 1 and l.shape[1] == 4
         self._chk(self.lib.rt_set_latents(self.h, _ptr(l), l.shape[2], l.shape[3]))
         self.synchronize()
+
+    # ---- image start: the source (encoded image + noise + optional keep mask), its noised start and the per-step pin
+    def set_source(self, x0, noise=None, keep=None):
+        """x0, noise [1,4,h,w]; keep [h,w] or [1,1,h,w] in [0,1] or None (nothing pinned).  x0 None clears the source."""
+        if x0 is None:
+            self._chk(self.lib.rt_set_source(self.h, None, None, None, 0, 0))
+            return
+        x0, noise = x0.contiguous().float(), noise.contiguous().float()
+        h, w = x0.shape[-2], x0.shape[-1]
+        assert tuple(x0.shape) == (1, 4, h, w) and noise.shape == x0.shape, (tuple(x0.shape), tuple(noise.shape))
+        if keep is not None:
+            keep = keep.contiguous().float()
+            assert keep.numel() == h * w and tuple(keep.shape[-2:]) == (h, w), tuple(keep.shape)
+        self._chk(self.lib.rt_set_source(self.h, _ptr(x0), _ptr(noise), _ptr(keep), h, w))
+        self.synchronize()
+
+    def noise_latents(self, a, b):
+        self._chk(self.lib.rt_noise_latents(self.h, C.c_float(float(a)), C.c_float(float(b))))
+
+    def source_blend(self, a, b):
+        self._chk(self.lib.rt_source_blend(self.h, C.c_float(float(a)), C.c_float(float(b))))
 
     # ---- token-map attention store
     def attn_modules(self):

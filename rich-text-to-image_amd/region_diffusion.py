@@ -2,6 +2,7 @@
 on the HIP engine.  Same method names / argument meaning / attributes as the reference."""
 import torch
 
+from . import img2img
 from .engine import SD15_CONFIG
 from .schedulers import DPMSolverTables, PNDMTables
 from .unet import HipUNet2DConditionModel
@@ -102,8 +103,14 @@ class RegionDiffusion:
     # rd.py:86-174
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, use_guidance=False, text_format_dict={}, inject_selfattn=0, inject_background=0,
-                        elide_dead_forwards=False):
-        if latents is None:
+                        elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None):
+        """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
+        `strength` of the schedule and pin the pixels of `keep_source` to the image at every step.  image=None: the reference's
+        behaviour, the other three are not read."""
+        img2img.check_start(image, latents)
+        if image is not None:
+            latents = self._start_noise(image, noise)
+        elif latents is None:
             latents = torch.randn((1, self.unet.in_channels, height // 8, width // 8), device=self.device)
         if use_guidance and not hasattr(self.vae, "color_guidance"):
             raise RuntimeError("use_guidance=True needs a rich_text_to_image_amd.engine.VaeDecoder as `vae` (rd.py:151-168)")
@@ -112,13 +119,17 @@ class RegionDiffusion:
         h, w = latents.shape[2], latents.shape[3]
         n_prompts = text_embeddings.shape[0]
         eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts)      # R+1 forwards, +2 reference forwards
-        self.scheduler.set_timesteps(num_inference_steps)
+        self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
+        keep = None
+        if image is not None:
+            x0 = img2img.source_latents(self, image)
+            keep = img2img.keep_mask(self, keep_source, h, w)
         eng.set_prompts(text_embeddings.to(self.device))
         eng.set_masks([m.to(self.device) for m in self.masks])
         tfd = text_format_dict or {}
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
-        eng.set_latents(latents.to(self.device))
+        levels = self._start(eng, latents, None if image is None else x0, keep)
         for i, t in enumerate(self.scheduler.timesteps):
             if getattr(self, "split_image", False):      # intra-image split over the ranks of the process group (launcher.split_region_step)
                 from .launcher import assert_ranks_agree, split_region_step
@@ -143,7 +154,34 @@ class RegionDiffusion:
                     else:
                         guide()
                 eng.background_blend()
-        return eng.read_latents(h, w)
+            if keep is not None:
+                eng.source_blend(*levels[i])
+        return self._finish(eng, h, w, image is not None)
+
+    # image start (img2img.py): the noise is drawn where `latents` is drawn, so the plain and the rich pass of one seed share their start
+    def _start_noise(self, image, noise):
+        h, w = img2img.latent_shape(image)
+        if noise is None:
+            noise = torch.randn((1, self.unet.in_channels, h, w), device=self.device)
+        if tuple(noise.shape) != (1, 4, h, w):
+            raise ValueError(f"noise: expected {(1, 4, h, w)}, got {tuple(noise.shape)}")
+        return noise
+
+    def _start(self, eng, latents, x0, keep):
+        """Sets the engine's start latents: `latents` as given, or - with a source x0 - a*x0 + b*latents at the scheduler's start level
+        (`latents` is the noise then).  Returns the per-iteration source levels (None without a source)."""
+        if x0 is None:
+            eng.set_latents(latents.to(self.device))
+            return None
+        eng.set_source(x0, latents.to(self.device), keep)
+        eng.noise_latents(*self.scheduler.start_level())
+        return self.scheduler.source_levels()
+
+    def _finish(self, eng, h, w, had_source):
+        out = eng.read_latents(h, w)
+        if had_source:
+            eng.set_source(None)
+        return out
 
     def predict_x0(self, x_t, eps_t, t):                                    # rd.py:176-178
         a = self.alphas_cumprod[int(t)].to(x_t.device)
@@ -151,26 +189,32 @@ class RegionDiffusion:
 
     # rd.py:180-225 (plain pass; attention-map capture = SURVEY 8a row a10, next)
     def produce_attn_maps(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50,
-                          guidance_scale=7.5, latents=None):
+                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts]
         emb = self.get_text_embeds(prompts, negative_prompts)
-        lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents)
+        lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents, image=image, strength=strength, noise=noise)
         return self.latents_to_uint8(lat)
 
-    def plain_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None):
-        if latents is None:
+    def plain_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
+                      image=None, strength=0.8, noise=None):
+        img2img.check_start(image, latents)
+        if image is not None:
+            latents = self._start_noise(image, noise)
+        elif latents is None:
             latents = torch.randn((1, self.unet.in_channels, height // 8, width // 8), device=self.device)
         h, w = latents.shape[2], latents.shape[3]
         n_prompts = text_embeddings.shape[0]
         eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts)      # R+1 forwards, +2 reference forwards
-        self.scheduler.set_timesteps(num_inference_steps)
+        self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
+        hooks = getattr(self, "_tokenmap_hooks", False)
+        if image is not None:
+            img2img.check_tokenmap_iterations(hooks, len(self.scheduler.timesteps))
         eng.set_prompts(text_embeddings.to(self.device))
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
-        eng.set_latents(latents.to(self.device))
-        hooks = getattr(self, "_tokenmap_hooks", False)
+        self._start(eng, latents, None if image is None else img2img.source_latents(self, image), None)
         if hooks:
             self._store_begin(eng)
         for i in range(len(self.scheduler.timesteps)):
@@ -181,7 +225,7 @@ class RegionDiffusion:
                 eng.plain_step(i, guidance_scale)
         if hooks:
             self._store_end(eng, len(self.scheduler.timesteps))
-        return eng.read_latents(h, w)
+        return self._finish(eng, h, w, image is not None)
 
     def decode_latents(self, latents):                                      # rd.py:227-236
         if self.vae is None:
@@ -199,7 +243,8 @@ class RegionDiffusion:
 
     # rd.py:248-273
     def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
-                      latents=None, text_format_dict={}, use_guidance=False, inject_selfattn=0, inject_background=0):
+                      latents=None, text_format_dict={}, use_guidance=False, inject_selfattn=0, inject_background=0,
+                      image=None, strength=0.8, noise=None, keep_source=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
@@ -208,7 +253,8 @@ class RegionDiffusion:
         latents = self.produce_latents(text_embeds, height=height, width=width, latents=latents,
                                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                        use_guidance=use_guidance, text_format_dict=text_format_dict,
-                                       inject_selfattn=inject_selfattn, inject_background=inject_background)
+                                       inject_selfattn=inject_selfattn, inject_background=inject_background,
+                                       image=image, strength=strength, noise=noise, keep_source=keep_source)
         return self.latents_to_uint8(latents)
 
     # hook surface of the reference (rd.py:397-443): token-map capture is the "next" row f1

@@ -4,6 +4,7 @@ import types
 
 import torch
 
+from . import img2img
 from .engine import SDXL_CONFIG
 from .schedulers import DPMSolverTables, EulerTables
 from .unet import HipUNet2DConditionModel
@@ -17,12 +18,14 @@ class StableDiffusionXLPipelineOutput(dict):
 
 class RegionDiffusionXL:
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
-                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None):
+                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None):
         """`RegionDiffusionXL(load_path="stabilityai/stable-diffusion-xl-base-1.0")` as sample.py:28-30 calls it (xl.py:105-120
         loads every component from `load_path`): a diffusers-layout directory, or a hub id resolved to one without a network
         (checkpoint.resolve_checkpoint: $RTDIFF_SDXL_PATH for the default id, then the Hugging Face hub cache).  Callers that hold
         the weights pass `unet_state_dict` (+ optional vae / text_encoders / tokenizer) and `load_path` is not read.
-        `scheduler`: EulerTables (the default, xl.py:120) or DPMSolverTables; assigning `self.scheduler` later works the same way."""
+        `scheduler`: EulerTables (the default, xl.py:120) or DPMSolverTables; assigning `self.scheduler` later works the same way.
+        `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
+        `vae_dir` on its first call."""
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device(f"cuda:{self.device_index}")
         self.device_type = "cuda"
@@ -32,8 +35,11 @@ class RegionDiffusionXL:
             unet_state_dict, config = comp["unet_state_dict"], config or comp["config"]
             vae, text_encoders, tokenizer = vae or comp["vae"], text_encoders or comp["text_encoders"], tokenizer or comp["tokenizer"]
             vae_scaling_factor = comp["vae_scaling_factor"]
+            vae_dir = vae_dir or comp.get("vae_dir")
         self.unet = HipUNet2DConditionModel(config or SDXL_CONFIG, unet_state_dict, self.device_index)
         self.vae = vae
+        self.vae_dir, self.vae_encoder = vae_dir, vae_encoder
+        self._lazy_encoder = None                  # (encoder built from vae_dir, or None: no encoder weights there)
         # Optional (round 6): a second VaeDecoder used ONLY for the colour-guidance pass (xl.py:849-867).  The reference runs the SDXL VAE in
         # fp32 because it overflows in fp16 (xl.py:856), and `vae` (precise = three bf16 MFMA passes) follows it.  A one-pass bf16 engine has
         # fp32's range; over the 50-step guided schedule it leaves the latents where the precise engine leaves them (update-relative error
@@ -71,13 +77,44 @@ class RegionDiffusionXL:
                                "pass prompt_embeds / pooled_prompt_embeds instead")
         return self.text_encoders(prompt, negative_prompt)
 
+    # RegionDiffusion.encode_imgs (rd.py:238-246) with the SDXL VAE: its config and scaling factor, fp32-class contractions like the
+    # pipeline's decoder (xl.py:856).  In order: a VAE object with `.encode`, the `vae_encoder` given to the constructor, an encoder
+    # built from `vae_dir` on the first call (checkpoint.load_vae_encoder(..., "SDXL", ...)), else NotImplementedError.
+    def encode_imgs(self, imgs):
+        if hasattr(self.vae, "encode"):
+            imgs = 2 * imgs - 1
+            return self.vae.encode(imgs).latent_dist.sample() * self.vae_scaling_factor
+        enc = self.vae_encoder or self._encoder_from_dir(imgs.shape[-2], imgs.shape[-1])
+        if enc is None:
+            raise NotImplementedError("encode_imgs needs VAE encoder weights: a VAE with `.encode`, `vae_encoder=`, or an AutoencoderKL "
+                                      "directory whose weights hold `encoder.*` (this one is decoder-only)")
+        return enc.encode(imgs, in_scale=2.0, in_shift=-1.0).latent_dist.sample(scale=self.vae_scaling_factor)
+
+    def _encoder_from_dir(self, H, W):
+        if self.vae_dir is None:
+            return None
+        lat = (-(-H // 8), -(-W // 8))
+        if self._lazy_encoder is not None:
+            enc = self._lazy_encoder[0]
+            if enc is None or (lat[0] <= enc.cfg.latent_h and lat[1] <= enc.cfg.latent_w):
+                return enc
+            lat = (max(lat[0], enc.cfg.latent_h), max(lat[1], enc.cfg.latent_w))
+            enc.close()
+        from .checkpoint import load_vae_encoder
+        enc = load_vae_encoder(self.vae_dir, "SDXL", self.device_index, lat, precise=True)
+        self._lazy_encoder = (enc,)
+        return enc
+
     def sample(self, prompt=None, prompt_2=None, height=None, width=None, num_inference_steps=50, guidance_scale=5.0,
                negative_prompt=None, negative_prompt_2=None, num_images_per_prompt=1, eta=0.0, generator=None,
                latents=None, prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
                negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True, callback=None, callback_steps=1,
                cross_attention_kwargs=None, guidance_rescale=0.0, original_size=None, crops_coords_top_left=(0, 0),
                target_size=None, use_guidance=False, inject_selfattn=0, inject_background=0, text_format_dict=None,
-               run_rich_text=False, elide_dead_forwards=False):
+               run_rich_text=False, elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None):
+        """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
+        `strength` of the schedule, and (rich pass) pin the pixels of `keep_source` to the image at every step.  image=None: the
+        reference's behaviour, the other three are not read."""
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
@@ -93,18 +130,36 @@ class RegionDiffusionXL:
             raise RuntimeError("use_guidance=True needs a rich_text_to_image_amd.engine.VaeDecoder as `vae` (xl.py:849-867)")
         if not isinstance(self.scheduler, (EulerTables, DPMSolverTables)):
             raise ValueError(f"RegionDiffusionXL: scheduler must be EulerTables or DPMSolverTables, got {type(self.scheduler).__name__}")
-        self.scheduler.set_timesteps(num_inference_steps)
+        img2img.check_start(image, latents)
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
-        if latents is None:
-            latents = torch.randn((1, 4, h, w), generator=generator, device=self.device if generator is None else generator.device)
-        latents = latents.to(self.device).float() * self.scheduler.init_noise_sigma                # xl.py:533-536
+        if image is None:
+            self.scheduler.set_timesteps(num_inference_steps)
+            if latents is None:
+                latents = torch.randn((1, 4, h, w), generator=generator, device=self.device if generator is None else generator.device)
+            latents = latents.to(self.device).float() * self.scheduler.init_noise_sigma            # xl.py:533-536
+            keep = None
+        else:
+            if img2img.latent_shape(image) != (h, w):
+                raise ValueError(f"image {tuple(image.shape)} does not match height x width = {height} x {width}")
+            self.scheduler.set_timesteps(num_inference_steps, strength)
+            if noise is None:                          # drawn where `latents` is drawn: the plain and the rich pass of one seed share their start
+                noise = torch.randn((1, 4, h, w), generator=generator, device=self.device if generator is None else generator.device)
+            noise = noise.to(self.device).float()
+            x0 = img2img.source_latents(self, image)
+            keep = img2img.keep_mask(self, keep_source, h, w) if run_rich_text else None
+            img2img.check_tokenmap_iterations(not run_rich_text and getattr(self, "_tokenmap_hooks", False), len(self.scheduler.timesteps))
         add_time_ids = self._get_add_time_ids(tuple(original_size), tuple(crops_coords_top_left), tuple(target_size))
         embeds = torch.cat([negative_prompt_embeds, prompt_embeds], 0).to(self.device).float()    # xl.py:760
         pooled = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], 0).to(self.device).float()
         eng = self.unet.engine(h, w, streams=embeds.shape[0] + 2 if run_rich_text else 2, prompts=embeds.shape[0])
         eng.set_prompts(embeds, pooled, add_time_ids)
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
-        eng.set_latents(latents)
+        if image is None:
+            eng.set_latents(latents)
+        else:
+            eng.set_source(x0, noise, keep)
+            eng.noise_latents(*self.scheduler.start_level())
+            levels = self.scheduler.source_levels()
         n = len(self.scheduler.timesteps)
         if run_rich_text:
             n_styles = embeds.shape[0] - 1
@@ -139,6 +194,8 @@ class RegionDiffusionXL:
                         else:
                             guide()
                     eng.background_blend()
+                if keep is not None:
+                    eng.source_blend(*levels[i])
                 if callback is not None and i % callback_steps == 0:
                     callback(i, self.scheduler.timesteps[i], eng.read_latents(h, w))
         else:
@@ -154,6 +211,8 @@ class RegionDiffusionXL:
             if hooks:
                 self._store_end(eng, n)
         latents = eng.read_latents(h, w)
+        if image is not None:
+            eng.set_source(None)
         if output_type == "latent":
             return StableDiffusionXLPipelineOutput(images=latents)
         if self.vae is None:

@@ -25,9 +25,12 @@ def _resize_bicubic_aa(mask, height, width):
 
 
 def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=0.5, inject_selfattn=0., segment_threshold=0.3,
-             num_segments=9, inject_background=0., latents=None):
+             num_segments=9, inject_background=0., latents=None, init_image=None, strength=0.8, keep_source=None):
     """Returns (plain_image, rich_image, timings).  `param` has the reference's keys: text_input, height, width,
-    guidance_weight, steps, noise_index, negative_prompt (sample.py:135-143)."""
+    guidance_weight, steps, noise_index, negative_prompt (sample.py:135-143).
+    `init_image` ([1,3,height,width] in [0,1], or [1,4,h,w] latents): both passes start from it instead of noise and run the last
+    `strength` of the schedule; it is encoded once and the same latents, strength and noise go to both passes.  `keep_source`
+    ("background" or a mask, img2img.py) pins those pixels of the rich pass to the image."""
     if run_dir:
         os.makedirs(run_dir, exist_ok=True)
     spans = parse_json(param['text_input'], device=model.device)
@@ -41,6 +44,11 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     timings = {}
 
     seed_everything(seed)
+    start = {}
+    if init_image is not None:
+        from . import img2img
+        x0 = img2img.source_latents(model, init_image)
+        start = dict(image=x0, strength=strength, noise=torch.randn(x0.shape, device=model.device))
     t0 = time.time()
     if model.attention_maps is None:
         model.register_tokenmap_hooks()
@@ -48,11 +56,11 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         model.reset_attention_maps()
     if model_type == 'SD':
         plain_img = model.produce_attn_maps([base_text_prompt], [negative_text], height=height, width=width,
-                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents)
+                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, **start)
     else:
         plain_img = model.sample([base_text_prompt], negative_prompt=[negative_text], height=height, width=width,
                                  num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], run_rich_text=False,
-                                 latents=latents)
+                                 latents=latents, **start)
     timings['plain'] = time.time() - t0
 
     t0 = time.time()
@@ -95,16 +103,18 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
 
     t0 = time.time()
     seed_everything(seed)
+    if start:
+        start['keep_source'] = keep_source
     if model_type == 'SD':
         rich_img = model.prompt_to_img(region_text_prompts, [negative_text], height=height, width=width,
                                        num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                        use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn,
-                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents)
+                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, **start)
     else:
         rich_img = model.sample(region_text_prompts, negative_prompt=[negative_text], height=height, width=width,
                                 num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                 use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn, text_format_dict=text_format_dict,
-                                inject_background=inject_background, run_rich_text=True, latents=latents)
+                                inject_background=inject_background, run_rich_text=True, latents=latents, **start)
     timings['rich'] = time.time() - t0
     return plain_img, rich_img, timings
 
@@ -179,6 +189,14 @@ def build_model(a, rank=0, local_rank=0, world=1):
     return apply_scheduler(model, a), seconds
 
 
+def load_init_image(path, height, width):
+    """--init_image: the file as RGB, resized to height x width -> [1,3,height,width] in [0,1]."""
+    import numpy as np
+    from PIL import Image
+    img = Image.open(path).convert('RGB').resize((width, height), Image.BICUBIC)
+    return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous()
+
+
 def make_scheduler(a):
     """--scheduler / --solver_order -> the scheduler object to put on the pipeline (None: the pipeline's default, PNDM for SD and
     Euler for SDXL).  A flag that cannot be honoured is an error, never ignored."""
@@ -228,6 +246,15 @@ def build_parser():
                    help='default: the reference\'s sampler (PNDM for SD, Euler for SDXL / AnimeXL); dpmsolver++: DPM-Solver++ multistep '
                         '(diffusers DPMSolverMultistepScheduler), usually run at 20-25 --sample_steps. Holds on every rank of --gpus N')
     p.add_argument('--solver_order', type=int, default=None, choices=[1, 2], help='DPM-Solver++ order (default 2); needs --scheduler dpmsolver++')
+    p.add_argument('--init_image', type=str, default=None,
+                   help='edit this image instead of starting from noise: it is resized to height x width, encoded once, and both passes '
+                        'start from it at --strength')
+    p.add_argument('--strength', type=float, default=0.8,
+                   help='with --init_image: the share of the schedule that is executed, in (0, 1]; 1 keeps nothing of the image but its '
+                        'pinned pixels.  The token maps need more than 10 executed steps')
+    p.add_argument('--keep_source', type=str, default='none', choices=['none', 'background'],
+                   help='with --init_image: background = the region of the unformatted text stays the image itself (its latents are reset to '
+                        'the image at every step of the rich pass)')
     p.add_argument('--load_path', type=str, default=None,
                    help='diffusers-layout checkpoint directory; default: the hub ids of sample.py:26-30 resolved locally '
                         '(checkpoint.resolve_checkpoint: $RTDIFF_SD_PATH / $RTDIFF_SDXL_PATH / the Hugging Face hub cache)')
@@ -255,6 +282,10 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     a = p.parse_args(argv)
     make_scheduler(a)                 # an unusable --scheduler / --solver_order combination fails here, before any rank starts
+    if a.init_image is None and a.keep_source != 'none':
+        raise SystemExit("sample: --keep_source needs --init_image")
+    if a.init_image is not None and a.keep_source != 'none' and a.split_image:
+        raise SystemExit("sample: --keep_source is not supported with --split_image")
     from . import launcher
     err = launcher.self_launch(None, argv, a.gpus, require_gpus=not a.dry_launch, module=__spec__.name if __spec__ else "rich_text_to_image_amd.sample")
     if err is not None:
@@ -280,12 +311,14 @@ def main(argv=None):
     model.split_image = bool(a.split_image and world > 1)
     os.makedirs(a.run_dir, exist_ok=True)
     from PIL import Image
+    init_image = load_init_image(a.init_image, a.height or res, a.width or res) if a.init_image else None
     out = []
     for r in mine:
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt']}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
-                                  a.segment_threshold, a.num_segments, a.inject_background)
+                                  a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
+                                  keep_source=None if a.keep_source == 'none' else a.keep_source)
         print('[rank %d] request %d seed %d: time lapses: plain %.3f s, token maps %.3f s, rich %.3f s'
               % (rank, r['index'], r['seed'], t['plain'], t['token_maps'], t['rich']), flush=True)
         # seed%d_plain.jpg / seed%d_rich.jpg in run_dir, as sample.py:62-76,97-112 writes them (imageio there, PIL here); with several

@@ -16,6 +16,27 @@ def alphas_cumprod(num_train=1000, beta_start=0.00085, beta_end=0.012):
     return torch.cumprod(1.0 - betas, dim=0).numpy()
 
 
+# ---- starting from an image (`set_timesteps(n, strength)`) --------------------------------------------------------------------------
+# strength in (0, 1]: the last k = min(int(n * strength), n) solver steps of the n-step schedule are executed, t_start = n - k.  The
+# truncated lists go to rt_set_schedule as they are, so `inject_background` is a fraction of the EXECUTED schedule, while
+# `inject_selfattn` keeps its timestep threshold (t > (1 - inject_selfattn) * 1000) whatever the strength.
+#   start_level()   -> (a, b): the loop starts from a * x0 + b * noise
+#   source_levels() -> one (a, b) per loop iteration: the level the latents are at AFTER it (what a pinned pixel is reset to);
+#                      the last one is (1, 0) for every scheduler: a pinned pixel ends as the source itself.
+def _executed_steps(name, n, strength, least=1):
+    if not (0.0 < strength <= 1.0):
+        raise ValueError(f"{name}.set_timesteps: strength must be in (0, 1], got {strength}")
+    k = min(int(n * strength), n)
+    if k < least:
+        raise ValueError(f"{name}.set_timesteps: strength {strength} of {n} steps leaves {k} solver steps, need at least {least}")
+    return k
+
+
+def _vp_level(ac, t):
+    a = float(ac[int(t)])                         # fp64 arithmetic on the fp32 table entry
+    return a ** 0.5, (1.0 - a) ** 0.5
+
+
 class PNDMTables:
     kind = 1
     init_noise_sigma = 1.0
@@ -24,11 +45,26 @@ class PNDMTables:
         self.num_train = num_train
         self.alphas_cumprod = alphas_cumprod(num_train)
 
-    def set_timesteps(self, n):
+    def set_timesteps(self, n, strength=1.0):
+        """strength < 1: the distinct descending timesteps D of the n-step schedule are cut to D[n - k:] and expanded again as PLMS
+        expects, [d0, d1, d1, d2, ...] = k + 1 iterations, so the warm-up pair restarts at the cut.  (diffusers' img2img pipelines
+        slice the EXPANDED list instead, after which the warm-up leaves every later iteration one timestep behind; this is a deliberate
+        deviation, [memory], parity unpinned.)  `num_inference_steps` stays n: the engine's step ratio is 1000 // n."""
+        k = _executed_steps("PNDMTables", n, strength, least=min(2, n))
         self.num_inference_steps = n
         ts = (np.arange(0, n) * (self.num_train // n)).round() + 1
+        ts = ts[:k]                                # ascending: the k smallest = the last k of the descending list
         self.timesteps = np.concatenate([ts[:-1], ts[-2:-1], ts[-1:]])[::-1].astype(np.int64).copy()
         return self
+
+    def start_level(self):
+        return _vp_level(self.alphas_cumprod, self.timesteps[0])
+
+    def source_levels(self):
+        """Iterations 0 and 1 (the PLMS warm-up pair) both land on d1, iteration j >= 2 on d_j, the last one on the source."""
+        d = [int(self.timesteps[0])] + [int(t) for t in self.timesteps[2:]]            # the distinct list d0, d1, ...
+        lands = [d[1]] + d[1:]
+        return [_vp_level(self.alphas_cumprod, t) for t in lands] + [(1.0, 0.0)]
 
     def table(self):
         return self.alphas_cumprod.tolist()
@@ -44,14 +80,25 @@ class EulerTables:
         self._train_sigmas = ((1 - ac) / ac) ** 0.5
         self.init_noise_sigma = float(self._train_sigmas.max())
 
-    def set_timesteps(self, n):
+    def set_timesteps(self, n, strength=1.0):
+        """strength < 1: timesteps and sigmas lose their first n - k entries (the sigmas still end in 0); init_noise_sigma stays the
+        full schedule's (an image start does not use it: start_level())."""
+        k = _executed_steps("EulerTables", n, strength)
         self.num_inference_steps = n
         ts = (np.arange(0, n) * (self.num_train // n)).round()[::-1].copy().astype(np.float32) + 1
         sig = np.interp(ts, np.arange(0, self.num_train), self._train_sigmas)
         self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
         self.timesteps = ts
         self.init_noise_sigma = float((self.sigmas.max() ** 2 + 1) ** 0.5)
+        if k < n:
+            self.timesteps, self.sigmas = self.timesteps[n - k:], self.sigmas[n - k:]
         return self
+
+    def start_level(self):
+        return 1.0, float(self.sigmas[0])           # diffusers' Euler add_noise: x0 + sigma * noise
+
+    def source_levels(self):
+        return [(1.0, float(s)) for s in self.sigmas[1:-1]] + [(1.0, 0.0)]
 
     def table(self):
         return self.sigmas.tolist()
@@ -74,12 +121,26 @@ class DPMSolverTables:
         self.sigma_t = torch.sqrt(1 - ac)
         self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
 
-    def set_timesteps(self, n):
+    def set_timesteps(self, n, strength=1.0):
+        """strength < 1: the (de-duplicated) list loses its first n - k entries.  The engine counts `lower_order_final` (a first-order
+        last step when fewer than 15 steps run) on the EXECUTED list, where diffusers' img2img counts the full one: a deliberate
+        deviation, [memory], parity unpinned."""
+        k = _executed_steps("DPMSolverTables", n, strength)
         ts = np.linspace(0, self.num_train - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
         _, first = np.unique(ts, return_index=True)
         self.timesteps = ts[np.sort(first)]
+        if k < n:
+            self.timesteps = self.timesteps[n - k:]
+            if len(self.timesteps) == 0:
+                raise ValueError(f"DPMSolverTables.set_timesteps: strength {strength} of {n} steps leaves no solver step")
         self.num_inference_steps = len(self.timesteps)
         return self
+
+    def start_level(self):
+        return _vp_level(self.alphas_cumprod, self.timesteps[0])
+
+    def source_levels(self):
+        return [_vp_level(self.alphas_cumprod, t) for t in self.timesteps[1:]] + [(1.0, 0.0)]
 
     def table(self):
         return self.alphas_cumprod.tolist()
