@@ -311,6 +311,22 @@ int rt_op_gemm_force_config(int cfg);
  *  bit 28 under-filled 3x3 convs on the split-K implicit GEMM instead of the chunk-split patch kernel
  *  bit 29 no two-halves chunk split for the 32x32 maps                  bit 30 the split rule counts streams of < 128 rows as whole tiles */
 int rt_op_gemm_debug(int flags);
+/* Second word of A/B switches (bits 0 - 30 of the first are taken; its bit 31 stays unused).  The engine wrapper reads RTDIFF_DEBUG_FLAGS2
+ * once at load; csrc/common.h (DebugBit2) names the bits.  0 = default.
+ *  bit 0  Upsample2D's convolutions stay on the patch kernel (nine taps on the nearest-2x up-sampled map, the route of rounds 2 - 6)
+ *         instead of running as four 2x2 phase convolutions of the low-resolution map on csrc/gemm16.hip */
+int rt_op_gemm_debug2(int flags);
+/* Upsample2D (models/resnet.py: F.interpolate(scale_factor=2, mode="nearest") followed by the 3x3 convolution) in its sub-pixel form: output
+ * pixel (2y + a, 2x + b) reads the 2x2 input pixels (y + a - 1 + r, x + b - 1 + c) only, with weights that are sums of the 3x3 taps.
+ * rt_op_pack_upconv: w [Cout, Cin, 3, 3] (dtype RT_DTYPE_*) -> out_bf16 [phase 2a + b][Cout][tap 2r + c][Cin], summed in fp32 from the
+ *   source values and rounded once (what rt_bind_weight stores next to the 3x3 pack of every `upsamplers.0.conv.weight`).
+ * rt_op_upconv: rt_op_gemm mode 3 / epi 4 with the phase pack next to the 3x3 pack, as the engine's up-samplers pass it.  x bf16 NHWC [B, Hin, Win, Cin]; w9 bf16 [N, 9 Cin] (K index = tap * Cin + c, as
+ *   rt_op_gemm mode 3); w_phase = rt_op_pack_upconv's output or NULL; out fp16 [B, 2 Hin, 2 Win, N].  *phase_route (may be NULL) = 1 when
+ *   the four-phase launch runs (w_phase given, Cin % 64 == 0, the 16x16x32 family has a tile for ONE image's low-resolution map, switch
+ *   clear), 0: the patch-kernel route of rt_op_gemm mode 3, bit for bit. */
+int rt_op_pack_upconv(const void* w, int dtype, int Cout, int Cin, void* out_bf16, void* stream);
+int rt_op_upconv(const void* x, const void* w9, const void* w_phase, const float* bias, void* out_f16, int B, int Hin, int Win, int Cin, int N,
+                 int* phase_route, void* stream);
 
 /* ---- VAE decoder: colour guidance (rd.py:151-168, xl.py:849-867) and plain decode (rd.py:227-236) ----
  * AutoencoderKL.decoder + post_quant_conv (diffusers 0.18.2, third party: architecture restated in oracle/vae.py).

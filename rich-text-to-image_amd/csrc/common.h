@@ -165,6 +165,10 @@ struct GemmArgs {
     float ln_inv_c, ln_eps;
     bf16_t* ln_copy;
     float* ln_emit;
+    // A_CONV3_UP2 only: the sub-pixel ("phase") pack of the same 3x3 weight, [phase 4][N][tap 4][Cin] bf16 (launch_pack_up2); null: the
+    // layer has none and stays on the patch kernel.  With it the layer may run as four 2x2 convolutions of the low-resolution map
+    // (gemm16.hip, MODE = A_CONV3_UP2; gemm_route: G16_UP2)
+    const bf16_t* W_up2;
 };
 // LayerNorm fold plumbing (host-only predicates are pure functions of the shape, like every routing decision)
 int gemm_ln_emit_bn(const GemmArgs& a);                 // column-tile width (160 / 320) of the partials launch_gemm(a) with a.ln_emit set would leave; 0: this route has no such epilogue
@@ -197,8 +201,8 @@ void launch_gemm(const GemmArgs& a, hipStream_t st);
 // It reads the shape and also A_lo / W_lo / pair_lo / ln_part / ln_emit / prefer_patch_conv / weights_on_rows / split_tiles /
 // rows_per_stream, so this and every query below must be asked with the arguments as they will be launched.
 struct GemmRoute {
-    enum Kind { G16, PATCH, PATCH_SPLIT, KSPLIT, TILE, TRIPLE };
-    Kind kind = TILE;  // G16: gemm16.hip | PATCH: conv3p_kernel | PATCH_SPLIT: conv3p_kernel over input-channel chunks + reduction |
+    enum Kind { G16, PATCH, PATCH_SPLIT, KSPLIT, TILE, TRIPLE, G16_UP2 };
+    Kind kind = TILE;  // G16: gemm16.hip | G16_UP2: gemm16.hip, the 2x-upsample convolution as four 2x2 phase convolutions | PATCH: conv3p_kernel | PATCH_SPLIT: conv3p_kernel over input-channel chunks + reduction |
                        // KSPLIT: K slices of the 128x128 kernel + reduction | TILE: a gemm.hip tile configuration |
                        // TRIPLE: hi / lo contraction as three launches of the single-pass problem
     int variant = -1, wstat = 0;   // G16: tile variant, W-stationary tile order
@@ -241,8 +245,13 @@ enum DebugBit {
     DBG_NO_CHUNK_HALVES = 29,     // no two-halves chunk split for the 32x32 maps
     DBG_SPLIT_NO_SMALL_ROWS = 30, // the split rule counts streams of < 128 rows as whole 128-row tiles
 };
+// rt_op_gemm_debug2's switches: the second word (bits 0 - 30 of the first are taken, bit 31 stays unused)
+enum DebugBit2 {
+    DBG2_NO_UP2_PHASE = 0,        // the 2x-upsample convolutions stay on the patch kernel (nine taps on the up-sampled map) instead of four 2x2 phase convolutions
+};
 static inline int debug_bit(int flags, int bit) { return (flags >> bit) & 1; }
 void gemm_set_debug(int flags);    // decodes the routing bits above
+void gemm_set_debug2(int flags);   // ... and those of the second word
 bool gemm_lnfold_enabled();       // LayerNorm folded into its consumers (debug bit 22 clear, gemm16 on, no forced configuration)
 bool gemm_xblock_enabled();       // the one-launch cross-attention block (xblock.hip) is switched on (debug bit 16 SET - opt-in; gemm16 on, no forced configuration)
 bool gemm_xattn_enabled();         // the fused to_q + cross-attention kernel is allowed (debug bit 4 clear, gemm16 on, no forced configuration)
@@ -251,6 +260,8 @@ bool gemm_xattn_enabled();         // the fused to_q + cross-attention kernel is
 bool gemm16_supported(const GemmArgs& a);
 int gemm16_pick(const GemmArgs& a, int weights_on_rows, int* wstat);      // variant id or -1; pure function of the shape
 void launch_gemm16_variant(const GemmArgs& a, int variant, int wstat, hipStream_t st);
+int gemm16_pick_up2(const GemmArgs& a);         // A_CONV3_UP2 with a phase pack: tile variant (0 / 4) of the four-phase launch, -1: none; pure function of ONE image's shape
+void launch_gemm16_up2(const GemmArgs& a, int variant, hipStream_t st);
 int gemm16_pair_variant(const GemmArgs& a, int va, int wa, const GemmArgs& b, int vb, int wb);     // id of the grouped instantiation of tiles
                                                                                                   // va / vb (gemm16_pick) (0..3), -1: none
 void launch_gemm16_pair(const GemmArgs& a, const GemmArgs& b, int pair, hipStream_t st);          // grouped launch of instantiation `pair` (gemm16.hip)
@@ -372,6 +383,10 @@ struct PackArgs {
     int lo_part;                      // 1: store the low part bf16(v - bf16(v)) instead of bf16(v) (precise VAE mode)
 };
 void launch_pack(const PackArgs& a, hipStream_t st);
+// Phase pack of a 3x3 weight behind a nearest-2x up-sample: src [Cout, Cin, 3, 3] (src_dtype as PackArgs) -> dst [phase 2a+b][Cout][tap 2r+c][Cin]
+// bf16, W_ab[r][c] = sum of w[ky][kx] over ky in S_a(r), kx in S_b(c) with S_0 = {0}, {1, 2} and S_1 = {0, 1}, {2}: summed in fp32 from
+// the SOURCE values in a fixed order, rounded once
+void launch_pack_up2(const void* src, int src_dtype, bf16_t* dst, int Cout, int Cin, hipStream_t st);
 
 // NCHW fp32 latents -> NHWC bf16 [B, HW, 8] (channels 4..7 zero), scaled per batch entry
 struct PrepArgs {

@@ -71,6 +71,38 @@ void launch_pack(const PackArgs& a, hipStream_t st) {
     HIP_CHECK(hipGetLastError());
 }
 
+// Phase pack of the 2x-upsample convolutions (common.h, launch_pack_up2).  After a nearest-2x up-sample the nine taps of output pixel
+// (2y + a, 2x + b) fall on the 2x2 input pixels (y + a - 1 + r, x + b - 1 + c): rows r <- ky {0} | {1, 2} for a = 0, {0, 1} | {2} for
+// a = 1, columns likewise.  One thread per destination element; ky-major, kx-minor fp32 sum of the source values, one rounding.
+__global__ void pack_up2_kernel(const void* __restrict__ src, int src_dtype, bf16_t* __restrict__ dst, int Cout, int Cin) {
+    const size_t total = (size_t)16 * Cout * Cin;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int ci = (int)(i % Cin), tap = (int)((i / Cin) & 3);
+        const size_t pr = i / ((size_t)4 * Cin);                     // phase * Cout + co
+        const int co = (int)(pr % Cout), ph = (int)(pr / Cout);
+        const int a = ph >> 1, b = ph & 1, r = tap >> 1, c = tap & 1;
+        const int ky0 = a == 0 ? (r == 0 ? 0 : 1) : (r == 0 ? 0 : 2), ky1 = a == 0 ? (r == 0 ? 0 : 2) : (r == 0 ? 1 : 2);
+        const int kx0 = b == 0 ? (c == 0 ? 0 : 1) : (c == 0 ? 0 : 2), kx1 = b == 0 ? (c == 0 ? 0 : 2) : (c == 0 ? 1 : 2);
+        const size_t base = ((size_t)co * Cin + ci) * 9;
+        float v = 0.f;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                const size_t off = base + ky * 3 + kx;
+                if (src_dtype == 0) v += ((const float*)src)[off];
+                else if (src_dtype == 1) v += __half2float(((const __half*)src)[off]);
+                else v += bf16_to_f32(((const bf16_t*)src)[off]);
+            }
+        dst[i] = f32_to_bf16(v);
+    }
+}
+void launch_pack_up2(const void* src, int src_dtype, bf16_t* dst, int Cout, int Cin, hipStream_t st) {
+    RT_REQUIRE(src && dst && Cout > 0 && Cin > 0 && src_dtype >= 0 && src_dtype <= 2, "pack_up2: arguments");
+    const size_t total = (size_t)16 * Cout * Cin;
+    int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(pack_up2_kernel, dim3(grid), dim3(256), 0, st, src, src_dtype, dst, Cout, Cin);
+    HIP_CHECK(hipGetLastError());
+}
+
 // ---------------------------------------------------------------- sinusoidal embedding
 // diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos(t f_j) | sin(t f_j)]
 // (reference call sites: models/unet_2d_condition.py:784,849)

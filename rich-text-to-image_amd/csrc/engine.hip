@@ -65,7 +65,8 @@ struct Scope {
 // ------------------------------------------------------------------------------------------------
 // plan
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
-struct MatW { bf16_t* w = nullptr; float* b = nullptr; int N = 0, K = 0; };   // packed [N, K] bf16 (+ f32 bias)
+struct MatW { bf16_t* w = nullptr; float* b = nullptr; int N = 0, K = 0;      // packed [N, K] bf16 (+ f32 bias)
+              bf16_t* w_up2 = nullptr; };                                      // up-sampler convolutions: the phase pack [4][N][4 Cin] (launch_pack_up2)
 
 struct ResnetP {
     std::string name;
@@ -106,6 +107,7 @@ struct WeightSlot {
     std::string name;
     std::vector<int64_t> shape;
     PackArgs pack;     // everything except src/src_dtype
+    bf16_t* up2 = nullptr; int up2_cout = 0, up2_cin = 0;   // second pack of the same source tensor: the phase form of an up-sampler convolution
     bool bound = false;
 };
 
@@ -251,13 +253,19 @@ struct rt_engine {
         return m;
     }
     // nn.Conv2d 3x3 [Cout, Cin, 3, 3] -> [Cout, 9*CinP], K index = tap*CinP + c
-    MatW mk_conv3(const std::string& name, int Cin, int Cout) {
+    // up2 (Upsample2D's convolution, Cin % 64 == 0): the SAME slot also fills the phase pack [4][Cout][4 Cin] next to the 3x3 pack - in
+    // the weight arena (32 Cin Cout bytes), so that the one broadcast of a multi-GPU launch carries it; both are re-derived by every bind
+    MatW mk_conv3(const std::string& name, int Cin, int Cout, bool up2 = false) {
         const int CinP = (Cin + 7) & ~7;
         MatW m; m.N = Cout; m.K = 9 * CinP;
         m.w = (bf16_t*)arena.alloc((size_t)Cout * m.K * 2);
         PackArgs p{}; p.dst = m.w; p.rows = Cout; p.cols = m.K; p.ld_dst = m.K; p.row_map = PACK_ROWS_ID;
         p.c_inner = CinP; p.ci_valid = Cin; p.s_r = (long)Cin * 9; p.s_co = 1; p.s_ci = 9; p.scale = 1.f;
         add_slot(name + ".weight", {Cout, Cin, 3, 3}, p);
+        if (up2 && Cin % 64 == 0) {
+            m.w_up2 = (bf16_t*)arena.alloc((size_t)16 * Cout * Cin * 2);
+            WeightSlot& sl = slots.back(); sl.up2 = m.w_up2; sl.up2_cout = Cout; sl.up2_cin = Cin;
+        }
         m.b = (float*)arena.alloc((size_t)Cout * 4);
         add_slot(name + ".bias", {Cout}, pk_vec(m.b, Cout));
         return m;
@@ -403,7 +411,7 @@ struct rt_engine {
                 u.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), res_in + skip_c, out_c));
                 if (u.has_attn) u.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[L - 1 - i], cfg.transformer_layers[L - 1 - i], L - 1 - i));
             }
-            if (u.has_up) u.up = mk_conv3(pre + ".upsamplers.0.conv", out_c, out_c);
+            if (u.has_up) u.up = mk_conv3(pre + ".upsamplers.0.conv", out_c, out_c, true);
             up.push_back(u);
         }
         norm_out = mk_norm("conv_norm_out", boc[0]);
@@ -491,13 +499,16 @@ struct rt_engine {
         if (mode == A_CONV3_S2) { Hout = (Hin + 1) / 2; Wout = (Win + 1) / 2; }   // k3 s2 p1
         if (mode == A_CONV3_UP2) { Hout = Hin * 2; Wout = Win * 2; }
         GemmArgs g{}; g.A = in; g.W = W.w; g.bias = W.b; g.out = out; g.res = res; g.temb = temb; g.zero = zero;
+        if (mode == A_CONV3_UP2) g.W_up2 = W.w_up2;
         g.mode = mode; g.epi = epi; g.M = B * Hout * Wout; g.N = W.N; g.K = W.K; g.lda = 0; g.ldw = W.K; g.ldo = W.N;
         g.ldres = W.N; g.temb_ld = W.N; g.rows_per_batch = Hout * Wout;
         g.Hin = Hin; g.Win = Win; g.Cin = CinP; g.Hout = Hout; g.Wout = Wout;
         g.split_tiles = cdiv(Hout * Wout, 128) * cdiv(W.N, 128);
         RT_REQUIRE(W.K == 9 * CinP, "conv: weight/input channel mismatch");
         if (!run_gemm(g)) return;
-        prof_begin(RT_PROF_GEMM_CONV, 2.0 * g.M * W.N * W.K);
+        // executed FLOPs: the phase form of an up-sampler convolution multiplies 4 taps per output pixel, not 9
+        const bool phase = profiling && gemm_route(g).kind == GemmRoute::G16_UP2;
+        prof_begin(RT_PROF_GEMM_CONV, 2.0 * g.M * W.N * (phase ? 4 * CinP : W.K));
         launch_gemm(g, stream);
         prof_end();
     }
@@ -1113,6 +1124,7 @@ int rt_bind_weight(rt_engine* e, const char* name, const void* ptr, int dtype, c
         RT_REQUIRE(dtype >= 0 && dtype <= 2, "rt_bind_weight: dtype");
         PackArgs p = s.pack; p.src = ptr; p.src_dtype = dtype;
         launch_pack(p, e->stream);
+        if (s.up2) launch_pack_up2(ptr, dtype, s.up2, s.up2_cout, s.up2_cin, e->stream);
         s.bound = true;
         e->fold_dirty = true;
     })
@@ -1387,6 +1399,7 @@ int rt_op_gemm_debug(int d) {
     groupnorm_set_fused(!on(DBG_GN_TWO_LAUNCH)); groupnorm_set_chunk_div(on(DBG_GN_CHUNK_128) ? 128 : 64);
     return RT_OK;
 }
+int rt_op_gemm_debug2(int d) { gemm_set_debug2(d); return RT_OK; }
 int rt_op_probes_built(void) {
 #ifdef RT_PROBES
     return 1;
@@ -1408,6 +1421,19 @@ int rt_op_gemm(const void* A, const void* W, const float* bias, void* out, const
         g.zero = op_zero_page(); g.mode = mode; g.epi = epi; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
         g.ldres = ldres; g.temb_ld = temb_ld; g.rows_per_batch = rows_per_batch; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
         g.Hout = Hout; g.Wout = Wout;
+        launch_gemm(g, (hipStream_t)stream);
+    })
+}
+int rt_op_pack_upconv(const void* w, int dtype, int Cout, int Cin, void* out_bf16, void* stream) {
+    OP_TRY({ launch_pack_up2(w, dtype, (bf16_t*)out_bf16, Cout, Cin, (hipStream_t)stream); })
+}
+int rt_op_upconv(const void* x, const void* w9, const void* w_phase, const float* bias, void* out_f16, int B, int Hin, int Win, int Cin, int N,
+                 int* phase_route, void* stream) {
+    OP_TRY({
+        GemmArgs g{}; g.A = (const bf16_t*)x; g.W = (const bf16_t*)w9; g.W_up2 = (const bf16_t*)w_phase; g.bias = bias; g.out = out_f16; g.zero = op_zero_page();
+        g.mode = A_CONV3_UP2; g.epi = EPI_F16; g.M = B * 4 * Hin * Win; g.N = N; g.K = 9 * Cin; g.ldw = g.K; g.ldo = N; g.ldres = N; g.temb_ld = N;
+        g.rows_per_batch = 4 * Hin * Win; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Hout = 2 * Hin; g.Wout = 2 * Win;
+        if (phase_route) *phase_route = gemm_route(g).kind == GemmRoute::G16_UP2 ? 1 : 0;
         launch_gemm(g, (hipStream_t)stream);
     })
 }

@@ -1263,6 +1263,7 @@ static struct GemmSwitches {
                                   // kernel (else on the split-K implicit GEMM, rounds 2 - 5)
     bool chunk_halves = true;     // ... and the two-halves rule of the 32x32 maps
     bool lnfold = true;           // round 6: LayerNorm folded into its consumers (gemm16.hip, "LNF")
+    bool up2_phase = true;        // 2x-upsample convolutions with a phase pack as four 2x2 phase convolutions on gemm16.hip (second debug word, bit 0 clears it)
 } g_sw;
 #ifdef RT_PROBE
 int g_conv3p_tn = 0;          // probe override of the patch kernel's column-tile count
@@ -1275,6 +1276,7 @@ void gemm_set_debug(int flags) {
     g_sw.split_small_rows = !on(DBG_SPLIT_NO_SMALL_ROWS); g_sw.conv3p_tn4 = !on(DBG_CONV3P_NO_TN4);
     g_sw.chunk_split = !on(DBG_NO_CHUNK_SPLIT); g_sw.chunk_halves = !on(DBG_NO_CHUNK_HALVES); g_sw.lnfold = !on(DBG_NO_LNFOLD);
 }
+void gemm_set_debug2(int flags) { g_sw.up2_phase = !debug_bit(flags, DBG2_NO_UP2_PHASE); }
 void gemm_force_config(int cfg) { g_sw.force_cfg = cfg; }
 bool gemm_cross77_enabled() { return g_sw.cross77; }
 bool gemm_lnfold_enabled() { return g_sw.lnfold && g_sw.use16 && g_sw.force_cfg < 0; }
@@ -1467,6 +1469,11 @@ GemmRoute gemm_route(const GemmArgs& a) {
         if (!fused) { r.kind = GemmRoute::TRIPLE; return r; }
     }
     if (conv16) { r.kind = GemmRoute::G16; return r; }
+    // Upsample2D's convolution with a phase pack (GemmArgs.W_up2): four 2x2 convolutions of the low-resolution map on the same main loop
+    // (gemm16.hip, MODE = A_CONV3_UP2) where the family has a tile for the phase problem; small maps, the precise VAE (hi / lo) and
+    // layers without a pack keep the patch kernel below
+    if (a.mode == A_CONV3_UP2 && a.W_up2 && !hilo && ksl == 1 && by_shape && s.use16 && s.conv16 && s.conv_patch && s.up2_phase && !a.prefer_patch_conv &&
+        (r.variant = gemm16_pick_up2(a)) >= 0) { r.kind = GemmRoute::G16_UP2; return r; }
     // patch convolutions that cannot fill the chip (K slices) are split over their input-channel chunks on the patch kernel, or go through the
     // split-K implicit GEMM; only the patch kernel's epilogue writes GemmArgs.pair_lo (pair_output_ok)
     const int chunks = by_shape ? conv3p_split_slices(a, ksl) : 0;
@@ -1606,6 +1613,7 @@ static void launch_routed(const GemmArgs& a, const GemmRoute& r, hipStream_t st)
             return;
         }
         case GemmRoute::G16: launch_gemm16_variant(a, r.variant, r.wstat, st); return;
+        case GemmRoute::G16_UP2: launch_gemm16_up2(a, r.variant, st); return;
         case GemmRoute::PATCH:
             if (a.mode == A_CONV3_UP2) { if (a.epi == EPI_F16) launch_conv3p<EPI_F16, true>(a, st); else launch_conv3p<EPI_F32, true>(a, st); }
             else switch (a.epi) {

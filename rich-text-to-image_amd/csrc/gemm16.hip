@@ -407,7 +407,8 @@ static void launch_v(const GemmArgs& a, int wstat, hipStream_t st) {
     }
     const int ntn = cdiv(a.N, BN), ntm = cdiv(a.M, BM);
     if (wstat == 1 && (ntn % 8 != 0)) wstat = 0;
-    hipLaunchKernelGGL((gemm16_kernel<MODE, EPI, TMW, TNW, WM, WN, WK, S, LNF>), dim3(ntm * ntn), dim3(WM * WN * WK * 64), LDS, st, a, wstat);
+    constexpr int NPH = MODE == A_CONV3_UP2 ? 4 : 1;                 // phase convolution: the four phases' tiles as one grid, phase slowest
+    hipLaunchKernelGGL((gemm16_kernel<MODE, EPI, TMW, TNW, WM, WN, WK, S, LNF>), dim3(ntm * ntn * NPH), dim3(WM * WN * WK * 64), LDS, st, a, wstat);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -557,6 +558,34 @@ bool gemm16_supported(const GemmArgs& a) {
     // launcher checks its own element-offset bound) instead of reading zeros beyond the range
     if ((long)a.M * a.lda * 2 >= 0x7fffffffL || (long)a.N * a.ldw * 2 >= 0x7fffffffL) return false;
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------- MODE = A_CONV3_UP2: sub-pixel form of Upsample2D's convolution
+// conv3x3(nearest-2x(x)) reads, for output pixel (2y + a, 2x + b), only the 2x2 input pixels (y + a - 1 + r, x + b - 1 + c): the nine taps
+// collapse onto four whose weights are sums of the 3x3 taps (launch_pack_up2: summed in fp32 from the source tensor, rounded once).  The
+// layer is therefore four implicit GEMMs [M / 4 low-resolution pixels] x [N] x [4 Cin] - 16 tap products per input pixel instead of 36 -
+// on the A_CONV3 loader with four taps and a phase-dependent shift, each phase's rows scattered to its output parity by the epilogue.
+// One launch: the phase is the slowest tile index.  Tile class: the A_CONV3 rule on ONE image's low-resolution map (never the batch).
+static bool up2_geometry(const GemmArgs& a) {
+    return a.mode == A_CONV3_UP2 && a.W_up2 && a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win && a.Cin % BK16 == 0 && a.K == 9 * a.Cin &&
+           a.rows_per_batch == a.Hout * a.Wout && a.M % a.rows_per_batch == 0 && (long)(a.M / 4) * a.Cin * 2 < (long)RT_G16_OOB &&
+           (long)a.N * 4 * a.Cin * 2 < 0x7fffffffL && a.epi == EPI_F16 && !a.res && !a.A_lo && !a.W_lo && !a.pair_lo && !a.ln_part && !a.ln_emit &&
+           a.N % 8 == 0 && a.ldo % 8 == 0 && ((uintptr_t)a.W_up2 & 15) == 0;
+}
+int gemm16_pick_up2(const GemmArgs& a) {
+    if (!up2_geometry(a)) return -1;
+    const int rps = a.Hin * a.Win;                                   // rows ONE image contributes to a phase
+    if (rps < 256) return -1;
+    if (a.N % 320 == 0 && (long)cdiv(rps, 224) * (a.N / 320) >= 32) return 4;
+    if (a.N % 160 == 0) return (long)cdiv(rps, 224) * (a.N / 160) >= 30 ? 0 : -1;      // (4 Cin / 64 K tiles: always even)
+    return -1;
+}
+void launch_gemm16_up2(const GemmArgs& a, int v, hipStream_t st) {
+    RT_REQUIRE(up2_geometry(a) && (v == 0 || v == 4), "gemm16: phase form of the 2x-upsample convolution (phase pack, fp16 output, no residual, Cin % 64 == 0; 224 x 160 / 224 x 320 tiles)");
+    GemmArgs g = a;                                                  // the phase problem: the low-resolution map against [N][4 Cin]
+    g.M = a.M / 4; g.rows_per_batch = a.Hin * a.Win; g.K = 4 * a.Cin; g.W = a.W_up2; g.ldw = 4 * a.Cin;
+    if (v == 0) launch_v<A_CONV3_UP2, EPI_F16, 7, 5, 2, 2, 2, 3>(g, 0, st);
+    else launch_v<A_CONV3_UP2, EPI_F16, 7, 5, 2, 4, 1, 2>(g, 0, st);
 }
 
 void launch_gemm16_variant(const GemmArgs& a, int v, int wstat, hipStream_t st) {

@@ -4,6 +4,12 @@
 // fp16-trunk epilogues of the 224 x 160 K-split kernels spilled their residual window (196 B of scratch per lane), the kernel form does not.
 // In scope: template parameters MODE, EPI, TMW, TNW, WM, WN, WK, S, LNF; `p` (GemmArgs), `wstat`, `bid_in` (the workgroup's linear id inside
 // its problem's grid).  LNF: LayerNorm fold (gemm16.hip, "LNF"): 0 none, 1 / 3 consumer (token rows / token columns), 2 producer of the partials.
+    // MODE = A_CONV3_UP2: the four 2x2 phase convolutions of a nearest-2x up-sample + 3x3 convolution as ONE grid (phase = slowest tile index);
+    // p.M / p.rows_per_batch / p.Hin / p.Win describe the LOW-resolution map, p.K = 4 Cin, p.W = the phase pack [4][N][4 Cin]
+    constexpr bool UP2 = MODE == A_CONV3_UP2;
+    constexpr bool CONV = MODE == A_CONV3 || UP2;
+    constexpr int NTAP = UP2 ? 4 : 9;
+    static_assert(!UP2 || (LNF == 0 && (EPI == EPI_F16 || EPI == EPI_F32)), "phase convolution: plain fp16 / fp32 epilogues");
     constexpr int NW = WM * WN * WK;                       // 8 waves (two per SIMD) or 4 waves (one per SIMD, 512 registers each)
     static_assert(NW == 8 || NW == 4, "4 or 8 waves");
     static_assert(WK == 1 || (WK == 2 && (S == 3 || S == 5)), "K split over at most two waves (3-slot ring; 5 slots for the 64-row tiles)");
@@ -33,11 +39,14 @@
     // 4 MiB L2 for the whole launch and W is fetched from HBM exactly once (the grouped order re-fetched the 26 MB GEGLU weight 7 x).
     const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM, nwg = ntm * ntn;
     int tm, tn;
+    const int up_ph = UP2 ? (int)(bid_in / (unsigned)nwg) : 0;      // phase 2a + b: output pixels (2y + a, 2x + b)
+    const unsigned bid_l = UP2 ? bid_in - (unsigned)(up_ph * nwg) : bid_in;
+    const int up_a = up_ph >> 1, up_b = up_ph & 1;
     if (wstat == 1) {
-        const int cpx = ntn >> 3, xcd = bid_in & 7, idx = bid_in >> 3;           // host guarantees ntn % 8 == 0
+        const int cpx = ntn >> 3, xcd = bid_l & 7, idx = bid_l >> 3;             // host guarantees ntn % 8 == 0
         tn = xcd * cpx + idx % cpx; tm = idx / cpx;
     } else {
-        int bid = bid_in;
+        int bid = bid_l;
         const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
         const int GRP = wstat == 2 ? 8 : 4;                         // (wstat 2, round 6 A/B: groups of 8 tile rows - the group's W panels are re-fetched half as often)
@@ -81,7 +90,7 @@
     int voff[PW];                       // byte offset of this lane's 16-B chunk at k0 = 0 (conv: of its pixel's channel vector)
     int ldst[PW];                       // LDS byte offset of the group inside a ring slot (wave-uniform)
     bool pisA[PW];                      // wave-uniform
-    int tapmask[MODE == A_CONV3 ? PW : 1];   // conv, A pieces: bit t set <=> tap t of this lane's pixel lies inside the image
+    int tapmask[CONV ? PW : 1];              // conv, A pieces: bit t set <=> tap t of this lane's pixel lies inside the image
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
         int g = i * NW + wave; if (g > GT - 1) g = GT - 1;          // tail duplicates copy the same bytes to the same place
@@ -91,20 +100,21 @@
         const int lim = isA ? p.M : p.N;
         if (row >= lim) row = lim - 1;
         const int key = ((gl << 2) | (lrow >> 1)) & 7;              // (tile row >> 1) & 7
-        if (MODE == A_CONV3 && isA) {
+        if (CONV && isA) {
             const int b = row / p.rows_per_batch, pix = row - b * p.rows_per_batch;
             const int y = pix / p.Win, x = pix - y * p.Win;
             voff[i] = (row * p.Cin + ((pslot ^ key) << 3)) * 2;     // NHWC, stride 1: output pixel index == input pixel index
             int m = 0;
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+            for (int t = 0; t < NTAP; ++t) {
+                // phase (a, b), tap (r, c) = (t >> 1, t & 1): low-resolution pixel (y + a - 1 + r, x + b - 1 + c)
+                const int yy = UP2 ? y + up_a - 1 + (t >> 1) : y + t / 3 - 1, xx = UP2 ? x + up_b - 1 + (t & 1) : x + t % 3 - 1;
                 if (yy >= 0 && yy < p.Hin && xx >= 0 && xx < p.Win) m |= 1 << t;
             }
-            tapmask[MODE == A_CONV3 ? i : 0] = m;
+            tapmask[CONV ? i : 0] = m;
         } else {
             voff[i] = (row * (isA ? p.lda : p.ldw) + ((pslot ^ key) << 3)) * 2;
-            if (MODE == A_CONV3) tapmask[MODE == A_CONV3 ? i : 0] = 0;
+            if (CONV) tapmask[CONV ? i : 0] = 0;
         }
         pisA[i] = isA;
         ldst[i] = (isA ? 0 : BM * 128) + gl * 1024;
@@ -113,27 +123,29 @@
     // ... and, round 4, the dense fp32-output kernels (the VAE's 512-wide projections, 1x1 shortcuts and attention products - the UNet's
     // dense launches are bf16 / fp16 / GEGLU epilogues and do not carry this code): the pass is a scalar advanced with the issued tiles
     constexpr bool TRIPLE_DENSE = MODE == A_DENSE && EPI == EPI_F32;
-    const bool triple = (MODE == A_CONV3 || TRIPLE_DENSE) && p.A_lo != nullptr;
+    const bool triple = (MODE == A_CONV3 || TRIPLE_DENSE) && p.A_lo != nullptr;      // (no hi / lo form of the phase convolution)
     const int nkp = p.K / BK16;                                      // K tiles of ONE pass
     const int nk = nkp * (triple ? 3 : 1);                           // host guarantees K % 128 == 0 / conv: 9 * Cin / 64, nk >= S + 1
     int d_kt = 0, d_pass = 0;                                        // dense triple: K tile inside the pass / pass of the NEXT tile to be issued
     // conv: (tap, chunk) of the NEXT K tile to be issued, carried as scalars (tiles are issued strictly in order)
-    const int nch = MODE == A_CONV3 ? p.Cin / BK16 : 1;
-    const unsigned a_range = MODE == A_CONV3 ? (unsigned)p.M * (unsigned)p.Cin * 2u : 0x7fffffffu;
+    const int nch = CONV ? p.Cin / BK16 : 1;
+    const unsigned a_range = CONV ? (unsigned)p.M * (unsigned)p.Cin * 2u : 0x7fffffffu;
     int is_tap = 0, is_chunk = 0, is_ky = 0, is_kx = 0, is_pass = 0;
-    int is_pix = -p.Win - 1;                                         // pixel shift of the tap, advanced incrementally (a (ky, kx) product in the
+    const int pix0 = UP2 ? (up_a - 1) * p.Win + up_b - 1 : -p.Win - 1;             // pixel shift of tap 0
+    const bf16_t* const wbase = UP2 ? p.W + (size_t)up_ph * p.N * p.ldw : p.W;     // the phase's [N][4 Cin] block of the pack
+    int is_pix = pix0;                                               // pixel shift of the tap, advanced incrementally (a (ky, kx) product in the
                                                                      // loop made hipcc build a 9-entry table in scratch memory)
     auto stage_piece = [&](int t, int slot_off, int i) {             // piece i of K tile t -> ring slot at slot_off
-        if (MODE == A_CONV3 && pisA[i]) {
+        if (CONV && pisA[i]) {
             const int shift = is_pix * p.Cin * 2;                                       // scalar: (ky - 1) * Win + (kx - 1) pixels
-            const int vo = ((tapmask[MODE == A_CONV3 ? i : 0] >> is_tap) & 1) ? voff[i] + shift : RT_G16_OOB;
+            const int vo = ((tapmask[CONV ? i : 0] >> is_tap) & 1) ? voff[i] + shift : RT_G16_OOB;
             glds16_buf(is_pass == 1 ? p.A_lo : p.A, vo, is_chunk * (BK16 * 2), smem + slot_off + ldst[i], a_range);
         } else {
             // conv weights are packed [Cout][tap][Cin]: the K offset of tile (tap, chunk) is tap * Cin + chunk * 64 (= t * 64 in the
             // tap-major order)
-            const int wk = MODE == A_CONV3 ? (is_tap * p.Cin + is_chunk * BK16) * 2 : (TRIPLE_DENSE ? d_kt : t) * (BK16 * 2);
+            const int wk = CONV ? (is_tap * p.Cin + is_chunk * BK16) * 2 : (TRIPLE_DENSE ? d_kt : t) * (BK16 * 2);
             const void* base = pisA[i] ? (const void*)(TRIPLE_DENSE && d_pass == 1 ? p.A_lo : p.A)
-                                       : (const void*)(((MODE == A_CONV3 && is_pass == 2) || (TRIPLE_DENSE && d_pass == 2)) ? p.W_lo : p.W);
+                                       : (const void*)(((MODE == A_CONV3 && is_pass == 2) || (TRIPLE_DENSE && d_pass == 2)) ? p.W_lo : wbase);
             // (round 6, measured and dropped: the activation pieces of the W-stationary GEGLU as non-temporal loads, so that the A stream
             //  would not evict the XCD's 3.3 MB of W between rounds - the step got 1.8 ms SLOWER: the five column workgroups of a row panel
             //  then fetch A from the fabric one by one instead of sharing it through L2; profiles/r6_ab_geglu_nt_activation_stream.txt)
@@ -148,6 +160,11 @@
     // timing: `make tapmajor` + RTDIFF_LIB_PATH).
     auto tile_issued = [&]() {                                       // every piece of a K tile went out: advance (tap, chunk)
         if (TRIPLE_DENSE) { if (++d_kt == nkp) { d_kt = 0; ++d_pass; } }
+        if (UP2) {                                                   // (chunk, tap) like the 3x3 form: taps (0,0) (0,1) (1,0) (1,1)
+            if (++is_tap == 4) { is_tap = 0; is_pix = pix0; if (++is_chunk == nch) { is_chunk = 0; ++is_pass; } }
+            else if (is_tap == 2) is_pix += p.Win - 1;
+            else ++is_pix;
+        }
         if (MODE == A_CONV3) {
 #ifdef RT_G16_CONV_TAP_MAJOR
             if (++is_chunk == nch) { is_chunk = 0; ++is_tap; if (++is_kx == 3) { is_kx = 0; ++is_ky; is_pix += p.Win - 2; } else ++is_pix;
@@ -368,7 +385,8 @@
     // 29.4 vs 31.6 us per 7168 x 1280 x 1280 launch); class A has no exchange to hide behind and measured better with the request
     // after the post-loop barrier (ff.net.2 28672 x 640 x 2560: 74.1 -> 69.7 us, to_out 640: 30.2 -> 28.6 us)
     constexpr bool RES_EARLY = WK == 2;
-    if constexpr (F16 && RES_EARLY) {
+    constexpr bool RES16 = F16 && !UP2;                              // (the phase convolution has no residual: no window registers)
+    if constexpr (RES16 && RES_EARLY) {
         if (p.res) {
 #pragma unroll
             for (int s_own = 0; s_own < RW; ++s_own) load_res(s_own, s_own);
@@ -451,13 +469,21 @@
             }
         }
     }
-    if constexpr (F16 && !RES_EARLY) {
+    if constexpr (RES16 && !RES_EARLY) {
         if (p.res) {
 #pragma unroll
             for (int s_own = 0; s_own < RW; ++s_own) load_res(s_own, s_own);
         }
     }
 
+    // phase convolution: row = low-resolution pixel (n, y, x) -> output row n 4 HW + (2y + a) 2W + 2x + b
+    auto out_row = [&](int row) -> size_t {
+        if constexpr (UP2) {
+            const int n = row / p.rows_per_batch, pix = row - n * p.rows_per_batch;
+            const int y = pix / p.Win, x = pix - y * p.Win;
+            return (size_t)n * 4 * p.rows_per_batch + (size_t)(2 * y + up_a) * (2 * p.Win) + 2 * x + up_b;
+        } else return (size_t)row;
+    };
     // ---- epilogue: lane (l15, q4) holds row l15 and columns 4*q4 .. +3 of every 16x16 tile.  Each wave transposes one 16-row tile
     // at a time through its private slab and moves row-contiguous 16-B chunks to / from HBM (guide T21).
     constexpr int RS = TNO * 16 * ES + 16;                           // slab row stride (16-B pad: conflict-free 16-B column writes)
@@ -561,7 +587,7 @@
                 if (r >= 16 || row >= p.M || col >= NO) continue;
                 const float4 a0 = *(const float4*)(slab + r * RS + c8 * 32), a1 = *(const float4*)(slab + r * RS + c8 * 32 + 16);
                 float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                if (p.res) {
+                if (RES16 && p.res) {
                     const f16_t* rh = (const f16_t*)&rres[F16 ? ((i < H0 ? i : i - H0) % RW) : 0][it];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += (float)rh[e];
@@ -569,7 +595,7 @@
                 uint4 o; f16_t* oh = (f16_t*)&o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) oh[e] = (f16_t)v[e];
-                *(uint4*)((f16_t*)p.out + (size_t)row * p.ldo + col) = o;
+                *(uint4*)((f16_t*)p.out + out_row(row) * p.ldo + col) = o;
                 if constexpr (LNF == RT_LNF_EMIT) {
                     // xb = bf16 of the same eight fp32 values -> the consumers' MFMA operand; sum / sum of squares of xb (one v_dot2c_f32_bf16
                     // per pair and moment) -> the wave's scratch [16 rows][10 items] behind the slabs.  Inline asm for the LDS traffic:
@@ -611,7 +637,7 @@
             }
             // the window slot of this tile is free: request the residual of the owned tile RW positions further on
             const int s_own = i < H0 ? i : i - H0;                   // compile-time after unrolling
-            if (s_own + RW < NOWN && p.res) load_res(s_own + RW, s_own % RW);
+            if (RES16 && s_own + RW < NOWN && p.res) load_res(s_own + RW, s_own % RW);
         } else {
             constexpr int CPR = TNO * 16 * ES / 16;                  // 16-B chunks per row
 #pragma unroll
@@ -624,9 +650,9 @@
                 if constexpr (F32) {
                     float4 o = make_float4(__uint_as_float(qv.x), __uint_as_float(qv.y), __uint_as_float(qv.z), __uint_as_float(qv.w));
                     if (p.res) { const float4 rv = *(const float4*)((const float*)p.res + (size_t)row * p.ldres + col); o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w; }
-                    *(float4*)((float*)p.out + (size_t)row * p.ldo + col) = o;
+                    *(float4*)((float*)p.out + out_row(row) * p.ldo + col) = o;
                 } else {
-                    *(uint4*)((bf16_t*)p.out + (size_t)row * p.ldo + col) = qv;
+                    *(uint4*)((bf16_t*)p.out + out_row(row) * p.ldo + col) = qv;
                 }
             }
         }

@@ -75,6 +75,7 @@ _SYMBOLS = [
     "rt_op_ln_gemm", "rt_op_gemm_emit_partials", "rt_op_ln_partials", "rt_op_probes_built", "rt_op_attention_units_plan",
     "rt_plain_step_part", "rt_plain_step_finish", "rt_vae_encoder_create", "rt_vae_encode", "rt_vae_posterior_sample",
     "rt_set_source", "rt_noise_latents", "rt_source_blend",
+    "rt_op_gemm_debug2", "rt_op_pack_upconv", "rt_op_upconv",
 ]
 
 
@@ -103,6 +104,9 @@ def load_library(path=None):
     flags = int(os.environ.get("RTDIFF_DEBUG_FLAGS", "0"))      # A/B switches of rt_op_gemm_debug (benchmarks only)
     if flags:
         lib.rt_op_gemm_debug(flags)
+    flags2 = int(os.environ.get("RTDIFF_DEBUG_FLAGS2", "0"))    # ... and of rt_op_gemm_debug2
+    if flags2 and hasattr(lib, "rt_op_gemm_debug2"):
+        lib.rt_op_gemm_debug2(flags2)
     if path is None:
         _lib = lib
     return lib
