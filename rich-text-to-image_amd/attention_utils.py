@@ -55,6 +55,13 @@ def _segment(selfattn_maps, crossattn_maps, seed, num_segments, resolution):
     """attention_utils.py:243-283: the part of get_token_maps that depends only on the recorded maps, the seed and the segment count -
     the 32x32 affinity, its spectral clustering and the averaged cross-attention maps."""
     from sklearn.cluster import SpectralClustering
+    # the maps are read as (sqrt(tokens), sqrt(tokens)) grids below, as in the reference: an image with height != width records maps that
+    # are not, and would fail in a reshape or come out empty further down
+    for name, attn_map in list(selfattn_maps.items()) + list(crossattn_maps.items()):
+        tokens = int(attn_map.shape[1])
+        if int(np.sqrt(tokens)) ** 2 != tokens:
+            raise ValueError(f"get_token_maps: the attention map '{name}' has {tokens} tokens, which is not a square grid - token maps "
+                             "need an image with height == width (the reference reads every map as sqrt(tokens) x sqrt(tokens))")
     maps32 = []
     for attn_map in selfattn_maps.values():
         res_map = int(np.sqrt(attn_map.shape[1]))
@@ -98,6 +105,11 @@ def get_token_maps(selfattn_maps, crossattn_maps, n_maps, save_dir, width, heigh
     same seeded clustering of the same affinity - 60 maps of 1024 x 1024 averaged on the host plus SpectralClustering(n_init=100),
     0.9 s of a 10 s SDXL image.  With a cache the second call reuses `clusters` and the averaged cross-attention maps of the first:
     same seed, same inputs, same labels (tests/test_token_maps.py)."""
+    if width != height:
+        # every recorded map is read as a sqrt(tokens) x sqrt(tokens) grid below, as in the reference: square images only (a 1:4 image
+        # records maps whose token counts ARE perfect squares, so the per-map check of _segment alone would let it through)
+        raise ValueError(f"get_token_maps: token maps need an image with height == width, got height {height} and width {width} "
+                         "(the attention maps are read as square grids)")
     resolution = 32
     key = (seed, num_segments, resolution)
     if cache is not None and cache.get("key") == key:

@@ -58,8 +58,8 @@ class _NoEngine:
         return lambda *a, **k: None
 
 
-def _build(cfg, hw, seed, max_streams, max_prompts):
-    """Engine + oracle on the same random weights: oracle.unet.random_state_dict(cfg, seed), drawn by torch's CPU generator - the same
+def _build(cfg, h, w, seed, max_streams, max_prompts):
+    """Engine (latent h x w) + oracle on the same random weights: oracle.unet.random_state_dict(cfg, seed), drawn by torch's CPU generator - the same
     tensors in the build container (where the oracle outputs under tests/golden/fullsize_oracle are generated) and on the GPU box."""
     sd = random_state_dict(cfg, seed=seed)
     o = OracleUNet(cfg, sd)
@@ -67,7 +67,7 @@ def _build(cfg, hw, seed, max_streams, max_prompts):
     if GENERATE:
         return _NoEngine(), o
     from rich_text_to_image_amd.engine import Engine
-    eng = Engine(cfg, hw, hw, device=0, max_streams=max_streams, max_prompts=max_prompts)
+    eng = Engine(cfg, h, w, device=0, max_streams=max_streams, max_prompts=max_prompts)
     eng.load_state_dict(sd)
     assert eng.weights_missing()[0] == 0
     return eng, o
@@ -75,25 +75,27 @@ def _build(cfg, hw, seed, max_streams, max_prompts):
 
 @pytest.fixture(scope="module")
 def sdxl():
-    eng, o = _build(SDXL_CONFIG, 128, 21, max_streams=8, max_prompts=8)
+    eng, o = _build(SDXL_CONFIG, 128, 128, 21, max_streams=8, max_prompts=8)
     yield eng, o
     eng.close()
 
 
 @pytest.fixture(scope="module")
 def sd15():
-    eng, o = _build(SD15_CONFIG, 64, 22, max_streams=8, max_prompts=8)
+    eng, o = _build(SD15_CONFIG, 64, 64, 22, max_streams=8, max_prompts=8)
     yield eng, o
     eng.close()
 
 
-def _stream_mode_forward(eng, o, cfg, hw, xl, t):
+def _stream_mode_forward(eng, o, cfg, h, w, xl, t, key=None):
+    """`key` names the committed oracle outputs of a non-square case; the square cases keep their historical keys.  time_ids are the
+    reference's original_size + crops_coords_top_left + target_size, each (height, width) (region_diffusion_sdxl.py:_get_add_time_ids)."""
     g = torch.Generator().manual_seed(123)
     P, D = 3, cfg["cross_attention_dim"]
     emb = torch.randn(P, 77, D, generator=g)
     pooled = torch.randn(P, 1280, generator=g) if xl else None
-    tid = torch.tensor([[hw * 8.0, hw * 8.0, 0, 0, hw * 8.0, hw * 8.0]]) if xl else None
-    lat, lat_ref = torch.randn(1, 4, hw, hw, generator=g), torch.randn(1, 4, hw, hw, generator=g)
+    tid = torch.tensor([list((h * 8.0, w * 8.0) + (0.0, 0.0) + (h * 8.0, w * 8.0))]) if xl else None
+    lat, lat_ref = torch.randn(1, 4, h, w, generator=g), torch.randn(1, 4, h, w, generator=g)
     wp, fs = torch.tensor([3, 5, 9]), torch.tensor([4.0, -2.0, 0.5])
 
     def added(k):
@@ -108,7 +110,7 @@ def _stream_mode_forward(eng, o, cfg, hw, xl, t):
             assert INJECT_RESNET in inj and sum(k.endswith("attn1") for k in inj) == (70 if xl else 16)
             r3 = o.forward(lat, t, emb[1:2], added(1), ctl={"inject": inj})
         return r0, r1, r2, r3
-    (r0, r1, r2, r3), hit = cached(f"stream_modes_{'sdxl' if xl else 'sd15'}", o.fingerprint, [lat, lat_ref, emb, pooled, tid, wp, fs, float(t)], oracle_forwards)
+    (r0, r1, r2, r3), hit = cached(key or f"stream_modes_{'sdxl' if xl else 'sd15'}", o.fingerprint, [lat, lat_ref, emb, pooled, tid, wp, fs, float(t)], oracle_forwards)
     print("oracle outputs:", "tests/golden/fullsize_oracle" if hit else "computed live")
     if xl:
         eng.set_prompts(emb.to(DEV), pooled.to(DEV), tid)
@@ -121,7 +123,7 @@ def _stream_mode_forward(eng, o, cfg, hw, xl, t):
     for name, got, ref in (("uncond", out[0], r0[0]), ("base+fontsize", out[1], r1[0]), ("text_ref", out[2], r2[0]),
                            ("region injected", out[3], r3[0])):
         res[name] = rel_l2(got, ref)
-        print(f"{'SDXL' if xl else 'SD-v1.5'} full arch, stream {name}: rel-L2 {res[name]:.3e} (ref rms {ref.pow(2).mean().sqrt():.3f})")
+        print(f"{'SDXL' if xl else 'SD-v1.5'} full arch @{h}x{w}, stream {name}: rel-L2 {res[name]:.3e} (ref rms {ref.pow(2).mean().sqrt():.3f})")
     plain = eng.unet_forward(x, t, [0, 2, 2, 1])          # the mode words must matter at this size too
     assert rel_l2(plain[1], out[1]) > 1e-3 and rel_l2(plain[3], out[3]) > 1e-3
     return res
@@ -129,21 +131,21 @@ def _stream_mode_forward(eng, o, cfg, hw, xl, t):
 
 def test_sdxl_full_architecture_stream_modes_match_oracle(sdxl):
     eng, o = sdxl
-    res = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, True, 801.0)
+    res = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, 128, True, 801.0)
     for name, r in res.items():
         assert r < 1.5e-2, (name, r)
 
 
 def test_sd15_full_architecture_stream_modes_match_oracle(sd15):
     eng, o = sd15
-    res = _stream_mode_forward(eng, o, SD15_CONFIG, 64, False, 701.0)
+    res = _stream_mode_forward(eng, o, SD15_CONFIG, 64, 64, False, 701.0)
     for name, r in res.items():
         assert r < 1.5e-2, (name, r)
 
 
-def _masks(R, hw, g):
-    m = torch.softmax(torch.randn(R, 1, hw // 4, hw // 4, generator=g) * 4, dim=0)
-    m = torch.nn.functional.interpolate(m, size=(hw, hw), mode="bilinear", align_corners=False)
+def _masks(R, h, w, g):
+    m = torch.softmax(torch.randn(R, 1, h // 4, w // 4, generator=g) * 4, dim=0)
+    m = torch.nn.functional.interpolate(m, size=(h, w), mode="bilinear", align_corners=False)
     return (m / (m.sum(0, keepdim=True) + 1e-8)).repeat(1, 4, 1, 1)
 
 
@@ -159,7 +161,7 @@ def test_sdxl_config3_rich_step_matches_oracle(sdxl):
     emb = torch.randn(R + 1, 77, 2048, generator=g)
     pooled = torch.randn(R + 1, 1280, generator=g)
     tid = torch.tensor([[1024.0, 1024.0, 0, 0, 1024.0, 1024.0]])
-    m = _masks(R, hw, g)
+    m = _masks(R, hw, hw, g)
     masks = [m[r:r + 1] for r in range(R)]
     sched = OracleEuler(); sched.set_timesteps(steps)
     assert [float(t) > 500 for t in sched.timesteps] == [True, False]
@@ -204,7 +206,7 @@ def test_sdxl_full_architecture_two_step_loop_with_background_blend(sdxl):
     emb = torch.randn(R + 1, 77, 2048, generator=g)
     pooled = torch.randn(R + 1, 1280, generator=g)
     tid = torch.tensor([[8.0 * hw, 8.0 * hw, 0, 0, 8.0 * hw, 8.0 * hw]])
-    m = _masks(R, hw, g)
+    m = _masks(R, hw, hw, g)
     masks = [m[r:r + 1] for r in range(R)]
     sched = OracleEuler(); sched.set_timesteps(steps)
     lat0 = torch.randn(1, 4, hw, hw, generator=g) * sched.init_noise_sigma
@@ -233,7 +235,7 @@ def test_sd15_config1_rich_loop_matches_oracle(sd15):
     hw, R, steps, gs = 64, 2, 2, 7.5
     g = torch.Generator().manual_seed(8)
     emb = torch.randn(R + 1, 77, 768, generator=g)
-    m = _masks(R, hw, g)
+    m = _masks(R, hw, hw, g)
     masks = [m[r:r + 1] for r in range(R)]
     sched = OraclePNDM(); sched.set_timesteps(steps)
     lat0 = torch.randn(1, 4, hw, hw, generator=g)
@@ -361,7 +363,7 @@ def test_sdxl_config5_guided_loop_through_the_facade(sdxl):
     emb = torch.randn(R + 1, 77, 2048, generator=g)
     pooled = torch.randn(R + 1, 1280, generator=g)
     tid = torch.tensor([[512.0, 512.0, 0, 0, 512.0, 512.0]])
-    m = _masks(R, hw, g)
+    m = _masks(R, hw, hw, g)
     masks = [m[r:r + 1] for r in range(R)]
     lat = torch.randn(1, 4, hw, hw, generator=g)
     tfd = dict(_guidance_inputs(hw, g, 1), word_pos=torch.tensor([4]), font_size=torch.tensor([8.0]))
@@ -406,7 +408,7 @@ def test_sd15_config2_guided_loop_through_the_facade(sd15):
     hw, R, steps, gs = 64, 2, 2, 7.5
     g = torch.Generator().manual_seed(31)
     emb = torch.randn(R + 1, 77, 768, generator=g)
-    m = _masks(R, hw, g)
+    m = _masks(R, hw, hw, g)
     masks = [m[r:r + 1] for r in range(R)]
     lat = torch.randn(1, 4, hw, hw, generator=g)
     tfd = dict(_guidance_inputs(hw, g, 1), word_pos=torch.tensor([2]), font_size=torch.tensor([3.0]))

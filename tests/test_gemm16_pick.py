@@ -92,3 +92,41 @@ def test_small_batches_take_64_row_tiles_of_the_same_class(pick):
                  (0, EPI_BF16, 4, 4096, 1280, 640)]:
         assert pick(*args)[0] in (0, 2, 4), args
     assert pick(0, EPI_BF16, 7, 1024, 1280, 1280, vt=1)[0] == 6
+
+
+def test_rows_per_stream_of_grids_with_height_unlike_width(pick):
+    """SDXL at 768x1344 (latent 96x168: 4032 / 1008 rows per stream at the attention levels) and 1024x768 (128x96: 3072 / 768), SD-v1.5 at
+    512x768 (64x96: 1536 / 384 / 96).  The class must not depend on the batch here either, and the answers are pinned as they stand, so
+    that a change of the shape rule shows up as a diff.  (224-row tiles do not divide 1008: 7 x 1008 rows are 31.5 tiles, tiles straddle
+    streams - covered on the GPU by tests/test_lnfold_gpu.py and tests/test_kernels_gpu.py at these shapes.)"""
+    cls = {-1: "none", 0: "B", 1: "B", 9: "B", 2: "A", 3: "A", 4: "A", 5: "A", 8: "A", 10: "A", 11: "A", 6: "BT", 7: "BT", 12: "BT"}
+    shapes = [(EPI_F16, 1008, 1280, 1280), (EPI_F16, 1008, 1280, 5120), (EPI_F16, 4032, 640, 640), (EPI_F16, 4032, 640, 2560), (EPI_F16, 768, 1280, 1280),
+              (EPI_F16, 3072, 640, 640), (EPI_F16, 1536, 640, 640), (EPI_F16, 384, 1280, 1280), (EPI_F16, 96, 1280, 1280), (EPI_BF16, 1008, 2560, 1280),
+              (EPI_BF16, 4032, 1280, 640), (EPI_BF16, 768, 2560, 1280), (EPI_BF16, 3072, 1280, 640), (EPI_GEGLU, 1008, 10240, 1280), (EPI_GEGLU, 4032, 5120, 640)]
+    for epi, rps, N, K in shapes:
+        got = {cls[pick(0, epi, s, rps, N, K)[0]] for s in (1, 2, 3, 4, 5, 7, 8)}
+        assert len(got) == 1, (epi, rps, N, K, got)
+    # 7 streams of a rich-text step
+    assert pick(0, EPI_F16, 7, 1008, 1280, 1280)[0] == 0 and pick(0, EPI_F16, 7, 1008, 1280, 5120)[0] == 0       # as at 1024 rows
+    assert pick(0, EPI_F16, 7, 4032, 640, 640)[0] == 4 and pick(0, EPI_F16, 7, 4032, 640, 2560)[0] == 4          # as at 4096 rows
+    assert pick(0, EPI_F16, 7, 768, 1280, 1280)[0] == 0
+    assert pick(0, EPI_F16, 7, 3072, 640, 640)[0] == 0              # 3072 rows x 640: the K-split class (4096 rows: class A)
+    assert pick(0, EPI_BF16, 7, 1008, 2560, 1280)[0] == 4 and pick(0, EPI_BF16, 7, 4032, 1280, 640)[0] == 4
+    assert pick(0, EPI_BF16, 7, 768, 2560, 1280)[0] == 2 and pick(0, EPI_BF16, 7, 3072, 1280, 640)[0] == 2
+    assert pick(0, EPI_BF16, 4, 1008, 2560, 1280)[0] == 2 and pick(0, EPI_BF16, 4, 4032, 1280, 640)[0] == 2      # the Q|K of an injected step
+    assert pick(0, EPI_BF16, 7, 1008, 1280, 1280, vt=1)[0] == 6 and pick(0, EPI_BF16, 7, 4032, 640, 640, vt=1)[0] == 6
+    assert pick(0, EPI_GEGLU, 7, 1008, 10240, 1280) == (2, 1) and pick(0, EPI_GEGLU, 7, 4032, 5120, 640) == (3, 0)
+    # the plain pass (2 streams) and SD-v1.5's 3-stream steps
+    assert pick(0, EPI_F16, 2, 1008, 1280, 1280)[0] == 9 and pick(0, EPI_F16, 2, 4032, 640, 640)[0] == 11
+    assert pick(0, EPI_F16, 3, 1536, 640, 640)[0] == 1 and pick(0, EPI_F16, 3, 384, 1280, 1280)[0] == 9
+    assert pick(0, EPI_F16, 3, 96, 1280, 1280)[0] == -1             # SD-v1.5's 8x12 maps stay on gemm.hip
+    assert pick(0, EPI_F16, 3, 6144, 320, 320)[0] == -1             # K % 128 != 0
+    # the convolution query describes a SQUARE map of rows_per_stream pixels: for any other pixel count it says -2 (include/rtdiff.h)
+    for rps in (1008, 4032, 16128, 768, 3072, 12288, 96, 384, 1536, 6144):
+        assert pick(1, EPI_F16, 7, rps, 1280, 1280)[0] == -2, rps
+    lib = load_library()
+    f = lib.rt_op_gemm_pair_pick                                     # the grouped Q|K + V^T launch exists at both levels of the 96x168 latent
+    assert f(7, 7, 1008, 2560, 1280, 1280) == 0 and f(4, 7, 1008, 2560, 1280, 1280) == 1
+    assert f(7, 7, 4032, 1280, 640, 640) == 0 and f(4, 7, 4032, 1280, 640, 640) == 1
+    assert f(2, 2, 1008, 2560, 1280, 1280) == 2 and f(2, 2, 4032, 1280, 640, 640) == 3
+    assert f(7, 7, 768, 2560, 1280, 1280) == 1 and f(7, 7, 3072, 1280, 640, 640) == 1       # 128x96: Q|K on 224x256

@@ -93,7 +93,9 @@ def _ln_gemm(x16, gamma, beta, W, bias, epi=0, vt=False, rps=0, xb=None, part=No
 
 
 @pytest.mark.parametrize("M,N,K,rps", [(7168, 1280, 1280, 1024), (7168, 1280, 5120, 1024), (28672, 640, 640, 4096), (2048, 1280, 1280, 1024),
-                                       (8192, 640, 2560, 4096), (5000, 640, 640, 5000), (4096, 640, 640, 1024)])
+                                       (8192, 640, 2560, 4096), (5000, 640, 640, 5000), (4096, 640, 640, 1024),
+                                       # rows per stream of latent grids with h != w (SDXL 96x168: 1008 / 4032, 128x96: 768): 224-row tiles straddle streams
+                                       (7056, 1280, 1280, 1008), (7056, 1280, 5120, 1008), (28224, 640, 640, 4032), (5376, 1280, 1280, 768)])
 def test_trunk_producer_leaves_layernorm_partials(M, N, K, rps):
     """The fp16-trunk epilogue with LNF = 2: the trunk it writes is the plain kernel's, xb is the bf16 rounding of the same fp32 values
     (within one bf16 ulp of the fp16 trunk, every element written), and the partials are the sums of xb over the column tiles of the producer's grid
@@ -149,7 +151,8 @@ def _geglu_rows(half):
     return rows
 
 
-@pytest.mark.parametrize("tokens,Cw,rps", [(7168, 1280, 1024), (28672, 640, 4096), (2048, 1280, 1024), (8192, 640, 4096), (4096, 1280, 1024)])
+@pytest.mark.parametrize("tokens,Cw,rps", [(7168, 1280, 1024), (28672, 640, 4096), (2048, 1280, 1024), (8192, 640, 4096), (4096, 1280, 1024),
+                                           (7056, 1280, 1008), (28224, 640, 4032), (5376, 1280, 768)])       # SDXL 96x168 and 128x96 (7 streams)
 def test_folded_consumers_against_layernorm_reference(tokens, Cw, rps):
     """to_q / stacked Q|K (bf16 out), V^T (tokens on the columns), GEGLU - each against fp32 `layer_norm(x) W^T + b` on the same fp16
     trunk / bf16 weights, and against the round-5 path (LayerNorm launch -> bf16 -> plain GEMM) for the size of the change."""

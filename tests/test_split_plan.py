@@ -65,3 +65,21 @@ def test_plan_is_the_route_launch_gemm_takes(plan):
         assert plan(1, EPI_TEMB, 3, 256, 1280, 1280) == (KSLICES, 3)
     finally:
         lib.rt_op_gemm_force_config(-1)
+
+
+def test_rows_per_stream_of_grids_with_height_unlike_width(plan):
+    """Dense routes at the rows per stream of SDXL 96x168 / 128x96 and SD-v1.5 64x96 (pinned as they stand: a change of the rule shows up
+    as a diff), batch-independent like the rest; the convolution queries describe square maps and refuse any other pixel count."""
+    for epi, rps, N, K in [(EPI_F16, 1008, 1280, 1280), (EPI_F16, 1008, 1280, 5120), (EPI_F16, 4032, 640, 640), (EPI_F16, 768, 1280, 1280),
+                           (EPI_F16, 3072, 640, 640), (EPI_F16, 1536, 640, 640), (EPI_F16, 384, 1280, 1280), (EPI_F16, 6144, 320, 320)]:
+        assert {plan(0, epi, s, rps, N, K) for s in (1, 2, 3, 4, 5, 7, 8)} == {(ONE, 1)}, (epi, rps, N, K)
+    # SD-v1.5's 8x12 maps (96 tokens per stream) are sliced like the 64-token level
+    for s in (1, 2, 3, 4, 7):
+        assert plan(0, EPI_F16, s, 96, 1280, 1280) == (KSLICES, 5)
+        assert plan(0, EPI_F16, s, 96, 1280, 5120) == (KSLICES, 8)
+    lib = load_library()
+    r, s = C.c_int(-7), C.c_int(-7)
+    for conv in (1, 3):
+        for rps in (1008, 4032, 16128, 768, 3072, 96, 384, 1536):
+            assert lib.rt_op_split_plan(conv, EPI_F16, 7, rps, 1280, 1280, C.byref(r), C.byref(s)) != 0, (conv, rps)
+            assert (r.value, s.value) == (-7, -7)                    # refused: nothing written

@@ -107,3 +107,28 @@ def test_return_vis_gives_the_reference_triple(tmp_path):
         assert isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.ndim == 3 and v.shape[2] == 3 and v.shape[0] > 50
     assert len(np.unique(seg_vis.reshape(-1, 3), axis=0)) >= 5            # five clusters, five colours (+ the white margin)
     assert (tmp_path / "segmentation_k5_seed1.jpg").exists() and (tmp_path / "average_seed1_attn1.png").exists()
+
+
+def test_maps_of_an_image_with_height_unlike_width_are_refused_with_a_clear_error():
+    """The token-map path reads every recorded map as a sqrt(tokens) x sqrt(tokens) grid (attention_utils.py:246, :279 of the reference):
+    square images only.  height != width is refused outright, and maps recorded at 256x384 (latent 32x48: 1536 / 384 tokens) are refused
+    by name before any reshape - not by an empty torch.cat or a reshape error further down."""
+    import pytest
+    from rich_text_to_image_amd.attention_utils import get_token_maps
+    g = torch.Generator().manual_seed(0)
+    selfm = {"down.self": torch.rand(1, 1536, 1536, generator=g)}
+    crossm = {"down.cross": torch.rand(1, 1536, 77, generator=g), "mid.cross": torch.rand(1, 384, 77, generator=g)}
+    with pytest.raises(ValueError, match="not a square grid"):
+        get_token_maps(selfm, crossm, {}, None, 256, 256, [torch.tensor([2, 3])], seed=4, device="cpu")      # (sizes equal: the maps themselves are refused)
+    # square maps (a 1:4 image records 4096 / 1024 / 256 tokens: all perfect squares) with height != width: refused by the sizes themselves,
+    # with a filled cache as well
+    sq, sqc = synthetic_attention_maps(0, n_self=1, n_cross=1)
+    cache = {}
+    get_token_maps(sq, sqc, {}, None, 64, 64, [torch.tensor([2, 3])], seed=4, device="cpu", cache=cache)
+    for kw in ({}, {"cache": cache}):
+        with pytest.raises(ValueError, match="height == width"):
+            get_token_maps(sq, sqc, {}, None, 256, 64, [torch.tensor([2, 3])], seed=4, device="cpu", **kw)
+    # a square self-attention map next to a non-square cross-attention map: refused as well (the cross maps are reshaped too)
+    sq, _ = synthetic_attention_maps(0, n_self=1, n_cross=1)
+    with pytest.raises(ValueError, match="mid.cross"):
+        get_token_maps(sq, {"mid.cross": crossm["mid.cross"]}, {}, None, 64, 64, [torch.tensor([2, 3])], seed=4, device="cpu")

@@ -179,7 +179,7 @@ def test_switch_restores_the_patch_route():
 def sdxl():
     from oracle.unet import SDXL_CONFIG
     from test_fullsize_gpu import _build
-    eng, o = _build(SDXL_CONFIG, 128, 21, max_streams=8, max_prompts=8)
+    eng, o = _build(SDXL_CONFIG, 128, 128, 21, max_streams=8, max_prompts=8)
     yield eng, o
     eng.close()
 
@@ -193,10 +193,10 @@ def test_sdxl_forward_distance_from_the_oracle_on_both_routes(sdxl):
 
     def dist(res):
         return (sum(v * v for v in res.values()) / len(res)) ** 0.5
-    new = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, True, 801.0)
+    new = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, 128, True, 801.0)
     try:
         chk(lib.rt_op_gemm_debug2(1))
-        old = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, True, 801.0)
+        old = _stream_mode_forward(eng, o, SDXL_CONFIG, 128, 128, True, 801.0)
     finally:
         chk(lib.rt_op_gemm_debug2(0))
     print(f"SDXL forward vs fp32 oracle: phase route {dist(new):.4e} {new}, patch route {dist(old):.4e} {old}, ratio {dist(new) / dist(old):.4f}")

@@ -98,3 +98,38 @@ def test_precise_color_guidance_is_fp32_class(vae_precise):
     print(f"precise colour guidance: loss {loss:.6f} vs {loss_ref:.6f}; grad rel-L2 {rg:.3e}; update rel-L2 {ru:.3e}")
     assert abs(loss - loss_ref) < 1e-4 * abs(loss_ref)
     assert rg < 1e-3 and ru < 1e-3
+
+
+# ------------------------------------------------------------------------------------------------ latents with h != w
+# The decoders above are built at 32x32 and only ever see square latents, where a swapped (h, w) in the decoder, its backward pass or the
+# image-size colour masks computes the right answer.  Same references, same bars as the square tests above, both arithmetics.
+@pytest.mark.parametrize("precise", [False, True], ids=["single_pass", "precise"])
+@pytest.mark.parametrize("h,w", [(16, 24), (24, 16), (12, 20)])
+def test_decode_and_color_guidance_off_the_square(vae, vae_precise, h, w, precise):
+    v, o = vae_precise if precise else vae
+    t_dec, t_loss, t_grad = (3e-4, 1e-4, 1e-3) if precise else (2e-2, 2e-2, 5e-2)
+    g = torch.Generator().manual_seed(4)
+    z = torch.randn(1, 4, h, w, generator=g) * 3
+    with torch.no_grad():
+        ref = o.decode(z)
+    out = v.decode(z.to(DEV))
+    assert tuple(out.shape) == (1, 3, 8 * h, 8 * w)
+    r = rel_l2(out, ref)
+    # (the control of the comparison itself: decoding the transposed latent and transposing back is a different image)
+    with torch.no_grad():
+        swapped = rel_l2(o.decode(z.transpose(2, 3).contiguous()).transpose(2, 3), ref)
+    print(f"{'precise' if precise else 'single-pass'} vae decode {h}x{w}: rel-L2 {r:.3e} (oracle on the transposed latent, transposed back: {swapped:.3e})")
+    assert r < t_dec and swapped > 10 * t_dec
+    lat, eps = torch.randn(1, 4, h, w, generator=g), torch.randn(1, 4, h, w, generator=g)
+    masks = [(torch.rand(1, 1, 8 * h, 8 * w, generator=g) ** 2).repeat(1, 4, 1, 1) for _ in range(2)]       # image-size masks, not square
+    rgb = [torch.rand(1, 3, 1, 1, generator=g) for _ in range(2)]
+    mall = torch.rand(1, 4, h, w, generator=g)
+    alpha, sc, wgt = 0.37, TINY_VAE_CONFIG["scaling_factor"], 0.8
+    new_ref, grad_ref, loss_ref = color_guidance_update(o, lat, eps, alpha, sc, masks, rgb, wgt, mall)
+    lat_g = lat.clone().to(DEV)
+    loss, grad = v.color_guidance(lat_g, eps.to(DEV), alpha, h, w, masks, rgb, wgt, mall, want_grad=True)
+    assert tuple(grad.shape) == (1, 4, h, w)
+    rg, ru = rel_l2(grad, grad_ref), rel_l2(lat_g.cpu() - lat, new_ref - lat)
+    print(f"{'precise' if precise else 'single-pass'} colour guidance {h}x{w}: loss {loss:.6f} vs {loss_ref:.6f}; grad rel-L2 {rg:.3e}; update rel-L2 {ru:.3e}")
+    assert abs(loss - loss_ref) < t_loss * abs(loss_ref)
+    assert rg < t_grad and ru < t_grad
