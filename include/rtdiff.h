@@ -55,7 +55,10 @@ typedef struct rt_config {
     int in_channels, out_channels;      /* 4, 4 */
     int latent_h, latent_w;             /* largest latent the workspace is sized for */
     int max_streams;                    /* UNet forwards batched per launch (<= RT_MAX_STREAMS) */
-    int max_prompts;                    /* prompts resident in the cross-attention K/V cache */
+    int max_prompts;                    /* prompts resident in the cross-attention K/V cache (<= 64) */
+    int max_keys;                       /* keys of the longest prompt: 77, 154 or 231 = one, two or three 77-token CLIP windows (0 = 77).  Sizes the
+                                         * K / V^T caches (96 rows per window and prompt), the font-size tables and the cross-map store; what a step
+                                         * launches depends on the prompts' own key counts only (rt_set_prompts_keys), never on this capacity */
 } rt_config;
 
 typedef struct rt_engine rt_engine;
@@ -80,9 +83,17 @@ int rt_arena_mark_bound(rt_engine* e);                               /* after th
  * rd.py:49-84 / xl.py:256-442,741-762; index 0 = negative prompt, 1..P-2 = region prompts, P-1 = base prompt */
 int rt_set_prompts(rt_engine* e, const float* prompt_embeds, const float* pooled, const float* time_ids_host,
                    int n_prompts, int pooled_dim);
+/* Prompts of different lengths (no counterpart in the reference, whose processor asserts 77 keys: attention_processor.py:386): prompt_embeds
+ * [P, L, D] f32 with L = 77 c; prompt p's first key_counts_host[p] rows are its keys - a multiple of 77, <= L and <= rt_config.max_keys - and
+ * the rest of its L rows is ignored (a shorter prompt is NOT padded with empty windows: it attends over exactly its own keys).  A count
+ * above max_keys is RT_E_INVALID, nothing is computed and the engine stays usable.  rt_set_prompts == L = 77, every count 77. */
+int rt_set_prompts_keys(rt_engine* e, const float* prompt_embeds, const int* key_counts_host, int L, const float* pooled,
+                        const float* time_ids_host, int n_prompts, int pooled_dim);
 /* region masks (model.masks, rd.py:97,119-128 / xl.py:775,810-821): [R,4,h,w] f32 */
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
-/* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables */
+/* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables.
+ * word_pos < max_keys: key positions of the base prompt (window c at 77 c + [0, 77)); a position beyond a stream's own key count has no
+ * effect on that stream */
 int rt_set_fontsize(rt_engine* e, const int64_t* word_pos_host, const float* font_size_host, int n);
 /* scheduler tables (HOST arrays): Euler: sigmas[n+1], timesteps[n]; PNDM: alphas_cumprod[1000], timesteps[n_iter];
  * DPM-Solver++: alphas_cumprod[1000], timesteps[n] (integers, descending) */
@@ -146,7 +157,7 @@ int rt_plain_step_finish(rt_engine* e, int step_index, float guidance_scale);
  * CONDITIONAL stream of rt_plain_step, recorded for the named attention modules (reference module names such as
  * "down_blocks.1.attentions.0.transformer_blocks.0.attn1").  mode 1: accumulate over calls after the module's 10th
  * call (n_maps[name] > 10); mode 2: overwrite after the 10th call (the SD-v1.5 self-attention quirk, rd.py:423);
- * mode 0: off.  Self-attention maps are limited to 32x32 tokens (the only ones get_token_maps consumes). */
+ * mode 0: off.  A cross-attention map has as many columns as the recorded prompt has keys (77, 154 or 231).  Self-attention maps are limited to 32x32 tokens (the only ones get_token_maps consumes). */
 int rt_attn_store_enable(rt_engine* e, const char* module_name, int mode);
 int rt_attn_store_reset(rt_engine* e);
 int rt_attn_store_read(rt_engine* e, const char* module_name, float* dst_dev /* [rows, cols] f32 or NULL */, int* n_calls,
@@ -186,6 +197,16 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
                     const int* q_src_host, const int* k_src_host, const int* v_src_host, const int* wset_host,
                     const float* wabs, const float* wsgn, int B, int H, int N, int NK, int nk_valid, int DP, int cross,
                     void* stream);
+/* Cross-attention over cached prompts of different lengths, as the engine launches it: K [P*NK, ldk] / VT [H*DP, ldvt] hold NK = 96, 192 or
+ * 288 rows per prompt (96 per 77-token window, a prompt's valid keys first); batch entry b attends with prompt_host[b] over its first
+ * key_counts_host[b] keys (77, 154 or 231, <= 77 NK / 96) and nothing else - the rows behind them may hold anything finite.  wset_host /
+ * wabs / wsgn [nsets, NK] as rt_op_attention (NULL wset = plain softmax everywhere); q_src_host must be NULL (entry b reads its own Q rows).
+ * The kernel of an entry follows its OWN key count: where the shape has cross77_kernel (d = 64, N % 64 == 0) the 77-key entries run on
+ * it - the bits of rt_op_attention with nk_valid = 77 - and the longer ones on the tile loop of attn_kernel; other shapes: one launch of
+ * attn_kernel, every workgroup with the trip count of its entry. */
+int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo,
+                         const int* q_src_host, const int* prompt_host, const int* wset_host, const float* wabs, const float* wsgn,
+                         const int* key_counts_host, int B, int H, int N, int NK, int DP, void* stream);
 /* Host-only (no GPU): the partition of a self-attention launch into shared-probability units (round 6; csrc/attention.hip).  Streams that
  * attend with the same (q_src, k_src) - text_ref and the region streams that take its probabilities, attention_processor.py:522-524 - are dealt
  * G at a time into units that compute softmax(QK^T) once; mode 0 = the shape rule (tokens >= 2048: units of four in their own launch, else

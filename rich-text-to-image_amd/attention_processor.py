@@ -176,7 +176,8 @@ class HipAttnProcessor:
         cross = encoder_hidden_states is not None
         if cross:
             NK, Dc = encoder_hidden_states.shape[1], encoder_hidden_states.shape[2]
-            NKp = ((NK + 31) // 32) * 32                                  # 77 -> 96
+            # 77 -> 96; chunked prompts (77 c keys, all of them valid): 96 rows per 77-token window, 154 -> 192, 231 -> 288
+            NKp = 96 * (NK // 77) if NK in (154, 231) else ((NK + 31) // 32) * 32
             ctx = torch.zeros(B, NKp, Dc, device=dev, dtype=torch.float32)
             ctx[:, :NK].copy_(encoder_hidden_states)
             kv_in = self._bf16(ctx.reshape(B * NKp, Dc))
@@ -206,7 +207,7 @@ class HipAttnProcessor:
         wabs = wsgn = None
         wset = [0] * B
         if cross and attn_weights is not None:
-            assert NK == 77                                               # attention_processor.py:386
+            assert NK in (77, 154, 231)                                   # attention_processor.py:386 asserts 77: one to three CLIP windows here
             wabs = torch.zeros(2, NKp, device=dev); wabs[:, :NK] = 1.0
             wsgn = torch.ones(2, NKp, device=dev)
             fs = attn_weights['font_size'].to(dev).float()
@@ -232,6 +233,9 @@ class HipAttnProcessor:
                     o_ptr = C.c_void_p(O.data_ptr() + (b * N * HD + h * DP) * eb)
                     self._chk(self.lib.rt_op_gemm(a_ptr, w_ptr, None, o_ptr, None, None, 0, 0, N, DP, NKp, NKp, VT.stride(0), HD,
                                                   0, 0, 0, 0, 0, 0, 0, 0, None))
+        elif cross and NK in (154, 231):                                  # every row of a chunked prompt is a key
+            self._chk(self.lib.rt_op_attention_keys(_ptr(Q), Q.stride(0), _ptr(K), K.stride(0), _ptr(VT), VT.stride(0), _ptr(O), O.stride(0),
+                                                    None, ia(idx), ia(wset), _ptr(wabs), _ptr(wsgn), ia([NK] * B), B, H, N, NKp, DP, None))
         else:
             self._chk(self.lib.rt_op_attention(_ptr(Q), Q.stride(0), _ptr(K), K.stride(0), _ptr(VT), VT.stride(0), _ptr(O), O.stride(0),
                                                ia(idx), ia(idx), ia(idx), ia(wset), _ptr(wabs), _ptr(wsgn), B, H, N, NKp, NK, DP, int(cross), None))

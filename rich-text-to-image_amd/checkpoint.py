@@ -75,8 +75,35 @@ class ClipEncodersXL:
             hidden.append(out.hidden_states[-2])
         return torch.cat(hidden, dim=-1).float(), pooled.float()
 
-    def __call__(self, prompt, negative_prompt):
+    def encode_chunked(self, texts, max_chunks):
+        """Prompts of up to `max_chunks` 77-token windows -> (embeddings [P, 77 c_max, D], pooled [P, Dp], key counts [P]): every window is
+        a 77-token row of its own for both encoders, a prompt's windows are concatenated (zero rows behind a shorter prompt's own), the
+        pooled embedding is that of window 0 of encoder 2."""
+        from .clip_tokenizer import encode_text_chunked
+
+        def rows(k, ids):
+            with torch.no_grad():
+                out = self.encoders[k](ids.to(self.device), output_hidden_states=True)
+            return out.hidden_states[-2], out[0]
+        emb, counts, pooled = encode_text_chunked(self.tokenizers, rows, texts, max_chunks)
+        return emb, pooled, counts
+
+    def __call__(self, prompt, negative_prompt, max_prompt_chunks=1):
+        """max_prompt_chunks = 1 (default): the reference's four tensors, prompts cut at 77 tokens.  2 / 3: long prompts are chunked
+        (encode_chunked) and the result has two more entries, the key counts of the prompts and of the negative prompts; both
+        embedding tensors then share one length (the longest prompt's), zero rows behind every prompt's own keys."""
         prompt = [prompt] if isinstance(prompt, str) else list(prompt)
+        if max_prompt_chunks != 1:
+            from .clip_tokenizer import check_max_prompt_chunks, pad_keys
+            check_max_prompt_chunks(max_prompt_chunks)
+            pe, pp, pc = self.encode_chunked(prompt, max_prompt_chunks)
+            if negative_prompt is None and self.force_zeros:
+                return pe, torch.zeros_like(pe), pp, torch.zeros_like(pp), pc, [77] * pe.shape[0]
+            neg = negative_prompt or ""
+            neg = [neg] if isinstance(neg, str) else list(neg)
+            ne, npool, nc = self.encode_chunked(neg, max_prompt_chunks)
+            L = max(pe.shape[1], ne.shape[1])
+            return pad_keys(pe, L), pad_keys(ne, L), pp, npool, pc, nc
         pe, pp = self._encode(prompt)
         if negative_prompt is None and self.force_zeros:
             return pe, torch.zeros_like(pe), pp, torch.zeros_like(pp)

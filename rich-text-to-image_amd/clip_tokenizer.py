@@ -31,6 +31,85 @@ def _byte_alphabet():
     return table
 
 
+# ---- prompts longer than one CLIP window: 77-id windows of [BOS] + <= 75 ids + [EOS] + pad, encoded one by one and concatenated
+CHUNK_TOKENS = 75          # BPE ids per window
+CHUNK_KEYS = 77            # cross-attention keys per window: BOS, the ids, EOS / pad
+MAX_PROMPT_CHUNKS = 3
+
+
+def chunk_count(n_tokens):
+    """Windows a text of n_tokens BPE ids (without BOS / EOS) needs: 0, 75 -> 1; 76, 150 -> 2; 151, 225 -> 3."""
+    return max(1, -(-n_tokens // CHUNK_TOKENS))
+
+
+def chunk_key(i):
+    """Key position of base token i (0-based, without BOS) in the concatenated windows: i + 1 inside the first window, then past
+    every window's EOS and the next one's BOS.  0 -> 1, 74 -> 75, 75 -> 78, 149 -> 152, 150 -> 155."""
+    return CHUNK_KEYS * (i // CHUNK_TOKENS) + 1 + i % CHUNK_TOKENS
+
+
+def check_max_prompt_chunks(max_chunks):
+    if max_chunks not in (1, 2, 3):
+        raise ValueError(f"max_prompt_chunks must be 1, 2 or 3, got {max_chunks!r}")
+    return max_chunks
+
+
+def encode_chunks(tokenizer, text, max_chunks=MAX_PROMPT_CHUNKS):
+    """The 77-id rows of `text`: its BPE ids split every 75 (no look-back to commas, no weighting syntax), each row
+    [BOS] + <= 75 ids + [EOS] + pad with the tokenizer's own pad id.  A text that needs more than `max_chunks` rows raises ValueError:
+    nothing is cut silently.  Works with any tokenizer that has tokenize / _tokenize, convert_tokens_to_ids and the three special ids."""
+    check_max_prompt_chunks(max_chunks)
+    tokenize = getattr(tokenizer, "_tokenize", None) or tokenizer.tokenize
+    ids = list(tokenizer.convert_tokens_to_ids(tokenize(text)))
+    n = chunk_count(len(ids))
+    if n > max_chunks:
+        raise ValueError(f"prompt of {len(ids)} tokens needs {n} windows of {CHUNK_TOKENS}; max_prompt_chunks={max_chunks} allows "
+                         f"{max_chunks * CHUNK_TOKENS} tokens: {text[:60]!r}...")
+    rows = []
+    for c in range(n):
+        inner = ids[c * CHUNK_TOKENS:(c + 1) * CHUNK_TOKENS]
+        row = [tokenizer.bos_token_id] + inner + [tokenizer.eos_token_id]
+        rows.append(row + [tokenizer.pad_token_id] * (CHUNK_KEYS - len(row)))
+    return rows
+
+
+def encode_text_chunked(tokenizers, encode_rows, texts, max_chunks):
+    """Shared by the two facades.  texts -> (embeddings [P, 77 c_max, D] with zero rows behind a prompt's own windows, key counts [P],
+    extra): every window goes through `encode_rows(k, ids [n, 77]) -> (hidden [n, 77, D_k], extra_k [n, ...] or None)` of tokenizer /
+    encoder k as a 77-token row of its own; hidden states are concatenated on channels over k and on rows over a prompt's windows;
+    `extra` is the last encoder's extra output of every prompt's FIRST window (SDXL's pooled embedding)."""
+    import torch
+    per_tok = [[encode_chunks(tok, t, max_chunks) for t in texts] for tok in tokenizers]
+    nchunks = [len(r) for r in per_tok[0]]
+    for rows in per_tok[1:]:                     # SDXL's tokenizers share the vocabulary; only the pad id differs
+        if [len(r) for r in rows] != nchunks:
+            raise ValueError("the tokenizers disagree on the number of windows of a prompt")
+    hidden, extra = [], None
+    for k, rows in enumerate(per_tok):
+        flat = torch.tensor([row for r in rows for row in r], dtype=torch.long)
+        h, x = encode_rows(k, flat)
+        hidden.append(h.float())
+        extra = x
+    hid = torch.cat(hidden, dim=-1)                                   # [sum chunks, 77, D]
+    cmax, first = max(nchunks), 0
+    out = hid.new_zeros(len(texts), CHUNK_KEYS * cmax, hid.shape[-1])
+    firsts = []
+    for p, n in enumerate(nchunks):
+        out[p, :CHUNK_KEYS * n] = hid[first:first + n].reshape(CHUNK_KEYS * n, -1)
+        firsts.append(first)
+        first += n
+    counts = [CHUNK_KEYS * n for n in nchunks]
+    return out, counts, (extra[firsts].float() if extra is not None else None)
+
+
+def pad_keys(emb, length):
+    """[P, L, D] -> [P, length, D] with zero rows appended (prompt sets of different window counts share one tensor)."""
+    import torch
+    if emb.shape[1] == length:
+        return emb
+    return torch.cat([emb, emb.new_zeros(emb.shape[0], length - emb.shape[1], emb.shape[2])], 1)
+
+
 class ClipBPETokenizer:
     model_max_length = 77
 
@@ -101,6 +180,9 @@ class ClipBPETokenizer:
         if padding == "max_length":
             ids = ids + [self.pad_token_id] * (max_length - len(ids))
         return ids
+
+    def encode_chunks(self, text, max_chunks=MAX_PROMPT_CHUNKS):
+        return encode_chunks(self, text, max_chunks)
 
     def __call__(self, text, padding=None, max_length=None, truncation=False, return_tensors=None, **_):
         texts = [text] if isinstance(text, str) else list(text)

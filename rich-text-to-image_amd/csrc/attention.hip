@@ -22,6 +22,7 @@
 // measured and is slower here: 376-423 vs 700 TFLOP/s).  Built with -amdgpu-mfma-vgpr-form (Makefile).
 #include "common.h"
 #include <math.h>
+#include <algorithm>
 #include <type_traits>
 #include <utility>
 
@@ -76,15 +77,22 @@ static __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b,
 #pragma unroll
     for (int g = 0; g < G; ++g) { vb[g] = p.gvs[b][g]; ob[g] = p.gob[b][g]; }
 
-    float* wl = (float*)(smem + 2 * STAGE);    // cross: [2][KT] multipliers
+    // cross: the stream's OWN key count (77 per prompt chunk) bounds its key loop and its validity test; p.NK is only the stride between
+    // prompts in K / V^T and in the multiplier tables.  A 77-key stream runs one tile whatever its neighbours in the launch or the
+    // capacity of the caches are - the instructions (and bits) of the one-tile launch - and no tile of a longer stream is without a valid
+    // key (tile t starts at key 96 t < 77 c), so the running maximum is finite from the first tile on.  Workgroup-uniform.
+    const int nkv = CROSS ? p.nkeys[b] : p.NK;
+    const int ntile = (nkv + KT - 1) / KT;
+    const int WLN = ntile * KT;
+    float* wl = (float*)(smem + 2 * STAGE);    // cross: [2][WLN] multipliers of ALL keys of the stream (indexed by the key, not the in-tile key)
     // wset[b] < 0: plain softmax over the nk_valid keys - no multiplier tables (6 of the 7 streams of a rich-text step); the 48
     // table reads + 2 x 48 multiplies per lane are a quarter of this single-tile kernel's instructions
     const bool plain = CROSS && p.wset[b] < 0;                      // workgroup-uniform
     if (CROSS && !plain) {
         const int ws = p.wset[b];
-        for (int i = tid; i < KT; i += NT) {
+        for (int i = tid; i < WLN; i += NT) {
             wl[i] = p.wabs[ws * p.NK + i];
-            wl[KT + i] = p.wsgn[ws * p.NK + i];
+            wl[WLN + i] = p.wsgn[ws * p.NK + i];
         }
     }
 
@@ -165,7 +173,6 @@ static __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b,
     for (int e = 0; e < 8; ++e) { ka[e] = (__bf16)0.f; qm[e] = (__bf16)0.f; }
     if (FOLD && hi == 0) ka[0] = (__bf16)1.f;
 
-    const int ntile = (p.NK + KT - 1) / KT;
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -214,9 +221,9 @@ static __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b,
             for (int r = 0; r < 16; ++r) {
                 if (CROSS || RAGGED) {
                     // (uniform test first: only the sub-tiles that reach past the last valid key pay the per-element compare)
-                    if (kt * KT + (j + 1) * 32 > (CROSS ? p.nk_valid : p.NK)) {
+                    if (kt * KT + (j + 1) * 32 > nkv) {
                         const int key = kt * KT + j * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
-                        if (key >= (CROSS ? p.nk_valid : p.NK)) s[j][r] = -INFINITY;
+                        if (key >= nkv) s[j][r] = -INFINITY;
                     }
                 }
                 mx = fmaxf(mx, s[j][r]);
@@ -264,10 +271,10 @@ static __device__ __forceinline__ void attn_tile(const AttnArgs& p, const int b,
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int kl = j * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
+                    const int kl = kt * KT + j * 32 + 16 * (r >> 3) + 8 * hi + (r & 7);
                     float pv = __builtin_amdgcn_exp2f(s[j][r] - m) * wl[kl];
                     rs += pv;
-                    s[j][r] = pv * wl[KT + kl];
+                    s[j][r] = pv * wl[WLN + kl];
                 }
         } else {
 #pragma unroll
@@ -422,7 +429,9 @@ void attention_set_prio(int on) { g_attn_prio = on ? 1 : 0; }
 template <int DP, int KT, bool CROSS, bool RAGGED, int NW, bool FOLD, int PRIO, int G = 1>
 static void launch_tp(const AttnArgs& a, hipStream_t st) {
     // K / V^T double buffer (+ the cross-attention multipliers); the epilogue reuses it as NW slabs of 32 x (DP*2 + 16) bytes
-    size_t lds = 2 * (1 + G) * (size_t)KT * DP * 2 + (CROSS ? 2 * KT * sizeof(float) : 0);
+    int wln = KT;                                                    // cross: multiplier rows of the longest stream of THIS launch
+    if (CROSS) for (int b = 0; b < a.B; ++b) wln = std::max(wln, cdiv(a.nkeys[b], KT) * KT);
+    size_t lds = 2 * (1 + G) * (size_t)KT * DP * 2 + (CROSS ? 2 * wln * sizeof(float) : 0);
     const size_t slabs = (size_t)NW * 32 * (DP * 2 + 16);
     if (slabs > lds) lds = slabs;
     if (G == 1 && !CROSS && g_attn_units == 6) lds = 80 * 1024;      // (probe) the one-stream kernel at two workgroups per CU
@@ -541,7 +550,12 @@ void launch_attention(const AttnArgs& a_in, hipStream_t st) {
     RT_REQUIRE(((uintptr_t)a.Q & 15) == 0 && ((uintptr_t)a.K & 15) == 0 && ((uintptr_t)a.VT & 15) == 0 &&
                ((uintptr_t)a.O & 15) == 0, "attention: alignment");
     if (a.cross) {
-        RT_REQUIRE(a.NK == 96 && a.nk_valid <= 96 && a.wabs && a.wsgn, "cross-attention expects 77 keys padded to 96");
+        // NK: rows per prompt in K / V^T and in the tables (96 per 77-key chunk); every entry attends over its own nkeys[b] <= NK keys
+        RT_REQUIRE((a.NK == 96 || a.NK == 192 || a.NK == 288) && a.nk_valid <= a.NK && a.wabs && a.wsgn, "cross-attention expects 77-key chunks padded to 96 rows, at most three");
+        for (int b = 0; b < a.B; ++b) {
+            if (a.nkeys[b] == 0) a.nkeys[b] = a.nk_valid;
+            RT_REQUIRE(a.nkeys[b] >= 1 && a.nkeys[b] <= a.NK, "cross-attention: a stream's key count must be in [1, NK]");
+        }
         switch (a.DP) {
             case 32: launch_t<32, 96, true>(a, st); break;
             case 64: launch_t<64, 96, true>(a, st); break;

@@ -235,7 +235,7 @@ enum DebugBit {
     DBG_STORE_OWN_STATS = 17,     // the token-map store computes the softmax statistics itself although the attention launch could leave them
     DBG_STORE_APPLY_V1 = 18,      // round 4's apply kernel of the token-map store for every head dim
     DBG_NO_CROSS77 = 19,          // cross-attention on the round-4 kernels instead of cross77_kernel
-    DBG_C77_ONE_TILE = 20,        // cross77_kernel: one 16-query tile per wave for every shape
+    DBG_C77_ONE_TILE = 20,        // cross77_kernel / crossmw_kernel: one 16-query tile per wave for every shape
     DBG_C77_TWO_HEADS = 21,       // cross77_kernel: two heads per workgroup
     DBG_NO_LNFOLD = 22,           // LayerNorm launches + bf16 projections (rounds 1 - 5) instead of the folded form
     DBG_GN_TWO_LAUNCH = 23,       // GroupNorm always in its two-launch form
@@ -284,6 +284,9 @@ struct AttnArgs {
     int B, H, N;                 // queries per batch entry
     int NK;                      // keys per batch entry in K / V^T (multiple of the key tile)
     int nk_valid;                // cross: keys >= nk_valid are masked out
+    int nkeys[RT_MAXB];          // cross (attn_kernel only): the valid keys of batch entry b - its prompt's own count, 77 per chunk - when they
+                                 // differ between the entries of a launch; 0 = nk_valid.  NK is then the prompt STRIDE (96 rows per chunk of
+                                 // the longest prompt the caches are sized for): entry b runs ceil(nkeys[b] / 96) key tiles, never more
     int DP;                      // padded head dim (multiple of 32)
     int cross;
     int nqb;                     // set by launch_attention: 128-query blocks per (batch entry, head)
@@ -296,6 +299,8 @@ void launch_attention(const AttnArgs& a, hipStream_t st);
 // xblock.hip: the 77-key cross-attention as its own kernel (d = 64, cached K / V^T): 64 queries x 2 heads per workgroup, K / V^T in LDS
 bool cross77_supported(int H, int DP, int tokens, int NK, int nk_valid);
 void launch_cross77(const AttnArgs& a, hipStream_t st);
+bool crossmw_supported(int H, int DP, int tokens, int NK);    // crossmw_kernel (cross77.hip): streams of 154 / 231 keys, head dim 64
+void launch_crossmw(const AttnArgs& a, hipStream_t st);
 bool gemm_cross77_enabled();      // debug bit 19 clear
 int attention_units_plan_host(const int* q_src, const int* k_src, int B, int N, int DP, int mode, int* launch_of, int* unit_of, int* members_of);   // host-only: the partition launch_attention would take
 void gemm16_set_tall(int on);        // (A/B) rt_op_gemm_debug bit 27

@@ -83,8 +83,8 @@ struct TBlockP {
     // (s, c) = (row sum of W', b + W beta).  Derived from the packed arena by ensure_fold(); null when the block's width has no folded form.
     MatW qk1f, v1f, q2f, ff1f;
     float* qk1s = nullptr; float* v1s = nullptr; float* q2s = nullptr; float* ff1s = nullptr;
-    bf16_t* kcache = nullptr;    // [maxP*96, H*DP]
-    bf16_t* vtcache = nullptr;   // [H*DP, maxP*96]
+    bf16_t* kcache = nullptr;    // [maxP*KP, H*DP]   KP = 96 rows per 77-key chunk of rt_config.max_keys; a prompt's valid keys come first
+    bf16_t* vtcache = nullptr;   // [H*DP, maxP*KP]
     // token-map attention store: index 0 = attn1, 1 = attn2
     std::string mod_name[2];
     float* store[2] = {nullptr, nullptr};
@@ -142,12 +142,34 @@ static inline bool rt_sched_is_dpm(int kind) { return kind == RT_SCHED_DPMPP_1 |
 void launch_gather_add_rows(const float* base, const float* table, const int* /*host*/ idx, float* out, int B, int C, hipStream_t st);
 void launch_inject_add(f16_t* out, const f16_t* sc, const float* hres, const int* /*host*/ src, int B, size_t per_batch, hipStream_t st);
 void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_t st);
-void launch_pad_ctx(const float* ctx, bf16_t* out, int P, int D, hipStream_t st);
+void launch_pad_ctx(const float* ctx, bf16_t* out, int rows_valid, int rows_out, int D, hipStream_t st);
 void launch_background_blend(float* lat, const float* lat_ref, const float* mask_last, int n, hipStream_t st);
 void launch_noise_latents(float* lat, float* lat_ref, const float* x0, const float* noise, float a, float b, int n, hipStream_t st);
 void launch_source_blend(float* lat, const float* x0, const float* noise, const float* keep, float a, float b, int HW, hipStream_t st);
 
 #include "step.h"
+
+// Cross-attention of a launch whose streams have DIFFERENT key counts (prompts of one to three 77-token windows), where the shape has
+// cross77_kernel: the kernel of a stream is a function of its OWN key count - maximal runs of 77-key streams go to cross77_kernel, the
+// runs of longer ones to crossmw_kernel (cross77.hip: all 154 / 231 keys of the head in LDS) - so a one-window stream computes the
+// bits it computes alone or in a launch of one-window streams, whatever its neighbours are.  A run is the same launch on offset Q / O pointers (cross launches read Q of their
+// own batch entry).  No statistics hand-over on this route (the cross-map store then computes its own).
+static void launch_cross_runs(const AttnArgs& a, hipStream_t st) {
+    for (int b0 = 0; b0 < a.B;) {
+        const bool one = a.nkeys[b0] == 77;
+        int b1 = b0;
+        while (b1 < a.B && (a.nkeys[b1] == 77) == one) ++b1;
+        AttnArgs r = a;
+        r.B = b1 - b0; r.stats = nullptr;
+        r.Q = a.Q + (size_t)b0 * a.N * a.ldq; r.O = a.O + (size_t)b0 * a.N * a.ldo;
+        for (int i = 0; i < RT_MAXB; ++i) {
+            const int b = b0 + i < a.B ? b0 + i : b0;
+            r.q_src[i] = i; r.k_src[i] = a.k_src[b]; r.v_src[i] = a.v_src[b]; r.wset[i] = a.wset[b]; r.nkeys[i] = i < r.B ? a.nkeys[b] : 0;
+        }
+        if (one) launch_cross77(r, st); else if (crossmw_supported(r.H, r.DP, r.N, r.NK)) launch_crossmw(r, st); else launch_attention(r, st);
+        b0 = b1;
+    }
+}
 
 struct rt_engine {
     rt_config cfg;
@@ -188,8 +210,10 @@ struct rt_engine {
 
     // per-image state
     int n_prompts = 0;
+    std::vector<int> prompt_keys;    // [max_prompts] valid keys of every resident prompt (77 per chunk); rt_create fills 77
+    int KP() const { return 96 * (cfg.max_keys / 77); }      // rows per prompt in the K / V^T caches and the multiplier tables
     float* aug_emb = nullptr;        // [maxP, temb_dim] (zeros when no addition embedding)
-    float* wabs = nullptr;           // [2, 96]
+    float* wabs = nullptr;           // [2, KP]
     float* wsgn = nullptr;
     float* masks = nullptr;          // [R, 4, HW]
     int n_regions = 0, mask_hw = 0;
@@ -354,8 +378,8 @@ struct rt_engine {
             { PackArgs p = pk_matrix(k.ff1.w, 8 * C, C, C, C); p.row_map = PACK_ROWS_GEGLU; add_slot(b + ".ff.net.0.proj.weight", {8 * C, C}, p); }
             { PackArgs p = pk_vec(k.ff1.b, 8 * C); p.row_map = PACK_ROWS_GEGLU; add_slot(b + ".ff.net.0.proj.bias", {8 * C}, p); }
             k.ff2 = mk_linear(b + ".ff.net.2", 4 * C, C, true);
-            k.kcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 96 * HD * 2);
-            k.vtcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 96 * HD * 2);
+            k.kcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
+            k.vtcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
             if (ln_fold_width(C)) {
                 auto mkf = [&](const MatW& w, MatW& f, float*& sv) {
                     f.N = w.N; f.K = w.K;
@@ -419,7 +443,7 @@ struct rt_engine {
         // per-image sampler state
         const size_t HW = (size_t)cfg.latent_h * cfg.latent_w;
         aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
-        wabs = (float*)sarena.alloc(2 * 96 * 4); wsgn = (float*)sarena.alloc(2 * 96 * 4);
+        wabs = (float*)sarena.alloc((size_t)2 * KP() * 4); wsgn = (float*)sarena.alloc((size_t)2 * KP() * 4);
         masks = (float*)sarena.alloc((size_t)RT_MAXB * 4 * HW * 4);
         lat = (float*)sarena.alloc(4 * HW * 4); lat_ref = (float*)sarena.alloc(4 * HW * 4); noise_pred = (float*)sarena.alloc(4 * HW * 4);
         eps = (float*)sarena.alloc((size_t)cfg.max_streams * HW * 4 * 4);
@@ -674,12 +698,21 @@ struct rt_engine {
                 // allows it - a pure function of the layer's shape; the token-map capture of the plain pass reads Q from HBM and
                 // keeps the two-launch form for the layers it records
                 const bool capture2 = in.store_stream >= 0 && k.store_mode[1];
+                // key counts of the streams' prompts (77 per chunk).  Every route below is a function of THESE and of the layer's shape,
+                // never of the capacity (KP only enters as the stride between prompts): a launch whose streams all have 77 keys takes
+                // the kernels - and gives the bits - of an engine built for one chunk.  The one exception are the two probe-only forms
+                // below (fused2 / block2, RT_PROBES builds with their debug switches on): their kernels hold the 96-row stride in their
+                // code, so an engine with a wider one leaves them out and runs the default route instead.
+                const int KPr = KP();
+                int nkeys[RT_MAXB]; bool all77 = true;
+                for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; all77 = all77 && nkeys[b] == 77; }
                 // round 5: the 77-key attention on its own kernel (cross77_kernel, xblock.hip: 64 queries x 2 heads per workgroup, K / V^T in
                 // LDS) behind the plain to_q GEMM is faster than the fused launch of round 4 and serves the capturing layers too (Q is in HBM)
-                const bool c77 = gemm_cross77_enabled() && cross77_supported(t.heads, t.DP, HW, 96, 77) && t.d == 64;
-                const bool fused2 = !c77 && !fold2 && gemm_xattn_enabled() && xattn_fused_supported(C, t.heads, t.DP, HW) && !capture2;
+                const bool c77ok = gemm_cross77_enabled() && cross77_supported(t.heads, t.DP, HW, KPr, 77) && t.d == 64;
+                const bool c77 = all77 && c77ok;
+                const bool fused2 = all77 && KPr == 96 && !c77 && !fold2 && gemm_xattn_enabled() && xattn_fused_supported(C, t.heads, t.DP, HW) && !capture2;
                 // the 640-channel level: to_q, attention AND to_out + residual as one launch with Q / P / O in registers (xblock.hip)
-                const bool block2 = !fold2 && gemm_xblock_enabled() && xblock_supported(C, t.heads, t.DP, HW) && t.d == 64 && !capture2;
+                const bool block2 = all77 && KPr == 96 && !fold2 && gemm_xblock_enabled() && xblock_supported(C, t.heads, t.DP, HW) && t.d == 64 && !capture2;
                 if (block2) {
                     if (!dry()) {
                         XBlockArgs xa{}; xa.x = n; xa.wq = k.q2.w; xa.wo = k.out2.w; xa.bo = k.out2.b; xa.kc = k.kcache; xa.vt = k.vtcache;
@@ -710,29 +743,35 @@ struct rt_engine {
                     gemm(xb, C, k.q2f, M, qk, HD, EPI_BF16, nullptr, 0, nullptr, 0, &l2);
                 } else gemm(n, C, k.q2, M, qk, HD, EPI_BF16);
                 if (!dry()) {
-                    AttnArgs a{}; a.Q = qk; a.ldq = HD; a.K = k.kcache; a.ldk = HD; a.VT = k.vtcache; a.ldvt = cfg.max_prompts * 96;
+                    AttnArgs a{}; a.Q = qk; a.ldq = HD; a.K = k.kcache; a.ldk = HD; a.VT = k.vtcache; a.ldvt = cfg.max_prompts * KPr;
                     a.O = o; a.ldo = HD;
+                    for (int b = 0; b < B; ++b) a.nkeys[b] = nkeys[b];
                     for (int b = 0; b < B; ++b) { a.q_src[b] = b; a.k_src[b] = in.prompt[b]; a.v_src[b] = in.prompt[b]; a.wset[b] = in.fontsize[b] ? 1 : -1; }      // -1: plain softmax, no multiplier tables
                     a.wabs = wabs; a.wsgn = wsgn;
-                    a.B = B; a.H = t.heads; a.N = HW; a.NK = 96; a.nk_valid = 77; a.DP = t.DP; a.cross = 1;
+                    a.B = B; a.H = t.heads; a.N = HW; a.NK = KPr; a.nk_valid = 77; a.DP = t.DP; a.cross = 1;
                     // a recorded layer on cross77_kernel: the launch leaves the softmax statistics of the recorded stream (as the self-attention
                     // launch does for attn1), the store runs its apply kernel only
                     const bool stats2 = c77 && capture2 && k.store_calls[1] + 1 > 10 && !g_store_own_stats_flag();
                     if (stats2) { a.stats = store_stats; a.stats_b = in.store_stream; }
-                    prof_begin(RT_PROF_ATTN_CROSS, 4.0 * B * t.heads * (double)HW * 77 * t.d);
-                    if (c77) launch_cross77(a, stream); else launch_attention(a, stream);
+                    double keysum = 0; for (int b = 0; b < B; ++b) keysum += nkeys[b];
+                    prof_begin(RT_PROF_ATTN_CROSS, 4.0 * t.heads * (double)HW * keysum * t.d);
+                    if (c77) launch_cross77(a, stream);
+                    else if (c77ok) launch_cross_runs(a, stream);           // mixed key counts: every stream on the kernel of its own count
+                    else launch_attention(a, stream);
                     prof_end();
                     if (in.store_stream >= 0 && k.store_mode[1] && ++k.store_calls[1] > 10) {
-                        RT_REQUIRE((size_t)HW * 77 <= k.store_cap[1], "attention store: map larger than the enabled buffer");
+                        // the recorded prompt's own keys: [HW, 77 c] out of its 96 c cached rows
+                        const int snk = nkeys[in.store_stream], srows = 96 * (snk / 77);
+                        RT_REQUIRE((size_t)HW * snk <= k.store_cap[1], "attention store: map larger than the enabled buffer");
                         AttnStoreArgs sa{}; sa.Q = qk; sa.ldq = HD; sa.q_row0 = (long)in.store_stream * HW;
-                        sa.K = k.kcache; sa.ldk = HD; sa.k_row0 = (long)in.prompt[in.store_stream] * 96;
-                        sa.out = k.store[1]; sa.H = t.heads; sa.N = HW; sa.NK = 77; sa.NKpad = 96; sa.NKrows = 96; sa.DP = t.DP;
+                        sa.K = k.kcache; sa.ldk = HD; sa.k_row0 = (long)in.prompt[in.store_stream] * KPr;
+                        sa.out = k.store[1]; sa.H = t.heads; sa.N = HW; sa.NK = snk; sa.NKpad = srows; sa.NKrows = srows; sa.DP = t.DP;
                         sa.overwrite = k.store_mode[1] == 2;
                         if (stats2) { sa.stats = store_stats; sa.stats_ready = 1; }
-                        prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * 77 * t.d, 8.0 * HW * 77 + 2.0 * (HW + 96.0) * HD);
+                        prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * snk * t.d, 8.0 * HW * snk + 2.0 * (HW + (double)srows) * HD);
                         launch_attn_store(sa, stream);
                         prof_end();
-                        k.store_rows[1] = HW; k.store_cols[1] = 77;
+                        k.store_rows[1] = HW; k.store_cols[1] = snk;
                     }
                 }
                 }
@@ -863,18 +902,29 @@ struct rt_engine {
     }
 
     // ---------------------------------------------------------------------------- per-image setup
-    void set_prompts(const float* pe, const float* pooled, const float* time_ids, int P, int pooled_dim) {
+    // pe [P, L, D]: prompt p's first counts[p] rows are its keys (77 per chunk; counts == nullptr: all L); the rest of its L rows is not read
+    void set_prompts(const float* pe, const int* counts, int L, const float* pooled, const float* time_ids, int P, int pooled_dim) {
         RT_REQUIRE(P >= 1 && P <= cfg.max_prompts, "set_prompts: too many prompts");
+        RT_REQUIRE(L >= 77 && L % 77 == 0, "set_prompts: the embeddings must hold whole 77-token windows");
+        for (int p_ = 0; p_ < P; ++p_) {
+            const int c = counts ? counts[p_] : L;
+            RT_REQUIRE(c >= 77 && c % 77 == 0 && c <= L, "set_prompts: a prompt's key count must be a multiple of 77, at most the embeddings' length");
+            if (c > cfg.max_keys)
+                throw rt_error(RT_E_INVALID, "set_prompts: a prompt of " + std::to_string(c) + " keys on an engine built for at most " +
+                                                 std::to_string(cfg.max_keys) + " (rt_config.max_keys)");
+        }
         require_bound();
-        const int D = cfg.cross_attention_dim;
+        const int D = cfg.cross_attention_dim, KPr = KP();
         Scope sc(ws);
-        bf16_t* ctx = ws.b16((size_t)cfg.max_prompts * 96 * D);
-        launch_pad_ctx(pe, ctx, P, D, stream);
+        bf16_t* ctx = ws.b16((size_t)cfg.max_prompts * KPr * D);
+        // rows past a prompt's own keys are zeros: their K / V^T rows are finite, and masked by every attention kernel
+        for (int p_ = 0; p_ < P; ++p_)
+            launch_pad_ctx(pe + (size_t)p_ * L * D, ctx + (size_t)p_ * KPr * D, counts ? counts[p_] : L, KPr, D, stream);
         auto build = [&](TransformerP& t) {
             const int HD = t.heads * t.DP;
             for (TBlockP& k : t.blocks) {
-                gemm(ctx, D, k.k2, P * 96, k.kcache, HD, EPI_BF16);
-                gemm_vt(k.v2, ctx, D, P * 96, k.vtcache, cfg.max_prompts * 96);
+                gemm(ctx, D, k.k2, P * KPr, k.kcache, HD, EPI_BF16);
+                gemm_vt(k.v2, ctx, D, P * KPr, k.vtcache, cfg.max_prompts * KPr);
             }
         };
         // one prompt = one "stream" of 96 rows: the tile class / split-K rule of these GEMMs is keyed on that, so a prompt's cached
@@ -901,25 +951,30 @@ struct rt_engine {
             launch_small_linear(hmid, temb_dim, a2.w, a2.K, a2.b, aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
         }
         n_prompts = P;
+        for (int p_ = 0; p_ < P; ++p_) prompt_keys[p_] = counts ? counts[p_] : L;
         HIP_CHECK(hipStreamSynchronize(stream));   // host buffers (time_ids) may go away
     }
 
     void set_fontsize(const int64_t* word_pos, const float* font_size, int n) {
         // set 0: plain softmax; set 1: font-size softmax (attention_processor.py:386-396).  wabs = 0 on padded keys.
-        float ha[2 * 96], hs[2 * 96];
-        for (int s = 0; s < 2; ++s) for (int k = 0; k < 96; ++k) { ha[s * 96 + k] = k < 77 ? 1.f : 0.f; hs[s * 96 + k] = 1.f; }
+        // One table row per key POSITION of the longest prompt the engine holds (KP = 96 rows per chunk, keys first): chunk c of a prompt
+        // sits at keys 77 c + [0, 77), so every position < max_keys is a key of some prompt length.  The kernels mask by the stream's own
+        // key count, not by these tables: an entry beyond a stream's keys has no effect on it.
+        const int KPr = KP();
+        float ha[2 * 288], hs[2 * 288];
+        for (int s = 0; s < 2; ++s) for (int k = 0; k < KPr; ++k) { ha[s * KPr + k] = k < cfg.max_keys ? 1.f : 0.f; hs[s * KPr + k] = 1.f; }
         for (int i = 0; i < n; ++i) {
-            RT_REQUIRE(word_pos[i] >= 0 && word_pos[i] < 77, "set_fontsize: word_pos out of range");
+            RT_REQUIRE(word_pos[i] >= 0 && word_pos[i] < cfg.max_keys, "set_fontsize: word_pos out of range");
         }
         // torch index_put semantics with repeated indices: the last write wins for '=' and every '*=' on the
         // gathered copy also resolves to a single write per index (attention_processor.py:393,396)
         for (int i = 0; i < n; ++i) {
             const int k = (int)word_pos[i];
-            ha[96 + k] = std::fabs(font_size[i]);
-            hs[96 + k] = font_size[i] > 0 ? 1.f : (font_size[i] < 0 ? -1.f : 0.f);
+            ha[KPr + k] = std::fabs(font_size[i]);
+            hs[KPr + k] = font_size[i] > 0 ? 1.f : (font_size[i] < 0 ? -1.f : 0.f);
         }
-        HIP_CHECK(hipMemcpyAsync(wabs, ha, sizeof(ha), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemcpyAsync(wsgn, hs, sizeof(hs), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(wabs, ha, (size_t)2 * KPr * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(wsgn, hs, (size_t)2 * KPr * 4, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
 
@@ -936,7 +991,7 @@ struct rt_engine {
                 if (k.mod_name[w] != name) continue;
                 found = true;
                 const size_t N = (size_t)(cfg.latent_h >> t.level) * (cfg.latent_w >> t.level);
-                const size_t cols = w == 0 ? N : 77;
+                const size_t cols = w == 0 ? N : (size_t)cfg.max_keys;
                 if (mode != 0 && w == 0 && N > 1024)
                     throw rt_error(RT_E_UNSUPPORTED, "attention store: self-attention maps above 32x32 are not recorded (never consumed: attention_utils.py:243-248)");
                 if (mode != 0 && k.store_cap[w] < N * cols) {
@@ -1002,8 +1057,11 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         RT_REQUIRE(cfg->max_streams >= 1 && cfg->max_streams <= RT_MAXB, "rt_create: max_streams must be in [1,16]");
         RT_REQUIRE(cfg->in_channels == 4 && cfg->out_channels == 4, "rt_create: latent channels must be 4");
         RT_REQUIRE(cfg->cross_attention_dim % 8 == 0, "rt_create: cross_attention_dim % 8");
+        RT_REQUIRE(cfg->max_keys == 0 || cfg->max_keys == 77 || cfg->max_keys == 154 || cfg->max_keys == 231, "rt_create: max_keys must be 77, 154 or 231 (0 = 77)");
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
+        if (e->cfg.max_keys == 0) e->cfg.max_keys = 77;
+        e->prompt_keys.assign((size_t)std::max(1, e->cfg.max_prompts), 77);
         // pass 1: measure the arena (no device needed: lets CPU-only hosts enumerate the weight table)
         e->arena = Arena(); e->sarena = Arena(); e->farena = Arena(); e->ws.dry = true;
         e->build_plan();
@@ -1036,7 +1094,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
             e->splitk_need = 0;
             e->unet_forward(in);
             {   // the K / V^T cache GEMMs of rt_set_prompts (one prompt = one 96-row stream) at the largest prompt count
-                const int D = cfg->cross_attention_dim, P96 = cfg->max_prompts * 96;
+                const int D = cfg->cross_attention_dim, P96 = cfg->max_prompts * e->KP();
                 e->cur_hw = 96;
                 e->for_each_tblock([&](TransformerP& t, TBlockP& k) {
                     e->gemm(nullptr, D, k.k2, P96, nullptr, t.heads * t.DP, EPI_BF16);
@@ -1058,7 +1116,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
                 }
             }
             // set_prompts scratch
-            size_t sp = (size_t)cfg->max_prompts * 96 * cfg->cross_attention_dim * 2 + (size_t)cfg->max_prompts * (cfg->projection_class_embeddings_input_dim + e->temb_dim) * 4 + (1 << 16);
+            size_t sp = (size_t)cfg->max_prompts * e->KP() * cfg->cross_attention_dim * 2 + (size_t)cfg->max_prompts * (cfg->projection_class_embeddings_input_dim + e->temb_dim) * 4 + (1 << 16);
             if (sp > peak) peak = sp;
             peak += 1 << 20;
             e->ws = Workspace();
@@ -1139,7 +1197,10 @@ int rt_arena_info(rt_engine* e, void** p, uint64_t* bytes) { RT_TRY(e, { need_de
 int rt_arena_mark_bound(rt_engine* e) { for (auto& s : e->slots) s.bound = true; e->fold_dirty = true; return RT_OK; }
 
 int rt_set_prompts(rt_engine* e, const float* pe, const float* pooled, const float* tids, int P, int pooled_dim) {
-    RT_TRY(e, { need_device(e); e->ensure_fold(); e->set_prompts(pe, pooled, tids, P, pooled_dim); })
+    RT_TRY(e, { need_device(e); e->ensure_fold(); e->set_prompts(pe, nullptr, 77, pooled, tids, P, pooled_dim); })
+}
+int rt_set_prompts_keys(rt_engine* e, const float* pe, const int* key_counts, int L, const float* pooled, const float* tids, int P, int pooled_dim) {
+    RT_TRY(e, { need_device(e); RT_REQUIRE(key_counts, "rt_set_prompts_keys: key counts"); e->ensure_fold(); e->set_prompts(pe, key_counts, L, pooled, tids, P, pooled_dim); })
 }
 int rt_set_masks(rt_engine* e, const float* m, int R, int h, int w) {
     RT_TRY(e, {
@@ -1499,6 +1560,30 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
         bool same_kv = true;
         for (int b = 0; b < B; ++b) same_kv = same_kv && a.k_src[b] == a.v_src[b];
         if (cross && same_kv && gemm_cross77_enabled() && cross77_supported(H, DP, N, NK, nk_valid)) launch_cross77(a, (hipStream_t)stream);     // the engine's kernel for these shapes
+        else launch_attention(a, (hipStream_t)stream);
+    })
+}
+int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo, const int* q_src,
+                         const int* prompt, const int* wset, const float* wabs, const float* wsgn, const int* key_counts, int B, int H,
+                         int N, int NK, int DP, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(B >= 1 && B <= RT_MAXB && key_counts, "rt_op_attention_keys: batch / key counts");
+        RT_REQUIRE(NK == 96 || NK == 192 || NK == 288, "rt_op_attention_keys: NK must be 96, 192 or 288 rows per prompt");
+        AttnArgs a{}; a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.VT = (const bf16_t*)VT; a.ldvt = ldvt;
+        a.O = (bf16_t*)O; a.ldo = ldo; a.wabs = wabs; a.wsgn = wsgn;
+        bool all77 = true;
+        for (int b = 0; b < B; ++b) {
+            RT_REQUIRE(key_counts[b] >= 77 && key_counts[b] % 77 == 0 && key_counts[b] / 77 * 96 <= NK, "rt_op_attention_keys: a key count must be 77 per 96-row chunk of NK");
+            a.q_src[b] = q_src ? q_src[b] : b; a.k_src[b] = a.v_src[b] = prompt ? prompt[b] : b; a.wset[b] = wset ? wset[b] : -1;
+            a.nkeys[b] = key_counts[b]; all77 = all77 && key_counts[b] == 77;
+        }
+        a.B = B; a.H = H; a.N = N; a.NK = NK; a.nk_valid = 77; a.DP = DP; a.cross = 1;
+        // the engine's route: a stream's kernel follows its own key count - cross77_kernel for the 77-key streams where the shape has it,
+        // the tile loop of attn_kernel for the longer ones (and for everything behind debug bit 19)
+        RT_REQUIRE(!q_src, "rt_op_attention_keys: cross launches read Q of their own batch entry (q_src must be NULL)");
+        const bool c77ok = gemm_cross77_enabled() && cross77_supported(H, DP, N, NK, 77);
+        if (all77 && c77ok) launch_cross77(a, (hipStream_t)stream);
+        else if (c77ok) launch_cross_runs(a, (hipStream_t)stream);
         else launch_attention(a, (hipStream_t)stream);
     })
 }

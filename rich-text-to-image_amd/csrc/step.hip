@@ -229,16 +229,14 @@ void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_
     HIP_CHECK(hipGetLastError());
 }
 
-// text context [P, 77, D] f32 -> bf16 [P, 96, D] with zero rows 77..95
-__global__ void pad_ctx_kernel(const float* ctx, bf16_t* out, int P, int D) {
-    const size_t n = (size_t)P * 96 * D;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t c = i % D, k = (i / D) % 96, p_ = i / ((size_t)96 * D);
-        out[i] = k < 77 ? f32_to_bf16(ctx[(p_ * 77 + k) * D + c]) : (bf16_t)0;
-    }
+// one prompt: its rows_valid embedding rows as bf16, zeros behind them up to the rows_out rows the prompt owns in the K / V^T caches
+__global__ void pad_ctx_kernel(const float* ctx, bf16_t* out, int rows_valid, int rows_out, int D) {
+    const size_t n = (size_t)rows_out * D;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = i < (size_t)rows_valid * D ? f32_to_bf16(ctx[i]) : (bf16_t)0;
 }
-void launch_pad_ctx(const float* ctx, bf16_t* out, int P, int D, hipStream_t st) {
-    hipLaunchKernelGGL(pad_ctx_kernel, dim3(cdiv(P * 96 * D, 256)), dim3(256), 0, st, ctx, out, P, D);
+void launch_pad_ctx(const float* ctx, bf16_t* out, int rows_valid, int rows_out, int D, hipStream_t st) {
+    hipLaunchKernelGGL(pad_ctx_kernel, dim3(cdiv(rows_out * D, 256)), dim3(256), 0, st, ctx, out, rows_valid, rows_out, D);
     HIP_CHECK(hipGetLastError());
 }
 

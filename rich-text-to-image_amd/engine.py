@@ -51,6 +51,7 @@ class RtConfig(C.Structure):
         ("in_channels", C.c_int), ("out_channels", C.c_int),
         ("latent_h", C.c_int), ("latent_w", C.c_int),
         ("max_streams", C.c_int), ("max_prompts", C.c_int),
+        ("max_keys", C.c_int),
     ]
 
 
@@ -76,6 +77,7 @@ _SYMBOLS = [
     "rt_plain_step_part", "rt_plain_step_finish", "rt_vae_encoder_create", "rt_vae_encode", "rt_vae_posterior_sample",
     "rt_set_source", "rt_noise_latents", "rt_source_blend",
     "rt_op_gemm_debug2", "rt_op_pack_upconv", "rt_op_upconv",
+    "rt_set_prompts_keys", "rt_op_attention_keys",
 ]
 
 
@@ -116,8 +118,8 @@ def _tup(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
 
-def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8):
-    """UNet2DConditionModel kwargs (reference config.json) -> rt_config."""
+def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77):
+    """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window)."""
     c = RtConfig()
     boc = tuple(cfg["block_out_channels"])
     n = len(boc)
@@ -143,6 +145,7 @@ def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8):
     c.in_channels, c.out_channels = cfg["in_channels"], cfg["out_channels"]
     c.latent_h, c.latent_w = latent_h, latent_w
     c.max_streams, c.max_prompts = max_streams, max_prompts
+    c.max_keys = max_keys
     return c
 
 
@@ -153,10 +156,11 @@ def _ptr(t):
 class Engine:
     """One engine = one GPU.  Mirrors the C ABI one to one; see include/rtdiff.h for semantics."""
 
-    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8):
+    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77):
         self.lib = load_library()
         self.cfg_dict = dict(cfg_dict)
-        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts)
+        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys)
+        self.max_keys = max_keys
         self.h = C.c_void_p()
         self.device = device
         rc = self.lib.rt_create(C.byref(self.cfg), C.c_int(device), C.byref(self.h))
@@ -249,13 +253,21 @@ class Engine:
         self._chk(self.lib.rt_set_stream(self.h, C.c_void_p(stream_ptr)))
 
     # ---- per image
-    def set_prompts(self, prompt_embeds, pooled=None, time_ids=None):
+    def set_prompts(self, prompt_embeds, pooled=None, time_ids=None, key_counts=None):
+        """prompt_embeds [P, 77 c, D].  key_counts (one per prompt, multiples of 77; default: every row of every prompt is a key): the
+        first key_counts[p] rows of prompt p are its keys and the rest is ignored, so prompts of different lengths share one call."""
         import torch
         pe = prompt_embeds.contiguous().float()
-        assert pe.dim() == 3 and pe.shape[1] == 77
+        assert pe.dim() == 3 and pe.shape[1] >= 77 and pe.shape[1] % 77 == 0, tuple(pe.shape)
         pl = pooled.contiguous().float() if pooled is not None else None
         tid = (C.c_float * 6)(*[float(v) for v in time_ids.flatten().tolist()[:6]]) if time_ids is not None else None
-        self._chk(self.lib.rt_set_prompts(self.h, _ptr(pe), _ptr(pl), tid, pe.shape[0], pl.shape[1] if pl is not None else 0))
+        if key_counts is None and pe.shape[1] == 77:
+            self._chk(self.lib.rt_set_prompts(self.h, _ptr(pe), _ptr(pl), tid, pe.shape[0], pl.shape[1] if pl is not None else 0))
+            return
+        kc = [int(v) for v in key_counts] if key_counts is not None else [pe.shape[1]] * pe.shape[0]
+        assert len(kc) == pe.shape[0], (len(kc), pe.shape[0])
+        self._chk(self.lib.rt_set_prompts_keys(self.h, _ptr(pe), (C.c_int * len(kc))(*kc), pe.shape[1], _ptr(pl), tid, pe.shape[0],
+                                               pl.shape[1] if pl is not None else 0))
 
     def set_masks(self, masks):
         """masks: list of [1,4,h,w] tensors (model.masks) or one [R,4,h,w] tensor."""

@@ -10,7 +10,7 @@ from .unet import HipUNet2DConditionModel
 
 class RegionDiffusion:
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
-                 latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None):
+                 latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None, max_prompt_chunks=1):
         """`RegionDiffusion(device)` as sample.py:26-27 calls it: the reference loads runwayml/stable-diffusion-v1-5 there
         (rd.py:26-33); here the same id is resolved to a local diffusers-layout directory (checkpoint.resolve_checkpoint:
         `load_path` directory / $RTDIFF_SD_PATH / the Hugging Face hub cache) and UNet, VAE decoder, tokenizer and text encoder are
@@ -18,7 +18,11 @@ class RegionDiffusion:
         CLIP objects with the diffusers / transformers call surface (`.decode(z).sample`, tokenizer(...), text_encoder(ids)[0]).
         `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
         `vae_dir` on its first call.  `scheduler`: PNDMTables (the default, rd.py:35-36) or DPMSolverTables; assigning
-        `self.scheduler` later works the same way (the diffusers idiom)."""
+        `self.scheduler` later works the same way (the diffusers idiom).  `max_prompt_chunks` (1, 2 or 3; also an argument of
+        prompt_to_img / produce_attn_maps / get_text_embeds*): prompts of up to that many 75-token windows are encoded window by window
+        and attended over 77 keys per window; 1 (default) cuts a prompt at 77 tokens as the reference does."""
+        from .clip_tokenizer import check_max_prompt_chunks
+        self.max_prompt_chunks = check_max_prompt_chunks(max_prompt_chunks)
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self.device = torch.device(f"cuda:{self.device_index}")
         self.num_train_timesteps = 1000
@@ -41,10 +45,29 @@ class RegionDiffusion:
         self.n_maps = None
         self.color_loss = torch.nn.functional.mse_loss
 
-    # rd.py:49-84
-    def get_text_embeds(self, prompt, negative_prompt):
+    def _chunks(self, max_prompt_chunks):
+        from .clip_tokenizer import check_max_prompt_chunks
+        return check_max_prompt_chunks(self.max_prompt_chunks if max_prompt_chunks is None else max_prompt_chunks)
+
+    def _embed_chunked(self, texts, max_chunks):
+        """texts -> (embeddings [P, 77 c_max, D], key counts [P]): every 77-id window through the text encoder as a row of its own."""
+        from .clip_tokenizer import encode_text_chunked
+
+        def rows(_, ids):
+            with torch.no_grad():
+                return self.text_encoder(ids.to(self.device))[0], None
+        emb, counts, _ = encode_text_chunked([self.tokenizer], rows, texts, max_chunks)
+        return emb, counts
+
+    # rd.py:49-84.  max_prompt_chunks > 1: (embeddings [1 + P, 77 c_max, D] zero-padded behind every prompt's own keys, key counts)
+    def get_text_embeds(self, prompt, negative_prompt, max_prompt_chunks=None):
         if self.tokenizer is None or self.text_encoder is None:
             raise RuntimeError("RegionDiffusion.get_text_embeds needs a CLIP tokenizer + text encoder (not available offline)")
+        chunks = self._chunks(max_prompt_chunks)
+        if chunks > 1:
+            prompt = [prompt] if isinstance(prompt, str) else list(prompt)
+            negative_prompt = [negative_prompt] if isinstance(negative_prompt, str) else list(negative_prompt)
+            return self._embed_chunked(negative_prompt + prompt, chunks)
         ti = self.tokenizer(prompt, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
                             return_tensors="pt")
         with torch.no_grad():
@@ -54,10 +77,14 @@ class RegionDiffusion:
             ue = self.text_encoder(ui.input_ids.to(self.device))[0]
         return torch.cat([ue, te])
 
-    # rd.py:72-84
-    def get_text_embeds_list(self, prompts):
+    # rd.py:72-84.  max_prompt_chunks > 1: (list of [1, 77 c_p, D] embeddings, key counts)
+    def get_text_embeds_list(self, prompts, max_prompt_chunks=None):
         if self.tokenizer is None or self.text_encoder is None:
             raise RuntimeError("RegionDiffusion.get_text_embeds_list needs a CLIP tokenizer + text encoder (not available offline)")
+        chunks = self._chunks(max_prompt_chunks)
+        if chunks > 1:
+            emb, counts = self._embed_chunked(list(prompts), chunks)
+            return [emb[p:p + 1, :c] for p, c in enumerate(counts)], counts
         out = []
         for prompt in prompts:
             ti = self.tokenizer([prompt], padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
@@ -103,10 +130,13 @@ class RegionDiffusion:
     # rd.py:86-174
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, use_guidance=False, text_format_dict={}, inject_selfattn=0, inject_background=0,
-                        elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None):
+                        elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None, key_counts=None):
         """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
         `strength` of the schedule and pin the pixels of `keep_source` to the image at every step.  image=None: the reference's
-        behaviour, the other three are not read."""
+        behaviour, the other three are not read.  `text_embeddings`: [P, 77, D] as the reference passes them, or - long prompts - what
+        get_text_embeds(max_prompt_chunks > 1) returns: [P, 77 c, D] with `key_counts` (or the pair as one argument)."""
+        if isinstance(text_embeddings, tuple):
+            text_embeddings, key_counts = text_embeddings
         img2img.check_start(image, latents)
         if image is not None:
             latents = self._start_noise(image, noise)
@@ -118,13 +148,13 @@ class RegionDiffusion:
         assert n_styles == len(self.masks)                                  # rd.py:97
         h, w = latents.shape[2], latents.shape[3]
         n_prompts = text_embeddings.shape[0]
-        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts)      # R+1 forwards, +2 reference forwards
+        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
         self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
         keep = None
         if image is not None:
             x0 = img2img.source_latents(self, image)
             keep = img2img.keep_mask(self, keep_source, h, w)
-        eng.set_prompts(text_embeddings.to(self.device))
+        eng.set_prompts(text_embeddings.to(self.device), key_counts=key_counts)
         eng.set_masks([m.to(self.device) for m in self.masks])
         tfd = text_format_dict or {}
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
@@ -189,17 +219,19 @@ class RegionDiffusion:
 
     # rd.py:180-225 (plain pass; attention-map capture = SURVEY 8a row a10, next)
     def produce_attn_maps(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50,
-                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None):
+                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None, max_prompt_chunks=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts]
-        emb = self.get_text_embeds(prompts, negative_prompts)
+        emb = self.get_text_embeds(prompts, negative_prompts, max_prompt_chunks)
         lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents, image=image, strength=strength, noise=noise)
         return self.latents_to_uint8(lat)
 
     def plain_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
-                      image=None, strength=0.8, noise=None):
+                      image=None, strength=0.8, noise=None, key_counts=None):
+        if isinstance(text_embeddings, tuple):                              # get_text_embeds(max_prompt_chunks > 1): (embeddings, key counts)
+            text_embeddings, key_counts = text_embeddings
         img2img.check_start(image, latents)
         if image is not None:
             latents = self._start_noise(image, noise)
@@ -207,12 +239,12 @@ class RegionDiffusion:
             latents = torch.randn((1, self.unet.in_channels, height // 8, width // 8), device=self.device)
         h, w = latents.shape[2], latents.shape[3]
         n_prompts = text_embeddings.shape[0]
-        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts)      # R+1 forwards, +2 reference forwards
+        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
         self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
         hooks = getattr(self, "_tokenmap_hooks", False)
         if image is not None:
             img2img.check_tokenmap_iterations(hooks, len(self.scheduler.timesteps))
-        eng.set_prompts(text_embeddings.to(self.device))
+        eng.set_prompts(text_embeddings.to(self.device), key_counts=key_counts)
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         self._start(eng, latents, None if image is None else img2img.source_latents(self, image), None)
         if hooks:
@@ -244,12 +276,12 @@ class RegionDiffusion:
     # rd.py:248-273
     def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                       latents=None, text_format_dict={}, use_guidance=False, inject_selfattn=0, inject_background=0,
-                      image=None, strength=0.8, noise=None, keep_source=None):
+                      image=None, strength=0.8, noise=None, keep_source=None, max_prompt_chunks=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts]
-        text_embeds = self.get_text_embeds(prompts, negative_prompts)
+        text_embeds = self.get_text_embeds(prompts, negative_prompts, max_prompt_chunks)
         latents = self.produce_latents(text_embeds, height=height, width=width, latents=latents,
                                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                        use_guidance=use_guidance, text_format_dict=text_format_dict,

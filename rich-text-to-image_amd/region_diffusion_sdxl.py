@@ -18,7 +18,8 @@ class StableDiffusionXLPipelineOutput(dict):
 
 class RegionDiffusionXL:
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
-                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None):
+                 vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None,
+                 max_prompt_chunks=1):
         """`RegionDiffusionXL(load_path="stabilityai/stable-diffusion-xl-base-1.0")` as sample.py:28-30 calls it (xl.py:105-120
         loads every component from `load_path`): a diffusers-layout directory, or a hub id resolved to one without a network
         (checkpoint.resolve_checkpoint: $RTDIFF_SDXL_PATH for the default id, then the Hugging Face hub cache).  Callers that hold
@@ -54,6 +55,10 @@ class RegionDiffusionXL:
         self.selfattn_maps = self.crossattn_maps = self.n_maps = None
         self.attention_maps = None                                   # xl.py:132 (only the evaluation hooks ever set it)
         self.tokenizer = tokenizer                                   # richtext_utils needs `model.tokenizer._tokenize`
+        # prompts of up to this many 75-token windows are encoded window by window and attended over 77 keys per window (also an
+        # argument of sample()); 1 = the reference: a prompt is cut at 77 tokens
+        from .clip_tokenizer import check_max_prompt_chunks
+        self.max_prompt_chunks = check_max_prompt_chunks(max_prompt_chunks)
 
     def reset_attention_maps(self):
         for maps in (self.selfattn_maps, self.crossattn_maps):
@@ -71,11 +76,14 @@ class RegionDiffusionXL:
     def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size):                # xl.py:539-553
         return torch.tensor([list(original_size + crops_coords_top_left + target_size)], dtype=torch.float32)
 
-    def encode_prompt(self, prompt, negative_prompt):
+    def encode_prompt(self, prompt, negative_prompt, max_prompt_chunks=1):
+        """-> the reference's four tensors; with max_prompt_chunks > 1 also the key counts of the prompts and the negative prompts."""
         if self.text_encoders is None:
             raise RuntimeError("RegionDiffusionXL needs CLIP text encoders for string prompts (not available offline); "
                                "pass prompt_embeds / pooled_prompt_embeds instead")
-        return self.text_encoders(prompt, negative_prompt)
+        if max_prompt_chunks == 1:
+            return self.text_encoders(prompt, negative_prompt)
+        return self.text_encoders(prompt, negative_prompt, max_prompt_chunks=max_prompt_chunks)
 
     # RegionDiffusion.encode_imgs (rd.py:238-246) with the SDXL VAE: its config and scaling factor, fp32-class contractions like the
     # pipeline's decoder (xl.py:856).  In order: a VAE object with `.encode`, the `vae_encoder` given to the constructor, an encoder
@@ -111,18 +119,28 @@ class RegionDiffusionXL:
                negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True, callback=None, callback_steps=1,
                cross_attention_kwargs=None, guidance_rescale=0.0, original_size=None, crops_coords_top_left=(0, 0),
                target_size=None, use_guidance=False, inject_selfattn=0, inject_background=0, text_format_dict=None,
-               run_rich_text=False, elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None):
+               run_rich_text=False, elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None,
+               max_prompt_chunks=None, prompt_key_counts=None, negative_key_counts=None):
         """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
         `strength` of the schedule, and (rich pass) pin the pixels of `keep_source` to the image at every step.  image=None: the
-        reference's behaviour, the other three are not read."""
+        reference's behaviour, the other three are not read.
+        `max_prompt_chunks` (default: the constructor's): string prompts of up to that many 75-token windows are chunked instead of cut.
+        Callers that pass `prompt_embeds` of 77 c rows say with `prompt_key_counts` / `negative_key_counts` how many rows of every
+        prompt are its keys (default: all of them)."""
+        from .clip_tokenizer import check_max_prompt_chunks, pad_keys
+        chunks = check_max_prompt_chunks(self.max_prompt_chunks if max_prompt_chunks is None else max_prompt_chunks)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
         self.check_inputs(prompt, height, width, prompt_embeds, pooled_prompt_embeds)
         if prompt_embeds is None:
-            prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
-                self.encode_prompt(prompt, negative_prompt)
+            if chunks > 1:
+                prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, prompt_key_counts, \
+                    negative_key_counts = self.encode_prompt(prompt, negative_prompt, chunks)
+            else:
+                prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = \
+                    self.encode_prompt(prompt, negative_prompt)
         do_cfg = guidance_scale > 1.0
         if run_rich_text and do_cfg and guidance_rescale > 0.0:
             raise NotImplementedError                                                              # xl.py:827-830
@@ -149,10 +167,17 @@ class RegionDiffusionXL:
             keep = img2img.keep_mask(self, keep_source, h, w) if run_rich_text else None
             img2img.check_tokenmap_iterations(not run_rich_text and getattr(self, "_tokenmap_hooks", False), len(self.scheduler.timesteps))
         add_time_ids = self._get_add_time_ids(tuple(original_size), tuple(crops_coords_top_left), tuple(target_size))
+        key_counts = None
+        if prompt_key_counts is not None or negative_key_counts is not None or prompt_embeds.shape[1] != negative_prompt_embeds.shape[1]:
+            key_counts = list(negative_key_counts or [negative_prompt_embeds.shape[1]] * negative_prompt_embeds.shape[0]) + \
+                list(prompt_key_counts or [prompt_embeds.shape[1]] * prompt_embeds.shape[0])
+            L = max(prompt_embeds.shape[1], negative_prompt_embeds.shape[1])
+            prompt_embeds, negative_prompt_embeds = pad_keys(prompt_embeds, L), pad_keys(negative_prompt_embeds, L)
         embeds = torch.cat([negative_prompt_embeds, prompt_embeds], 0).to(self.device).float()    # xl.py:760
         pooled = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], 0).to(self.device).float()
-        eng = self.unet.engine(h, w, streams=embeds.shape[0] + 2 if run_rich_text else 2, prompts=embeds.shape[0])
-        eng.set_prompts(embeds, pooled, add_time_ids)
+        eng = self.unet.engine(h, w, streams=embeds.shape[0] + 2 if run_rich_text else 2, prompts=embeds.shape[0],
+                               keys=max(key_counts) if key_counts else embeds.shape[1])
+        eng.set_prompts(embeds, pooled, add_time_ids, key_counts=key_counts)
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         if image is None:
             eng.set_latents(latents)

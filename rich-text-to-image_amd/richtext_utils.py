@@ -13,6 +13,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from .clip_tokenizer import chunk_key
+
 # named colours used to turn a hex colour into a word of the region prompt (richtext_utils.py:7-19; data)
 COLORS = {'brown': [165, 42, 42], 'red': [255, 0, 0], 'pink': [253, 108, 158], 'orange': [255, 165, 0], 'yellow': [255, 255, 0],
           'purple': [128, 0, 128], 'green': [0, 128, 0], 'blue': [0, 0, 255], 'white': [255, 255, 255], 'gray': [128, 128, 128],
@@ -126,36 +128,56 @@ def parse_json(json_str, device=None):
     return parse_rich_text(json_str, device).astuple()
 
 
-def _token_ids(tokenizer, base_tokens, text):
-    # quirk 7: `.index` maps a repeated word to its FIRST occurrence; +1 skips the start-of-text token
-    return [base_tokens.index(tok) + 1 for tok in tokenizer._tokenize(text)]
+def _max_chunks(model, max_prompt_chunks):
+    return getattr(model, 'max_prompt_chunks', 1) if max_prompt_chunks is None else max_prompt_chunks
+
+
+def _token_ids(tokenizer, base_tokens, text, max_chunks=None):
+    # quirk 7: `.index` maps a repeated word to its FIRST occurrence; chunk_key(i) = i + 1 (skips the start-of-text token) inside the
+    # first 75-token window and steps over every later window's EOS / BOS pair (clip_tokenizer.chunk_key).
+    # max_chunks: the CLIP windows the text may span - a formatted word behind them has no key to stand on, which is said here and not
+    # as an index error further down
+    ids = [chunk_key(base_tokens.index(tok)) for tok in tokenizer._tokenize(text)]
+    if max_chunks is not None and any(k >= 77 * max_chunks for k in ids):
+        raise ValueError(f"the formatted text {text!r} lies behind token {75 * max_chunks} of a base text of {len(base_tokens)} tokens: "
+                         f"max_prompt_chunks={max_chunks} keeps {75 * max_chunks} tokens; raise max_prompt_chunks (up to 3) or shorten the text")
+    return ids
+
+
+def _unused_token_ids(base_tokens, used, max_chunks=None):
+    """Key positions of the base tokens no span claimed (the "background" list): mapped positions only, never a BOS / EOS / pad key,
+    and none behind the windows the text is cut to (max_chunks = 1: the unformatted tail of a long text is dropped, as its encoding is)."""
+    last = None if max_chunks is None else 77 * max_chunks
+    return [k for k in (chunk_key(i) for i in range(len(base_tokens))) if k not in used and (last is None or k < last)]
 
 
 def get_region_diffusion_input(model, base_text_prompt, style_text_prompts, footnote_text_prompts, footnote_target_tokens,
-                               color_text_prompts, color_names):
+                               color_text_prompts, color_names, max_prompt_chunks=None):
     """Algorithm 1 of the paper (utils/richtext_utils.py:139-185): one region prompt per attributed span + the base prompt."""
     tok = model.tokenizer
+    mc = _max_chunks(model, max_prompt_chunks)
     base_tokens = tok._tokenize(base_text_prompt)
     prompts, ids = [], []
     for p in style_text_prompts:
         prompts.append(p)
-        ids.append(_token_ids(tok, base_tokens, p.split('in the style of')[0]))
+        ids.append(_token_ids(tok, base_tokens, p.split('in the style of')[0], mc))
     for note, target in zip(footnote_text_prompts, footnote_target_tokens):
         prompts.append(note)
-        ids.append(_token_ids(tok, base_tokens, target))
+        ids.append(_token_ids(tok, base_tokens, target, mc))
     for text, name in zip(color_text_prompts, color_names):
         prompts.append(name + ' ' + text)
-        ids.append(_token_ids(tok, base_tokens, text))
+        ids.append(_token_ids(tok, base_tokens, text, mc))
     prompts.append(base_text_prompt)
     used = {i for group in ids for i in group}
-    ids.append([i for i in range(1, len(base_tokens) + 1) if i not in used])
+    ids.append(_unused_token_ids(base_tokens, used, mc))
     return prompts, [torch.LongTensor(g) for g in ids], base_tokens
 
 
-def get_attention_control_input(model, base_tokens, size_text_prompts_and_sizes, device=None):
+def get_attention_control_input(model, base_tokens, size_text_prompts_and_sizes, device=None, max_prompt_chunks=None):
+    mc = _max_chunks(model, max_prompt_chunks)
     word_pos, sizes = [], []
     for text, fs in size_text_prompts_and_sizes:
-        for i in _token_ids(model.tokenizer, base_tokens, text):
+        for i in _token_ids(model.tokenizer, base_tokens, text, mc):
             word_pos.append(i)
             sizes.append(fs)
     if not word_pos:
@@ -165,10 +187,11 @@ def get_attention_control_input(model, base_tokens, size_text_prompts_and_sizes,
 
 
 def get_gradient_guidance_input(model, base_tokens, color_text_prompts, color_rgbs, text_format_dict, guidance_start_step=999,
-                                color_guidance_weight=1):
-    ids = [_token_ids(model.tokenizer, base_tokens, t) for t in color_text_prompts]
+                                color_guidance_weight=1, max_prompt_chunks=None):
+    mc = _max_chunks(model, max_prompt_chunks)
+    ids = [_token_ids(model.tokenizer, base_tokens, t, mc) for t in color_text_prompts]
     used = {i for group in ids for i in group}
-    ids.append([i for i in range(1, len(base_tokens) + 1) if i not in used])
+    ids.append(_unused_token_ids(base_tokens, used, mc))
     text_format_dict['target_RGB'] = color_rgbs
     text_format_dict['guidance_start_step'] = guidance_start_step
     text_format_dict['color_guidance_weight'] = color_guidance_weight

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from .attention_utils import get_token_maps
+from .clip_tokenizer import check_max_prompt_chunks
 from .richtext_utils import (get_attention_control_input, get_gradient_guidance_input, get_region_diffusion_input, parse_json,
                              seed_everything)
 
@@ -30,16 +31,20 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     guidance_weight, steps, noise_index, negative_prompt (sample.py:135-143).
     `init_image` ([1,3,height,width] in [0,1], or [1,4,h,w] latents): both passes start from it instead of noise and run the last
     `strength` of the schedule; it is encoded once and the same latents, strength and noise go to both passes.  `keep_source`
-    ("background" or a mask, img2img.py) pins those pixels of the rich pass to the image."""
+    ("background" or a mask, img2img.py) pins those pixels of the rich pass to the image.
+    `param['max_prompt_chunks']` (optional: 1, 2 or 3; default: the model's own `max_prompt_chunks`): texts of up to that many 75-token CLIP windows are chunked, in
+    both passes, instead of cut at 77 tokens; a text that needs more raises ValueError."""
+    # the request's own choice, else the one the model was built with; passed to every call below, the model is not changed
+    chunks = check_max_prompt_chunks(param.get('max_prompt_chunks') or getattr(model, 'max_prompt_chunks', 1))
     if run_dir:
         os.makedirs(run_dir, exist_ok=True)
     spans = parse_json(param['text_input'], device=model.device)
     base_text_prompt, style_p, note_p, note_tok, color_p, color_names, color_rgbs, sizes, use_grad_guidance = spans
     region_text_prompts, region_target_token_ids, base_tokens = get_region_diffusion_input(
-        model, base_text_prompt, style_p, note_p, note_tok, color_p, color_names)
-    text_format_dict = get_attention_control_input(model, base_tokens, sizes, device=model.device)
+        model, base_text_prompt, style_p, note_p, note_tok, color_p, color_names, max_prompt_chunks=chunks)
+    text_format_dict = get_attention_control_input(model, base_tokens, sizes, device=model.device, max_prompt_chunks=chunks)
     text_format_dict, color_target_token_ids = get_gradient_guidance_input(
-        model, base_tokens, color_p, color_rgbs, text_format_dict, color_guidance_weight=color_guidance_weight)
+        model, base_tokens, color_p, color_rgbs, text_format_dict, color_guidance_weight=color_guidance_weight, max_prompt_chunks=chunks)
     height, width, seed, negative_text = param['height'], param['width'], param['noise_index'], param['negative_prompt']
     timings = {}
 
@@ -56,11 +61,11 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         model.reset_attention_maps()
     if model_type == 'SD':
         plain_img = model.produce_attn_maps([base_text_prompt], [negative_text], height=height, width=width,
-                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, **start)
+                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, max_prompt_chunks=chunks, **start)
     else:
         plain_img = model.sample([base_text_prompt], negative_prompt=[negative_text], height=height, width=width,
                                  num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], run_rich_text=False,
-                                 latents=latents, **start)
+                                 latents=latents, max_prompt_chunks=chunks, **start)
     timings['plain'] = time.time() - t0
 
     t0 = time.time()
@@ -109,12 +114,12 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         rich_img = model.prompt_to_img(region_text_prompts, [negative_text], height=height, width=width,
                                        num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                        use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn,
-                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, **start)
+                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, max_prompt_chunks=chunks, **start)
     else:
         rich_img = model.sample(region_text_prompts, negative_prompt=[negative_text], height=height, width=width,
                                 num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                 use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn, text_format_dict=text_format_dict,
-                                inject_background=inject_background, run_rich_text=True, latents=latents, **start)
+                                inject_background=inject_background, run_rich_text=True, latents=latents, max_prompt_chunks=chunks, **start)
     timings['rich'] = time.time() - t0
     return plain_img, rich_img, timings
 
@@ -142,12 +147,13 @@ def build_requests(a):
                 r = json.loads(line)
                 js = r["rich_text_json"]
                 reqs.append(dict(text_input=_load_json_arg(js) if isinstance(js, str) else js, seed=int(r.get("seed", a.seed)),
-                                 negative_prompt=r.get("negative_prompt", a.negative_prompt)))
+                                 negative_prompt=r.get("negative_prompt", a.negative_prompt),
+                                 max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1))))))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
-        reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt) for j, sd in pairs]
+        reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1)) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -231,6 +237,9 @@ def build_parser():
     p.add_argument('--sample_steps', type=int, default=41)
     p.add_argument('--rich_text_json', type=str, nargs='+', default=None, help='JSON text or a file holding it; several = independent requests')
     p.add_argument('--negative_prompt', type=str, default='')
+    p.add_argument('--max_prompt_chunks', type=int, default=1, choices=(1, 2, 3),
+                   help='75-token CLIP windows a text may span (chunked and concatenated: 77 cross-attention keys per window); 1 = cut at 77 tokens, '
+                        'as the reference does.  A text that needs more windows than allowed is an error, never cut silently')
     p.add_argument('--model', type=str, default='SD', choices=['SD', 'SDXL', 'AnimeXL'])
     p.add_argument('--guidance_weight', type=float, default=8.5)
     p.add_argument('--color_guidance_weight', type=float, default=0.5)
@@ -315,7 +324,8 @@ def main(argv=None):
     out = []
     for r in mine:
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
-                 'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt']}
+                 'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
+                 'max_prompt_chunks': r.get('max_prompt_chunks', 1)}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

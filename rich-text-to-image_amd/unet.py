@@ -10,12 +10,12 @@ from .engine import Engine
 class HipUNet2DConditionModel:
     """Holds the engine(s) for one set of weights; engines are created lazily per latent size."""
 
-    def __init__(self, config, state_dict=None, device=0, max_streams=8, max_prompts=8):
+    def __init__(self, config, state_dict=None, device=0, max_streams=8, max_prompts=8, max_keys=77):
         self.config_dict = dict(config)
         self.config = types.SimpleNamespace(**config)
         self.in_channels = config["in_channels"]
         self.device_index = device
-        self.max_streams, self.max_prompts = max_streams, max_prompts
+        self.max_streams, self.max_prompts, self.max_keys = max_streams, max_prompts, max_keys
         self._state_dict = state_dict
         self._engines = {}
 
@@ -24,13 +24,20 @@ class HipUNet2DConditionModel:
         for e in self._engines.values():
             e.load_state_dict(sd)
 
-    def engine(self, h, w, streams=None, prompts=None):
-        """Engine for latent size (h, w).  `streams` / `prompts`: what the caller is about to use (F batched forwards per step,
-        P prompts in the K/V cache); an engine sized for fewer is rebuilt once with room for them (<= 16 streams)."""
+    def engine(self, h, w, streams=None, prompts=None, keys=None):
+        """Engine for latent size (h, w).  `streams` / `prompts` / `keys`: what the caller is about to use (F batched forwards per step,
+        P prompts in the K/V cache, the keys of the longest prompt: 77 per CLIP window); an engine sized for fewer is rebuilt once with
+        room for them (<= 16 streams, <= 231 keys).  If the rebuild fails the old engines AND the old limits stay."""
         grow = False
+        limits = (self.max_streams, self.max_prompts, self.max_keys)
+        # every request is checked before any limit moves: a refused call leaves the limits the engines were built for
+        if keys and keys > self.max_keys and keys not in (154, 231):
+            raise ValueError(f"{keys} cross-attention keys per prompt: the engine takes 77, 154 or 231 (one to three CLIP windows)")
+        if streams and streams > 16:
+            raise ValueError(f"{streams} batched UNet forwards per step exceed the engine limit of 16 (at most 13 regions with injection)")
+        if keys and keys > self.max_keys:
+            self.max_keys, grow = keys, True
         if streams and streams > self.max_streams:
-            if streams > 16:
-                raise ValueError(f"{streams} batched UNet forwards per step exceed the engine limit of 16 (at most 13 regions with injection)")
             self.max_streams, grow = min(16, max(streams, 2 * self.max_streams)), True
         if prompts and prompts > self.max_prompts:
             self.max_prompts, grow = max(prompts, 2 * self.max_prompts), True
@@ -50,7 +57,7 @@ class HipUNet2DConditionModel:
                 raise RuntimeError("HipUNet2DConditionModel: no weights loaded (call load_state_dict)")
             try:
                 e = Engine(self.config_dict, h, w, device=self.device_index, max_streams=self.max_streams,
-                           max_prompts=self.max_prompts)
+                           max_prompts=self.max_prompts, max_keys=self.max_keys)
                 try:
                     if empty:
                         if donor is not None:
@@ -70,8 +77,9 @@ class HipUNet2DConditionModel:
                     e.close()
                     raise
             except BaseException:
-                if grow:                                   # the old engines (and the only copy of a broadcast-fed rank's weights) stay usable
-                    self._engines = stale
+                if grow:                                   # the old engines (and the only copy of a broadcast-fed rank's weights) stay usable,
+                    self._engines = stale                  # and so do the limits they were built for: the next call tries the growth again
+                    self.max_streams, self.max_prompts, self.max_keys = limits
                 raise
             self._engines[key] = e
         for old in stale.values():                         # the rebuilt engine is bound: the smaller ones can go
@@ -81,7 +89,7 @@ class HipUNet2DConditionModel:
     def __call__(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, **kw):
         """Batch of independent samples; every sample uses its own row of `encoder_hidden_states`."""
         B, _, h, w = sample.shape
-        eng = self.engine(h, w)
+        eng = self.engine(h, w, keys=encoder_hidden_states.shape[1])
         pooled = tid = None
         if added_cond_kwargs is not None:
             pooled, tid = added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"][:1]
