@@ -33,7 +33,11 @@ extern "C" {
 enum { RT_DTYPE_F32 = 0, RT_DTYPE_F16 = 1, RT_DTYPE_BF16 = 2 };
 /* RT_SCHED_DPMPP_1 / _2: DPM-Solver++ (multistep, midpoint, epsilon prediction, lower-order final step) of order 1 / 2; either
  * UNet family, no input scaling, the x0 history of each stream kept in the engine */
-enum { RT_SCHED_EULER = 0, RT_SCHED_PNDM = 1, RT_SCHED_DPMPP_1 = 2, RT_SCHED_DPMPP_2 = 3 };
+enum { RT_SCHED_EULER = 0, RT_SCHED_PNDM = 1, RT_SCHED_DPMPP_1 = 2, RT_SCHED_DPMPP_2 = 3,
+       /* stochastic samplers: a fresh N(0, 1) field per step, a pure function of (rt_set_noise_seed, step index, pixel), made on the device.
+        * RT_SCHED_EULER_A: Euler ancestral, wherever RT_SCHED_EULER is accepted (sigma space, the same input scaling);
+        * RT_SCHED_DPMPP_SDE_1 / _2: SDE-DPM-Solver++ of order 1 / 2, wherever the DPM-Solver++ kinds are (same history, same order rule) */
+       RT_SCHED_EULER_A = 4, RT_SCHED_DPMPP_SDE_1 = 5, RT_SCHED_DPMPP_SDE_2 = 6 };
 
 /* Architecture of the UNet: the constructor arguments of UNet2DConditionModel that SD-v1.5 / SDXL use
  * (models/unet_2d_condition.py:160-215). */
@@ -96,9 +100,15 @@ int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
  * effect on that stream */
 int rt_set_fontsize(rt_engine* e, const int64_t* word_pos_host, const float* font_size_host, int n);
 /* scheduler tables (HOST arrays): Euler: sigmas[n+1], timesteps[n]; PNDM: alphas_cumprod[1000], timesteps[n_iter];
- * DPM-Solver++: alphas_cumprod[1000], timesteps[n] (integers, descending) */
+ * DPM-Solver++: alphas_cumprod[1000], timesteps[n] (integers, descending).
+ * The stochastic kinds take their parents' tables: RT_SCHED_EULER_A (4) Euler's sigmas[n+1] / timesteps[n]; RT_SCHED_DPMPP_SDE_1 / _2
+ * (5 / 6) DPM-Solver++'s alphas_cumprod[1000] / timesteps[n] */
 int rt_set_schedule(rt_engine* e, int kind, const float* timesteps_host, int n_timesteps, const float* table_host,
                     int n_table, int num_inference_steps);
+/* Seed of the noise field of the stochastic kinds (csrc/philox.h: Philox4x32-10, key = the seed's two words, counter = (pixel, step index,
+ * 0, 0), one call per pixel = its four channels).  Engine state, default 0; survives rt_set_schedule and rt_set_latents; the three
+ * deterministic kinds ignore it.  The same seed gives the same field on every rank, in the plain pass and in both streams of a rich step. */
+int rt_set_noise_seed(rt_engine* e, unsigned long long seed);
 /* sampler state: latents [1,4,h,w] f32 (copied in); the reference stream starts as a clone (rd.py:93, xl.py:774) */
 int rt_set_latents(rt_engine* e, const float* latents, int h, int w);
 int rt_get_latents(rt_engine* e, float* latents_out, float* latents_ref_out /* may be NULL */);
@@ -288,6 +298,10 @@ int rt_op_small_linear(const float* a, int lda, const void* W_bf16, int ldw, con
                        int B, int N, int K, int silu_in, int accumulate, void* stream);
 int rt_op_timestep_embed(const float* t, int n, int dim, float* out, int ldo, void* stream);
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream);
+/* The noise field a stochastic step with (seed, step index) adds on an h x w latent grid, from the same device function as the step
+ * epilogue: out_dev [4, h, w] f32 normals; words_dev [h*w, 4] the raw Philox words of every pixel, or NULL. */
+int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev /* [4,h,w] */, unsigned int* words_dev /* [h*w,4] or NULL */,
+                     void* stream);
 /* ---- CLIP text encoder pieces (transformers' CLIPTextModel[WithProjection] as called at rd.py:53-66, xl.py:330-356); the linear layers
  * and LayerNorms are rt_op_gemm / rt_op_layernorm.  ids [rows] int32 (device), tok [vocab, C], pos [N, C] fp32 -> out [rows, C] fp32 */
 int rt_op_embed(const int* ids, const float* tok, const float* pos, float* out, int rows, int N, int C, int vocab, void* stream);

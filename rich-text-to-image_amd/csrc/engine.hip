@@ -138,7 +138,15 @@ struct StepArgs;
 void launch_step_epilogue(const StepArgs& a, hipStream_t st);
 struct DpmArgs;
 void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st);
-static inline bool rt_sched_is_dpm(int kind) { return kind == RT_SCHED_DPMPP_1 || kind == RT_SCHED_DPMPP_2; }
+struct StochArgs;
+void launch_step_epilogue_stoch(const StepArgs& a, const StochArgs& d, hipStream_t st);
+void launch_step_noise(unsigned long long seed, int step, int HW, float* out, unsigned* words, hipStream_t st);
+// the SDE kinds share the DPM kinds' tables, x0 history and family rule; Euler ancestral shares Euler's tables, input scaling and family rule
+static inline bool rt_sched_is_dpm(int kind) {
+    return kind == RT_SCHED_DPMPP_1 || kind == RT_SCHED_DPMPP_2 || kind == RT_SCHED_DPMPP_SDE_1 || kind == RT_SCHED_DPMPP_SDE_2;
+}
+static inline bool rt_sched_is_euler(int kind) { return kind == RT_SCHED_EULER || kind == RT_SCHED_EULER_A; }
+static inline bool rt_sched_is_stoch(int kind) { return kind == RT_SCHED_EULER_A || kind == RT_SCHED_DPMPP_SDE_1 || kind == RT_SCHED_DPMPP_SDE_2; }
 void launch_gather_add_rows(const float* base, const float* table, const int* /*host*/ idx, float* out, int B, int C, hipStream_t st);
 void launch_inject_add(f16_t* out, const f16_t* sc, const float* hres, const int* /*host*/ src, int B, size_t per_batch, hipStream_t st);
 void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_t st);
@@ -230,6 +238,7 @@ struct rt_engine {
     int pndm_counter = 0, pndm_nets = 0, pndm_head = 0;
     int dpm_lower_order_nums = 0, dpm_head = 0;     // DPM-Solver++: steps taken (capped at 2), history slot this step writes
     int steps_done = 0;
+    unsigned long long noise_seed = 0;              // stochastic samplers: key of the per-step noise field (rt_set_noise_seed); survives rt_set_schedule / rt_set_latents
 
     // optional per-launch HIP-event profiling of the MFMA kernels (bench.py roofline leg)
     struct ProfRec { int cls; double flops, bytes; hipEvent_t a, b; };
@@ -1213,8 +1222,8 @@ int rt_set_masks(rt_engine* e, const float* m, int R, int h, int w) {
 int rt_set_fontsize(rt_engine* e, const int64_t* wp, const float* fs, int n) { RT_TRY(e, { need_device(e); e->set_fontsize(wp, fs, n); }) }
 int rt_set_schedule(rt_engine* e, int kind, const float* ts, int nts, const float* table, int ntab, int nsteps) {
     RT_TRY(e, {
-        RT_REQUIRE(kind == RT_SCHED_EULER || kind == RT_SCHED_PNDM || rt_sched_is_dpm(kind), "rt_set_schedule: kind");
-        if (kind == RT_SCHED_EULER) RT_REQUIRE(ntab == nts + 1, "euler: need n+1 sigmas");
+        RT_REQUIRE(rt_sched_is_euler(kind) || kind == RT_SCHED_PNDM || rt_sched_is_dpm(kind), "rt_set_schedule: kind");
+        if (rt_sched_is_euler(kind)) RT_REQUIRE(ntab == nts + 1, "euler: need n+1 sigmas");
         if (rt_sched_is_dpm(kind)) {
             RT_REQUIRE(ntab == 1000 && nts >= 1, "dpm-solver++: need alphas_cumprod[1000] and at least one timestep");
             for (int k = 0; k < nts; ++k)
@@ -1239,6 +1248,7 @@ int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
         e->dpm_lower_order_nums = 0; e->dpm_head = 0;
     })
 }
+int rt_set_noise_seed(rt_engine* e, unsigned long long seed) { RT_TRY(e, { e->noise_seed = seed; }) }
 int rt_set_source(rt_engine* e, const float* x0, const float* noise, const float* keep, int h, int w) {
     RT_TRY(e, {
         need_device(e);
@@ -1749,6 +1759,12 @@ int rt_op_activation(const void* x_bf16, void* out_bf16, long long n, int kind, 
 int rt_op_causal_attention(const void* q, const void* k, const void* v, int ld, void* out, int ldo, int B, int H, int N, int d, float scale,
                            void* stream) {
     OP_TRY({ launch_causal_attention((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (bf16_t*)out, ldo, B, H, N, d, scale, (hipStream_t)stream); })
+}
+int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev, unsigned int* words_dev, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(out_dev && step >= 0 && h >= 1 && w >= 1 && (long long)h * w <= (1ll << 30), "rt_op_step_noise: bad arguments");
+        launch_step_noise(seed, step, h * w, out_dev, words_dev, (hipStream_t)stream);
+    })
 }
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream) {
     OP_TRY({ RT_REQUIRE(n > 0, "cast: empty"); launch_cast_f32_bf16(x, (bf16_t*)out_bf16, (size_t)n, (hipStream_t)stream); })

@@ -12,7 +12,7 @@ struct StepArgs {
     int s_region[RT_MAXB];                  // stream of region r (r < R-1); plain mode: R == 0
     float g;
     int plain;             // 1: eps = eps[s_uncond] + g (eps[s_base] - eps[s_uncond]) without masks
-    int sched;             // RT_SCHED_EULER / RT_SCHED_PNDM / RT_SCHED_DPMPP_* (the DPM kernel takes its scalars in DpmArgs)
+    int sched;             // RT_SCHED_EULER / RT_SCHED_PNDM / RT_SCHED_DPMPP_* (the DPM kernel takes its scalars in DpmArgs, the stochastic one in StochArgs)
     int step_ref;          // advance lat_ref too
     float dsigma;          // Euler: sigma_{i+1} - sigma_i
     int pndm_mode;         // 0 first call, 1 second call (counter == 1), 2/3/4 = 2/3/4 stored eps
@@ -36,4 +36,22 @@ struct DpmArgs {
     float c2;              // 0.5 c1
     float inv_r0;          // 1 / r0, r0 = (lambda_s0 - lambda_s1) / h
     int order;             // 1 or 2
+};
+
+// Stochastic samplers (Euler ancestral, SDE-DPM-Solver++ of order 1 / 2): scalars of one step, computed on the host in fp32
+// (step_driver.inl: stoch_coeffs), and the coordinates of the step's noise field z (csrc/philox.h).
+//   Euler ancestral:   x' = x + eps dsig + z cn                                    dsig = sigma_down - sigma, cn = sigma_up
+//   SDE-DPM-Solver++:  x0 = (x - sigma_s0 eps) / alpha_s0;  x' = ratio x + c1 x0 [+ c2 inv_r0 (x0 - m1)] + cn z
+struct StochArgs {
+    int euler;             // 1: Euler ancestral, 0: SDE-DPM-Solver++
+    float dsig;            // Euler ancestral: sigma_down - sigma_i
+    float alpha_s0, sigma_s0;
+    float ratio;           // sigma_p / sigma_s0 exp(-h)
+    float c1;              // alpha_p (1 - exp(-2h))
+    float c2;              // 0.5 c1
+    float inv_r0;
+    int order;             // 1 or 2
+    float cn;              // noise scale: sigma_up / sigma_p sqrt(1 - exp(-2h))
+    unsigned seed_lo, seed_hi;
+    int step;              // index into the executed schedule
 };

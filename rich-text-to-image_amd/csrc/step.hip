@@ -1,9 +1,10 @@
 // a11 + a12 + a14 of SURVEY.md section 8a: mask-weighted region combine (models/region_diffusion.py:119-132,
 // models/region_diffusion_sdxl.py:810-825), classifier-free guidance, scheduler update (third-party
-// diffusers 0.18.2 PNDM/PLMS and Euler restated, see oracle/schedulers.py; DPM-Solver++ in a second kernel) and background blend
+// diffusers 0.18.2 PNDM/PLMS and Euler restated, see oracle/schedulers.py; DPM-Solver++ in a second kernel, the stochastic samplers in a third) and background blend
 // (rd.py:171-173, xl.py:870-872) fused into one elementwise launch over 4*h*w elements.
 // The arithmetic follows the reference's fp32 operation order so that the epilogue itself is exact.
 #include "step.h"
+#include "philox.h"
 #include "../../include/rtdiff.h"
 
 __global__ void step_epilogue_kernel(StepArgs p) {
@@ -168,12 +169,66 @@ __global__ void step_epilogue_dpm_kernel(StepArgs p, DpmArgs d) {
     }
     step_store(p, pix, newv, has_ref);
 }
+// Stochastic epilogue (Euler ancestral; SDE-DPM-Solver++ of order 1 / 2: diffusers' EulerAncestralDiscreteScheduler and
+// DPMSolverMultistepScheduler with algorithm_type="sde-dpmsolver++", [memory], see tests/sde_ref.py).  A third kernel for the reason the
+// DPM one is a second.  One Philox call per pixel gives the four channels' normals of this step; the SAME values go to the main and the
+// reference latents, so streams that are equal before the step are equal after it and the reference stream of a rich pass sees the
+// noise the plain pass saw.
+__global__ void step_epilogue_stoch_kernel(StepArgs p, StochArgs d) {
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= p.HW) return;
+    float e[4], er[4];
+    const bool has_ref = step_combine(p, pix, e, er);
+    float z[4];
+    step_noise4(d.seed_lo, d.seed_hi, (unsigned)d.step, (unsigned)pix, z);
+    float newv[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (s == 1 && !has_ref) break;
+        const float* x = s == 0 ? p.lat : p.lat_ref;
+        const float* ee = s == 0 ? e : er;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const size_t li = (size_t)c * p.HW + pix;
+            const size_t hi = (size_t)s * 4 * p.HW + li;
+            const float sample = x[li];
+            if (d.euler) {
+                newv[s][c] = sample + ee[c] * d.dsig + z[c] * d.cn;
+            } else {
+                const float x0 = (sample - d.sigma_s0 * ee[c]) / d.alpha_s0;
+                float v = d.ratio * sample + d.c1 * x0;
+                if (d.order == 2) v = v + d.c2 * (d.inv_r0 * (x0 - p.ets[1][hi]));
+                p.ets[0][hi] = x0;
+                newv[s][c] = v + d.cn * z[c];
+            }
+        }
+    }
+    step_store(p, pix, newv, has_ref);
+}
+// The field alone (rt_op_step_noise): out [4, HW] fp32, words [HW, 4] or null
+__global__ void step_noise_kernel(unsigned seed_lo, unsigned seed_hi, int step, int HW, float* out, unsigned* words) {
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= HW) return;
+    float z[4];
+    step_noise4(seed_lo, seed_hi, (unsigned)step, (unsigned)pix, z, words ? words + (size_t)pix * 4 : nullptr);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[(size_t)c * HW + pix] = z[c];
+}
 void launch_step_epilogue(const StepArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(step_epilogue_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a);
     HIP_CHECK(hipGetLastError());
 }
 void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st) {
     hipLaunchKernelGGL(step_epilogue_dpm_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_step_epilogue_stoch(const StepArgs& a, const StochArgs& d, hipStream_t st) {
+    hipLaunchKernelGGL(step_epilogue_stoch_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
+    HIP_CHECK(hipGetLastError());
+}
+void launch_step_noise(unsigned long long seed, int step, int HW, float* out, unsigned* words, hipStream_t st) {
+    hipLaunchKernelGGL(step_noise_kernel, dim3(cdiv(HW, 256)), dim3(256), 0, st, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step, HW, out,
+                       words);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -66,6 +66,53 @@ static void dpm_coeffs(rt_engine* e, int i, StepArgs& a, DpmArgs& d) {
     if (e->dpm_lower_order_nums < 2) e->dpm_lower_order_nums++;
 }
 
+static void stoch_coeffs(rt_engine* e, int i, StepArgs& a, StochArgs& d) {
+    // The stochastic samplers ([memory], see tests/sde_ref.py); fp32 scalars, evaluated left to right.  The noise field of the step is
+    // a function of (noise_seed, i, pixel): csrc/philox.h.
+    const int n = (int)e->timesteps.size();
+    RT_REQUIRE(i >= 0 && i < n, "stochastic sampler: step index out of range");
+    d.seed_lo = (unsigned)(e->noise_seed & 0xffffffffull); d.seed_hi = (unsigned)(e->noise_seed >> 32); d.step = i;
+    if (e->sched_kind == RT_SCHED_EULER_A) {
+        // EulerAncestralDiscreteScheduler: sigma_up = sqrt(s'^2 (s^2 - s'^2) / s^2), sigma_down = sqrt(s'^2 - sigma_up^2);
+        // x' = x + eps (sigma_down - s) + z sigma_up.  The last step has s' = 0: no noise.
+        const float sg = e->table[i], sp = e->table[i + 1];
+        const float up = std::sqrt(sp * sp * (sg * sg - sp * sp) / (sg * sg));
+        const float down = std::sqrt(sp * sp - up * up);
+        d.euler = 1; d.dsig = down - sg; d.cn = up;
+        return;
+    }
+    // DPMSolverMultistepScheduler, algorithm_type="sde-dpmsolver++", midpoint: alpha, sigma, lambda, s0, s1, p, h, r0, the order rule and
+    // the x0 history exactly as dpm_coeffs above.
+    //   x' = (sigma_p / sigma_s0 exp(-h)) x + alpha_p (1 - exp(-2h)) x0 [+ 0.5 alpha_p (1 - exp(-2h)) (1 / r0) (x0 - m1)] + sigma_p sqrt(1 - exp(-2h)) z
+    RT_REQUIRE((int)e->table.size() >= 1000, "sde-dpm-solver++: alphas_cumprod table missing");
+    auto alpha = [&](int t) { return std::sqrt(e->table[t]); };
+    auto sigma = [&](int t) { return std::sqrt(1.f - e->table[t]); };
+    auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
+    const int s0 = (int)e->timesteps[i], p = i == n - 1 ? 0 : (int)e->timesteps[i + 1];
+    const bool lower_order_final = i == n - 1 && n < 15;
+    const bool first = e->sched_kind == RT_SCHED_DPMPP_SDE_1 || e->dpm_lower_order_nums < 1 || lower_order_final || i == 0;
+    const float h = lambda(p) - lambda(s0);
+    const float q = 1.f - std::exp(-2.f * h);
+    d.euler = 0;
+    d.alpha_s0 = alpha(s0); d.sigma_s0 = sigma(s0);
+    d.ratio = sigma(p) / sigma(s0) * std::exp(-h);
+    d.c1 = alpha(p) * q;
+    d.c2 = 0.5f * d.c1;
+    d.cn = sigma(p) * std::sqrt(q);
+    d.order = first ? 1 : 2;
+    d.inv_r0 = 0.f;
+    if (!first) {
+        const int s1 = (int)e->timesteps[i - 1];
+        const float r0 = (lambda(s0) - lambda(s1)) / h;
+        d.inv_r0 = 1.f / r0;
+    }
+    const size_t per = (size_t)2 * 4 * e->lat_h * e->lat_w;
+    a.ets[0] = e->ets + (size_t)e->dpm_head * per;
+    a.ets[1] = e->ets + (size_t)(e->dpm_head ^ 1) * per;
+    e->dpm_head ^= 1;
+    if (e->dpm_lower_order_nums < 2) e->dpm_lower_order_nums++;
+}
+
 // The streams of rich-text step i and the flags of its epilogue (everything of region_step that is a pure function of the schedule
 // position): `in` = the F batched forwards with their mode words, `a` = the epilogue's arguments without the scheduler coefficients
 // (PNDM's are stateful: region_finish computes them once).
@@ -76,7 +123,7 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     RT_REQUIRE(i >= 0 && i < n, "region_step: step index out of range");
     RT_REQUIRE(R >= 1 && n_prompts == R + 1, "region_step: need R masks and R+1 prompts (rd.py:96-97)");
     RT_REQUIRE(mask_hw == lat_h * lat_w && lat_h > 0, "region_step: masks/latents shape mismatch");
-    RT_REQUIRE(rt_sched_is_dpm(sched_kind) || (sched_kind == RT_SCHED_EULER) == xl,
+    RT_REQUIRE(rt_sched_is_dpm(sched_kind) || rt_sched_is_euler(sched_kind) == xl,
                "region_step: SD uses PNDM or DPM-Solver++, SDXL uses Euler or DPM-Solver++");
     const float t = timesteps[i];
     const bool use_ref = isa > 0 || ibg > 0;
@@ -99,7 +146,7 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     if (!run_ref) step_ref = false;
 
     in = FwdIn{}; in.h = lat_h; in.w = lat_w; in.t = t; in.eps_out = eps;
-    const float scale = sched_kind == RT_SCHED_EULER ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;   // Euler's scale_model_input
+    const float scale = rt_sched_is_euler(sched_kind) ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;   // Euler's scale_model_input
     a = StepArgs{};
     int F = 0;
     auto add = [&](const float* x, int prompt, int fs) {
@@ -128,6 +175,13 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
 // region_diffusion_sdxl.py:810-846)
 void rt_engine::region_finish(int i, StepArgs& a, bool blend_deferred) {
     pending_blend = blend_deferred;
+    if (rt_sched_is_stoch(sched_kind)) {
+        StochArgs d{};
+        stoch_coeffs(this, i, a, d);
+        launch_step_epilogue_stoch(a, d, stream);
+        steps_done++;
+        return;
+    }
     if (rt_sched_is_dpm(sched_kind)) {
         DpmArgs d{};
         dpm_coeffs(this, i, a, d);
@@ -205,7 +259,7 @@ void rt_engine::plain_forward(int i, int first, int count) {
     RT_REQUIRE(i >= 0 && i < n, "plain_step: step index out of range");
     RT_REQUIRE(n_prompts >= 2, "plain_step: need [negative, text] prompts");
     RT_REQUIRE(first >= 0 && count >= 1 && first + count <= 2, "plain_step: stream range");
-    const bool xl = sched_kind == RT_SCHED_EULER;
+    const bool xl = rt_sched_is_euler(sched_kind);
     FwdIn in{}; in.h = lat_h; in.w = lat_w; in.t = timesteps[i]; in.B = count;
     in.eps_out = eps + (size_t)first * lat_h * lat_w * 4;            // a stream's prediction lands in its own slot of the eps buffer
     const float scale = xl ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;
@@ -216,10 +270,17 @@ void rt_engine::plain_forward(int i, int first, int count) {
 }
 void rt_engine::plain_finish(int i, float g) {
     RT_REQUIRE(i >= 0 && i < (int)timesteps.size(), "plain_step: step index out of range");     // PNDM / Euler index their tables with it
-    const bool xl = sched_kind == RT_SCHED_EULER;
+    const bool xl = rt_sched_is_euler(sched_kind);
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
     a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.sched = sched_kind; a.step_ref = 0; a.blend = 0;
+    if (rt_sched_is_stoch(sched_kind)) {
+        StochArgs d{};
+        stoch_coeffs(this, i, a, d);
+        launch_step_epilogue_stoch(a, d, stream);
+        steps_done++;
+        return;
+    }
     if (rt_sched_is_dpm(sched_kind)) {
         DpmArgs d{};
         dpm_coeffs(this, i, a, d);

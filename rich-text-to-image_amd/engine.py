@@ -78,6 +78,7 @@ _SYMBOLS = [
     "rt_set_source", "rt_noise_latents", "rt_source_blend",
     "rt_op_gemm_debug2", "rt_op_pack_upconv", "rt_op_upconv",
     "rt_set_prompts_keys", "rt_op_attention_keys",
+    "rt_set_noise_seed", "rt_op_step_noise",
 ]
 
 
@@ -291,6 +292,11 @@ class Engine:
         self._chk(self.lib.rt_set_schedule(self.h, kind, (C.c_float * len(ts))(*ts), len(ts), (C.c_float * len(tb))(*tb),
                                            len(tb), num_inference_steps))
 
+    def set_noise_seed(self, seed):
+        """Key of the per-step noise field of the stochastic samplers (schedule kinds 4 / 5 / 6); None = 0.  Engine state: it survives
+        set_schedule / set_latents, and the deterministic kinds ignore it."""
+        self._chk(self.lib.rt_set_noise_seed(self.h, C.c_uint64(int(seed or 0) & 0xFFFFFFFFFFFFFFFF)))
+
     def set_latents(self, latents):
         l = latents.contiguous().float()
         assert l.shape[0] == 1 and l.shape[1] == 4
@@ -433,6 +439,23 @@ class Engine:
                                            iarr(fontsize), iarr(qk_src), iarr(res_src), _ptr(out)))
         self.synchronize()
         return out
+
+
+def step_noise(seed, step, h, w, words=False, device=0):
+    """The N(0, 1) field a stochastic step with (noise seed, step index) adds on an h x w latent grid, from the device function the step
+    epilogue calls: [1, 4, h, w] fp32 on the GPU; words=True also returns the raw Philox words [h*w, 4] (uint32 bit patterns in int64)."""
+    import torch
+    lib = load_library()
+    dev = f"cuda:{device}"
+    with torch.cuda.device(dev):
+        out = torch.empty(1, 4, h, w, device=dev)
+        wd = torch.empty(h * w, 4, dtype=torch.int32, device=dev) if words else None
+        rc = lib.rt_op_step_noise(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(step), int(h), int(w), _ptr(out), _ptr(wd),
+                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return (out, wd.to(torch.int64) & 0xFFFFFFFF) if words else out
 
 
 # ------------------------------------------------------------------------------------------------ VAE decoder

@@ -17,7 +17,7 @@ class RegionDiffusion:
         loaded from it.  Callers that hold the weights already pass `unet_state_dict` (reference key names) and, optionally, VAE /
         CLIP objects with the diffusers / transformers call surface (`.decode(z).sample`, tokenizer(...), text_encoder(ids)[0]).
         `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
-        `vae_dir` on its first call.  `scheduler`: PNDMTables (the default, rd.py:35-36) or DPMSolverTables; assigning
+        `vae_dir` on its first call.  `scheduler`: PNDMTables (the default, rd.py:35-36) or DPMSolverTables (either algorithm); assigning
         `self.scheduler` later works the same way (the diffusers idiom).  `max_prompt_chunks` (1, 2 or 3; also an argument of
         prompt_to_img / produce_attn_maps / get_text_embeds*): prompts of up to that many 75-token windows are encoded window by window
         and attended over 77 keys per window; 1 (default) cuts a prompt at 77 tokens as the reference does."""
@@ -130,8 +130,11 @@ class RegionDiffusion:
     # rd.py:86-174
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, use_guidance=False, text_format_dict={}, inject_selfattn=0, inject_background=0,
-                        elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None, key_counts=None):
-        """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
+                        elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None, key_counts=None,
+                        noise_seed=None):
+        """`noise_seed`: seed of the per-step noise of a stochastic scheduler (DPMSolverTables(algorithm='sde-dpmsolver++')); None = 0;
+        a deterministic scheduler ignores it.  The plain pass of the same seed sees the same noise at every step.
+        `image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
         `strength` of the schedule and pin the pixels of `keep_source` to the image at every step.  image=None: the reference's
         behaviour, the other three are not read.  `text_embeddings`: [P, 77, D] as the reference passes them, or - long prompts - what
         get_text_embeds(max_prompt_chunks > 1) returns: [P, 77 c, D] with `key_counts` (or the pair as one argument)."""
@@ -159,6 +162,7 @@ class RegionDiffusion:
         tfd = text_format_dict or {}
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_noise_seed(noise_seed)
         levels = self._start(eng, latents, None if image is None else x0, keep)
         for i, t in enumerate(self.scheduler.timesteps):
             if getattr(self, "split_image", False):      # intra-image split over the ranks of the process group (launcher.split_region_step)
@@ -219,17 +223,18 @@ class RegionDiffusion:
 
     # rd.py:180-225 (plain pass; attention-map capture = SURVEY 8a row a10, next)
     def produce_attn_maps(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50,
-                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None, max_prompt_chunks=None):
+                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None, max_prompt_chunks=None, noise_seed=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts]
         emb = self.get_text_embeds(prompts, negative_prompts, max_prompt_chunks)
-        lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents, image=image, strength=strength, noise=noise)
+        lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents, image=image, strength=strength, noise=noise,
+                                 noise_seed=noise_seed)
         return self.latents_to_uint8(lat)
 
     def plain_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
-                      image=None, strength=0.8, noise=None, key_counts=None):
+                      image=None, strength=0.8, noise=None, key_counts=None, noise_seed=None):
         if isinstance(text_embeddings, tuple):                              # get_text_embeds(max_prompt_chunks > 1): (embeddings, key counts)
             text_embeddings, key_counts = text_embeddings
         img2img.check_start(image, latents)
@@ -246,6 +251,7 @@ class RegionDiffusion:
             img2img.check_tokenmap_iterations(hooks, len(self.scheduler.timesteps))
         eng.set_prompts(text_embeddings.to(self.device), key_counts=key_counts)
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_noise_seed(noise_seed)
         self._start(eng, latents, None if image is None else img2img.source_latents(self, image), None)
         if hooks:
             self._store_begin(eng)
@@ -276,7 +282,7 @@ class RegionDiffusion:
     # rd.py:248-273
     def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                       latents=None, text_format_dict={}, use_guidance=False, inject_selfattn=0, inject_background=0,
-                      image=None, strength=0.8, noise=None, keep_source=None, max_prompt_chunks=None):
+                      image=None, strength=0.8, noise=None, keep_source=None, max_prompt_chunks=None, noise_seed=None):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
@@ -286,7 +292,7 @@ class RegionDiffusion:
                                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                        use_guidance=use_guidance, text_format_dict=text_format_dict,
                                        inject_selfattn=inject_selfattn, inject_background=inject_background,
-                                       image=image, strength=strength, noise=noise, keep_source=keep_source)
+                                       image=image, strength=strength, noise=noise, keep_source=keep_source, noise_seed=noise_seed)
         return self.latents_to_uint8(latents)
 
     # hook surface of the reference (rd.py:397-443): token-map capture is the "next" row f1

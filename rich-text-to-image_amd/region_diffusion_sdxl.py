@@ -6,7 +6,7 @@ import torch
 
 from . import img2img
 from .engine import SDXL_CONFIG
-from .schedulers import DPMSolverTables, EulerTables
+from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables
 from .unet import HipUNet2DConditionModel
 
 
@@ -24,7 +24,7 @@ class RegionDiffusionXL:
         loads every component from `load_path`): a diffusers-layout directory, or a hub id resolved to one without a network
         (checkpoint.resolve_checkpoint: $RTDIFF_SDXL_PATH for the default id, then the Hugging Face hub cache).  Callers that hold
         the weights pass `unet_state_dict` (+ optional vae / text_encoders / tokenizer) and `load_path` is not read.
-        `scheduler`: EulerTables (the default, xl.py:120) or DPMSolverTables; assigning `self.scheduler` later works the same way.
+        `scheduler`: EulerTables (the default, xl.py:120), EulerAncestralTables or DPMSolverTables (either algorithm); assigning `self.scheduler` later works the same way.
         `vae_encoder` (engine.VaeEncoder) serves encode_imgs; without it encode_imgs builds one from the AutoencoderKL weights in
         `vae_dir` on its first call."""
         self.device_index = device if isinstance(device, int) else (torch.device(device).index or 0)
@@ -120,8 +120,11 @@ class RegionDiffusionXL:
                cross_attention_kwargs=None, guidance_rescale=0.0, original_size=None, crops_coords_top_left=(0, 0),
                target_size=None, use_guidance=False, inject_selfattn=0, inject_background=0, text_format_dict=None,
                run_rich_text=False, elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None,
-               max_prompt_chunks=None, prompt_key_counts=None, negative_key_counts=None):
-        """`image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
+               max_prompt_chunks=None, prompt_key_counts=None, negative_key_counts=None, noise_seed=None):
+        """`noise_seed`: seed of the per-step noise of a stochastic scheduler (EulerAncestralTables, DPMSolverTables(algorithm=
+        'sde-dpmsolver++')); None = 0; a deterministic scheduler ignores it.  The plain pass (run_rich_text=False) of the same seed sees
+        the same noise at every step.
+        `image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
         `strength` of the schedule, and (rich pass) pin the pixels of `keep_source` to the image at every step.  image=None: the
         reference's behaviour, the other three are not read.
         `max_prompt_chunks` (default: the constructor's): string prompts of up to that many 75-token windows are chunked instead of cut.
@@ -146,8 +149,8 @@ class RegionDiffusionXL:
             raise NotImplementedError                                                              # xl.py:827-830
         if use_guidance and not hasattr(self.vae, "color_guidance"):
             raise RuntimeError("use_guidance=True needs a rich_text_to_image_amd.engine.VaeDecoder as `vae` (xl.py:849-867)")
-        if not isinstance(self.scheduler, (EulerTables, DPMSolverTables)):
-            raise ValueError(f"RegionDiffusionXL: scheduler must be EulerTables or DPMSolverTables, got {type(self.scheduler).__name__}")
+        if not isinstance(self.scheduler, (EulerTables, EulerAncestralTables, DPMSolverTables)):
+            raise ValueError(f"RegionDiffusionXL: scheduler must be EulerTables, EulerAncestralTables or DPMSolverTables, got {type(self.scheduler).__name__}")
         img2img.check_start(image, latents)
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         if image is None:
@@ -179,6 +182,7 @@ class RegionDiffusionXL:
                                keys=max(key_counts) if key_counts else embeds.shape[1])
         eng.set_prompts(embeds, pooled, add_time_ids, key_counts=key_counts)
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
+        eng.set_noise_seed(noise_seed)
         if image is None:
             eng.set_latents(latents)
         else:

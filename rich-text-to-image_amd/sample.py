@@ -33,7 +33,8 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     `strength` of the schedule; it is encoded once and the same latents, strength and noise go to both passes.  `keep_source`
     ("background" or a mask, img2img.py) pins those pixels of the rich pass to the image.
     `param['max_prompt_chunks']` (optional: 1, 2 or 3; default: the model's own `max_prompt_chunks`): texts of up to that many 75-token CLIP windows are chunked, in
-    both passes, instead of cut at 77 tokens; a text that needs more raises ValueError."""
+    both passes, instead of cut at 77 tokens; a text that needs more raises ValueError.
+    The request's seed (`noise_index`) is also the noise seed of a stochastic scheduler, in both passes: they see the same per-step noise."""
     # the request's own choice, else the one the model was built with; passed to every call below, the model is not changed
     chunks = check_max_prompt_chunks(param.get('max_prompt_chunks') or getattr(model, 'max_prompt_chunks', 1))
     if run_dir:
@@ -61,11 +62,11 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         model.reset_attention_maps()
     if model_type == 'SD':
         plain_img = model.produce_attn_maps([base_text_prompt], [negative_text], height=height, width=width,
-                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, max_prompt_chunks=chunks, **start)
+                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
     else:
         plain_img = model.sample([base_text_prompt], negative_prompt=[negative_text], height=height, width=width,
                                  num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], run_rich_text=False,
-                                 latents=latents, max_prompt_chunks=chunks, **start)
+                                 latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
     timings['plain'] = time.time() - t0
 
     t0 = time.time()
@@ -114,12 +115,12 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         rich_img = model.prompt_to_img(region_text_prompts, [negative_text], height=height, width=width,
                                        num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                        use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn,
-                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, max_prompt_chunks=chunks, **start)
+                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
     else:
         rich_img = model.sample(region_text_prompts, negative_prompt=[negative_text], height=height, width=width,
                                 num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                 use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn, text_format_dict=text_format_dict,
-                                inject_background=inject_background, run_rich_text=True, latents=latents, max_prompt_chunks=chunks, **start)
+                                inject_background=inject_background, run_rich_text=True, latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
     timings['rich'] = time.time() - t0
     return plain_img, rich_img, timings
 
@@ -132,11 +133,26 @@ def _load_json_arg(v):
     return json.loads(v)
 
 
+def _request_scheduler(a, name):
+    """A --requests line's "scheduler": checked like the flag (an unknown name or one the model cannot run ends the run).  A line without
+    the key (None) runs on the flag's scheduler; "default" is not a name a line may use (it would be ambiguous between the flag's
+    scheduler and the pipeline's own): leave the key out instead."""
+    if name is None:
+        return None
+    names = [c for c in SCHEDULER_CHOICES if c != 'default']
+    if name not in names:
+        raise SystemExit(f"sample: --requests: unknown scheduler {name!r} (one of {', '.join(names)}; no key = the --scheduler flag's)")
+    order = getattr(a, 'solver_order', None) if name in ('dpmsolver++', 'sde-dpmsolver++') else None
+    make_scheduler(types.SimpleNamespace(scheduler=name, solver_order=order, model=getattr(a, 'model', 'SDXL')))
+    return name
+
+
 def build_requests(a):
     """The (rich-text JSON, seed) list of one invocation.  One JSON + one --seed = the reference's single image.  Several JSONs and / or
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
-    one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "..."} (missing keys: the flags)."""
+    one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
+    (missing keys: the flags; a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -147,7 +163,7 @@ def build_requests(a):
                 r = json.loads(line)
                 js = r["rich_text_json"]
                 reqs.append(dict(text_input=_load_json_arg(js) if isinstance(js, str) else js, seed=int(r.get("seed", a.seed)),
-                                 negative_prompt=r.get("negative_prompt", a.negative_prompt),
+                                 negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
                                  max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1))))))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
@@ -203,15 +219,24 @@ def load_init_image(path, height, width):
     return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous()
 
 
+SCHEDULER_CHOICES = ['default', 'dpmsolver++', 'sde-dpmsolver++', 'euler-ancestral']
+
+
 def make_scheduler(a):
     """--scheduler / --solver_order -> the scheduler object to put on the pipeline (None: the pipeline's default, PNDM for SD and
     Euler for SDXL).  A flag that cannot be honoured is an error, never ignored."""
-    from .schedulers import DPMSolverTables
+    from .schedulers import DPMSolverTables, EulerAncestralTables
     order = getattr(a, 'solver_order', None)
-    if getattr(a, 'scheduler', 'default') == 'dpmsolver++':
-        return DPMSolverTables(solver_order=2 if order is None else order)
+    name = getattr(a, 'scheduler', 'default')
+    if name in ('dpmsolver++', 'sde-dpmsolver++'):
+        return DPMSolverTables(solver_order=2 if order is None else order, algorithm=name)
     if order is not None:
-        raise SystemExit("sample: --solver_order needs --scheduler dpmsolver++")
+        raise SystemExit("sample: --solver_order needs --scheduler dpmsolver++ or sde-dpmsolver++")
+    if name == 'euler-ancestral':
+        if getattr(a, 'model', 'SD') == 'SD':
+            raise SystemExit("sample: --scheduler euler-ancestral runs in sigma space: --model SDXL or AnimeXL only "
+                             "(--model SD: sde-dpmsolver++ is its stochastic sampler)")
+        return EulerAncestralTables()
     return None
 
 
@@ -219,6 +244,17 @@ def apply_scheduler(model, a):
     sched = make_scheduler(a)
     if sched is not None:
         model.scheduler = sched
+    return model
+
+
+def apply_request_scheduler(model, flag_scheduler, r, a):
+    """The scheduler request `r` runs on: the one its --requests line names (with --solver_order where that applies), else
+    `flag_scheduler`, what --scheduler left on the pipeline.  Set for every request, so a line's choice never leaks into the next."""
+    model.scheduler = flag_scheduler
+    name = r.get('scheduler')
+    if name is not None:
+        apply_scheduler(model, types.SimpleNamespace(scheduler=name, model=a.model,
+                                                     solver_order=a.solver_order if name in ('dpmsolver++', 'sde-dpmsolver++') else None))
     return model
 
 
@@ -251,10 +287,13 @@ def build_parser():
                    help='SDXL colour guidance: fp32 = the fp32-class VAE the reference guides with (xl.py:856; default), bf16 = the guidance pass '
                         'alone on a one-pass bf16 VAE engine (same trajectory within the bf16 noise of the UNet, 37 instead of 80 ms per step); '
                         'the final decode stays fp32-class either way')
-    p.add_argument('--scheduler', type=str, default='default', choices=['default', 'dpmsolver++'],
+    p.add_argument('--scheduler', type=str, default='default', choices=SCHEDULER_CHOICES,
                    help='default: the reference\'s sampler (PNDM for SD, Euler for SDXL / AnimeXL); dpmsolver++: DPM-Solver++ multistep '
-                        '(diffusers DPMSolverMultistepScheduler), usually run at 20-25 --sample_steps. Holds on every rank of --gpus N')
-    p.add_argument('--solver_order', type=int, default=None, choices=[1, 2], help='DPM-Solver++ order (default 2); needs --scheduler dpmsolver++')
+                        '(diffusers DPMSolverMultistepScheduler), usually run at 20-25 --sample_steps; sde-dpmsolver++ ("DPM++ 2M SDE") and '
+                        'euler-ancestral ("Euler a", SDXL / AnimeXL only): their stochastic forms, fresh noise at every step, made on the GPU '
+                        'from the request\'s seed. Holds on every rank of --gpus N')
+    p.add_argument('--solver_order', type=int, default=None, choices=[1, 2],
+                   help='DPM-Solver++ order (default 2); needs --scheduler dpmsolver++ or sde-dpmsolver++')
     p.add_argument('--init_image', type=str, default=None,
                    help='edit this image instead of starting from noise: it is resized to height x width, encoded once, and both passes '
                         'start from it at --strength')
@@ -322,7 +361,9 @@ def main(argv=None):
     from PIL import Image
     init_image = load_init_image(a.init_image, a.height or res, a.width or res) if a.init_image else None
     out = []
+    flag_scheduler = model.scheduler
     for r in mine:
+        apply_request_scheduler(model, flag_scheduler, r, a)
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
                  'max_prompt_chunks': r.get('max_prompt_chunks', 1)}
@@ -393,7 +434,7 @@ def _dry_launch(a, rank, world, reqs, mine):
                                  "seeds_mine": [r["seed"] for r in mine], "pipeline_received": ok, "broadcast_collectives": launcher.LAST_BROADCAST_CALLS,
                                  "broadcast_s": seconds,
                                  "scheduler": None if sched is None else {"class": type(sched).__name__, "kind": sched.kind,
-                                                                          "solver_order": sched.solver_order}}) + "\n")
+                                                                          "solver_order": getattr(sched, "solver_order", None)}}) + "\n")
     sys.stdout.flush()
     launcher.barrier()
     if world > 1:

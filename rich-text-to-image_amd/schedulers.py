@@ -3,7 +3,8 @@
 Restates the published diffusers 0.18.2 `PNDMScheduler` (skip_prk_steps=True, steps_offset=1; used at
 models/region_diffusion.py:35-37), `EulerDiscreteScheduler` (SDXL config; models/region_diffusion_sdxl.py:120) and
 `DPMSolverMultistepScheduler` (dpmsolver++, midpoint, epsilon, lower_order_final; imported at models/region_diffusion.py:7, never
-wired in there).
+wired in there), and the two stochastic samplers that share their tables: `EulerAncestralDiscreteScheduler` and
+`DPMSolverMultistepScheduler` with algorithm_type="sde-dpmsolver++" (their noise is made by the engine: Engine.set_noise_seed).
 Only the *tables* live here (timesteps, sigmas, alphas_cumprod); the update arithmetic runs in
 csrc/step.hip.  diffusers is third-party and not on disk => [memory], parity unpinned."""
 import numpy as np
@@ -104,16 +105,29 @@ class EulerTables:
         return self.sigmas.tolist()
 
 
+class EulerAncestralTables(EulerTables):
+    """Euler ancestral ("Euler a"), SDXL family: Euler's timesteps, sigmas and input scaling; each step lands on the level its
+    deterministic parent lands on (sigma_down^2 + sigma_up^2 = sigma_{i+1}^2), so start_level() / source_levels() are inherited."""
+    kind = 4                                                           # RT_SCHED_EULER_A
+
+
 class DPMSolverTables:
     """DPM-Solver++(1M / 2M), either pipeline: `pipe.scheduler = DPMSolverTables()`.  `table()` is alphas_cumprod: the engine derives
-    alpha / sigma / lambda from it and keeps each stream's x0 history itself (rt_set_schedule resets it)."""
+    alpha / sigma / lambda from it and keeps each stream's x0 history itself (rt_set_schedule resets it).
+    algorithm='sde-dpmsolver++': the stochastic variant ("DPM++ 2M SDE") on the same tables, levels and history."""
     init_noise_sigma = 1.0
 
-    def __init__(self, solver_order=2, num_train=1000):
+    def __init__(self, solver_order=2, num_train=1000, algorithm='dpmsolver++'):
         if solver_order not in (1, 2):
             raise ValueError(f"DPMSolverTables: solver_order must be 1 or 2, got {solver_order}")
+        if algorithm not in ('dpmsolver++', 'sde-dpmsolver++'):
+            raise ValueError(f"DPMSolverTables: algorithm must be 'dpmsolver++' or 'sde-dpmsolver++', got {algorithm!r}")
         self.solver_order = solver_order
-        self.kind = 3 if solver_order == 2 else 2                      # RT_SCHED_DPMPP_2 / RT_SCHED_DPMPP_1
+        self.algorithm = algorithm
+        if algorithm == 'dpmsolver++':
+            self.kind = 3 if solver_order == 2 else 2                  # RT_SCHED_DPMPP_2 / RT_SCHED_DPMPP_1
+        else:
+            self.kind = 6 if solver_order == 2 else 5                  # RT_SCHED_DPMPP_SDE_2 / RT_SCHED_DPMPP_SDE_1
         self.num_train = num_train
         self.alphas_cumprod = alphas_cumprod(num_train)
         ac = torch.from_numpy(self.alphas_cumprod)

@@ -1,7 +1,8 @@
-"""The step epilogue alone, Euler against DPM-Solver++(2M), at SDXL's 128 x 128 latents: R = 4 regions with the reference pair stepped
+"""The step epilogue alone, Euler against DPM-Solver++(2M) and the two stochastic samplers (Euler ancestral, SDE-DPM-Solver++(2M): the
+third kernel, one Philox call + two Box-Muller pairs per pixel), at SDXL's 128 x 128 latents: R = 4 regions with the reference pair stepped
 (F = 7 streams, inject_selfattn 0.5), seeded noise predictions in the eps buffer, no UNet.  Meant to run under
-`rocprofv3 --kernel-trace --stats -- python tools/dpm_epilogue_profile.py`: the kernel statistics give step_epilogue_kernel (Euler) and
-step_epilogue_dpm_kernel (DPM-Solver++) their own rows.  Also prints a HIP-event mean per launch."""
+`rocprofv3 --kernel-trace --stats -- python tools/dpm_epilogue_profile.py`: the kernel statistics give step_epilogue_kernel (Euler),
+step_epilogue_dpm_kernel (DPM-Solver++) and step_epilogue_stoch_kernel (both stochastic samplers) their own rows.  Also prints a HIP-event mean per launch."""
 import os
 import sys
 
@@ -14,7 +15,7 @@ def main(hw=128, R=4, steps=50, reps=4):
     from oracle.unet import TINY_SD_CONFIG
     from rich_text_to_image_amd.engine import Engine
     from rich_text_to_image_amd.launcher import eps_tensor
-    from rich_text_to_image_amd.schedulers import DPMSolverTables, EulerTables
+    from rich_text_to_image_amd.schedulers import DPMSolverTables, EulerAncestralTables, EulerTables
     dev = "cuda:0"
     e = Engine(TINY_SD_CONFIG, hw, hw, device=0, max_streams=8, max_prompts=8)
     e.arena_mark_bound()                                        # the UNet never runs here
@@ -27,9 +28,11 @@ def main(hw=128, R=4, steps=50, reps=4):
     buf.view(torch.float32)[:(per // 4) * (R + 3)].copy_(torch.randn((per // 4) * (R + 3), generator=g).to(dev))
     out = {}
     for rep in range(reps):
-        for name, s in (("euler", EulerTables()), ("dpmsolver++", DPMSolverTables())):
+        for name, s in (("euler", EulerTables()), ("dpmsolver++", DPMSolverTables()), ("euler-ancestral", EulerAncestralTables()),
+                        ("sde-dpmsolver++", DPMSolverTables(algorithm="sde-dpmsolver++"))):
             s.set_timesteps(steps)
             e.set_schedule(s.kind, s.timesteps.tolist(), s.table(), steps)
+            e.set_noise_seed(rep)
             e.set_latents(lat0)
             e.synchronize()
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
