@@ -109,6 +109,20 @@ int rt_set_schedule(rt_engine* e, int kind, const float* timesteps_host, int n_t
  * 0, 0), one call per pixel = its four channels).  Engine state, default 0; survives rt_set_schedule and rt_set_latents; the three
  * deterministic kinds ignore it.  The same seed gives the same field on every rank, in the plain pass and in both streams of a rich step. */
 int rt_set_noise_seed(rt_engine* e, unsigned long long seed);
+/* What the UNet predicts and how the guidance is rescaled (no counterpart call in the reference: `guidance_rescale` is an argument of
+ * sample(), xl.py:42-53, :903-905; v-prediction is the checkpoint's scheduler_config.json).  prediction_type RT_PRED_EPSILON (0) or
+ * RT_PRED_V (1); guidance_rescale = phi in [0, 1].  Engine state, default (0, 0); survives rt_set_schedule and rt_set_latents; other values
+ * are RT_E_INVALID and leave the state alone.  With (0, 0) a step launches exactly what it launched before this call existed.  Otherwise
+ * rt_region_step / rt_*_step_finish / rt_plain_step run the two launches of csrc/guided.hip before the unchanged epilogue:
+ *   cfg  = the mask-composed, guided prediction (the pair: its own CFG),   text = its conditional half
+ *   f    = phi std(text) / std(cfg) + (1 - phi)     std over all 4 h w values, unbiased, fp64 sums in a fixed order, f rounded to fp32 once;
+ *                                                   the main stream and the reference pair each use their own two series
+ *   m    = cfg f                                    (phi > 0)
+ *   eps  = cv m + cx x                              (v; x = the stream's unscaled latents; sigma space: cv = 1 / sqrt(sigma^2 + 1),
+ *                                                   cx = sigma / (sigma^2 + 1); VP: cv = sqrt(ac_t), cx = sqrt(1 - ac_t))
+ * and the scheduler update, its history and the noise_pred of rt_get_state_ptrs see eps.  Every rank of a split step computes the same bits. */
+enum { RT_PRED_EPSILON = 0, RT_PRED_V = 1 };
+int rt_set_prediction(rt_engine* e, int prediction_type, float guidance_rescale);
 /* sampler state: latents [1,4,h,w] f32 (copied in); the reference stream starts as a clone (rd.py:93, xl.py:774) */
 int rt_set_latents(rt_engine* e, const float* latents, int h, int w);
 int rt_get_latents(rt_engine* e, float* latents_out, float* latents_ref_out /* may be NULL */);
@@ -302,6 +316,15 @@ int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream);
  * epilogue: out_dev [4, h, w] f32 normals; words_dev [h*w, 4] the raw Philox words of every pixel, or NULL. */
 int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev /* [4,h,w] */, unsigned int* words_dev /* [h*w,4] or NULL */,
                      void* stream);
+/* The pre-pass of rt_set_prediction alone, on caller buffers: eps [F, h*w, 4] f32 (the layout of rt_eps_info), masks [R, 4, h*w] (rich mode),
+ * lat / lat_ref [4, h*w] (read only for v-prediction; lat_ref may be NULL without a pair), the stream indices as the step plans them
+ * (s_uref < 0: no pair; s_region_host [R - 1], host), `plain`: 1 = eps[s_uncond] + g (eps[s_base] - eps[s_uncond]) without masks, `step_ref`:
+ * the pair is stepped.  Outputs: gpred_dev [2][h*w][4] (slot 1 only written when the pair is stepped), factors_dev [2] f32 (1 for the main
+ * stream when phi == 0; 0 for the pair when it is not stepped); partials_dev: scratch of ceil(h*w / 256) * 8 doubles (may be NULL when
+ * phi == 0). */
+int rt_op_guided_prediction(const float* eps, const float* masks, const float* lat, const float* lat_ref, int h, int w, int R, int s_uncond,
+                            int s_base, int s_uref, int s_tref, const int* s_region_host, float g, int plain, int step_ref, float phi,
+                            int prediction_type, float cv, float cx, float* gpred_dev, double* partials_dev, float* factors_dev, void* stream);
 /* ---- CLIP text encoder pieces (transformers' CLIPTextModel[WithProjection] as called at rd.py:53-66, xl.py:330-356); the linear layers
  * and LayerNorms are rt_op_gemm / rt_op_layernorm.  ids [rows] int32 (device), tok [vocab, C], pos [N, C] fp32 -> out [rows, C] fp32 */
 int rt_op_embed(const int* ids, const float* tok, const float* pos, float* out, int rows, int N, int C, int vocab, void* stream);

@@ -215,6 +215,20 @@ def load_vae_encoder(vae_dir, kind="SD", device=0, latent_hw=None, precise=False
     return VaeEncoder(cfg, hw[0], hw[1], device=device, state_dict=sd, precise=precise)
 
 
+def scheduler_prediction_type(load_path):
+    """The `prediction_type` of `load_path`/scheduler/scheduler_config.json: 'epsilon' or 'v_prediction'; None when the file or the key is
+    absent (the pipelines then default to epsilon).  Only that key is read - which sampler runs stays the caller's choice; any other
+    value ('sample', ...) is a ValueError."""
+    f = os.path.join(load_path, "scheduler", "scheduler_config.json")
+    if not os.path.exists(f):
+        return None
+    v = json.load(open(f)).get("prediction_type")
+    if v is None:
+        return None
+    from .schedulers import check_prediction_type
+    return check_prediction_type(v, "scheduler/scheduler_config.json: prediction_type")
+
+
 def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=None, lora_scale=1.0, weights=True):
     """Everything the facade constructors need from a diffusers-layout directory (unet/, vae/, tokenizer[_2]/, text_encoder[_2]/) as
     keyword arguments of RegionDiffusion / RegionDiffusionXL.  `latent_hw` sizes the VAE plan (default: the model's native size).
@@ -230,6 +244,7 @@ def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=No
         from .lora import merge_lora
         unet_sd, _ = merge_lora(unet_sd, load_file(lora_path), lora_scale)
     unet_cfg = unet_config(os.path.join(load_path, "unet"), SD15_CONFIG if kind == "SD" else SDXL_CONFIG)
+    ptype = scheduler_prediction_type(load_path)
     vae_cfg = vae_config(os.path.join(load_path, "vae"), SD_VAE_CONFIG if kind == "SD" else SDXL_VAE_CONFIG)
     hw = latent_hw or ((64, 64) if kind == "SD" else (128, 128))
     vae = VaeDecoder(vae_cfg, hw[0], hw[1], device=device, state_dict=vae_sd, precise=(kind == "SDXL"))   # xl.py:856 / :918-938: fp32 VAE
@@ -238,7 +253,7 @@ def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=No
         enc = load_text_encoder(os.path.join(load_path, "text_encoder"), device, weights=weights)
         # vae_dir: RegionDiffusion.encode_imgs builds its VaeEncoder from it on first use (load_vae_encoder)
         return dict(unet_state_dict=unet_sd, config=unet_cfg, vae=vae, tokenizer=tok, text_encoder=ClipEncoderSD(enc, dev),
-                    vae_dir=os.path.join(load_path, "vae"))
+                    vae_dir=os.path.join(load_path, "vae"), prediction_type=ptype)
     tok2 = ClipBPETokenizer.from_pretrained(load_path, "tokenizer_2")
     enc1 = load_text_encoder(os.path.join(load_path, "text_encoder"), device, weights=weights)
     enc2 = load_text_encoder(os.path.join(load_path, "text_encoder_2"), device, with_projection=True, weights=weights)
@@ -247,7 +262,8 @@ def load_components(load_path, kind="SD", device=0, latent_hw=None, lora_path=No
     if os.path.exists(mi):
         fz = json.load(open(mi)).get("force_zeros_for_empty_prompt", True)
     return dict(unet_state_dict=unet_sd, config=unet_cfg, vae=vae, tokenizer=tok, vae_scaling_factor=vae_cfg["scaling_factor"],
-                text_encoders=ClipEncodersXL([tok, tok2], [enc1, enc2], dev, fz), vae_dir=os.path.join(load_path, "vae"))
+                text_encoders=ClipEncodersXL([tok, tok2], [enc1, enc2], dev, fz), vae_dir=os.path.join(load_path, "vae"),
+                prediction_type=ptype)
 
 
 def load_pipeline(load_path, kind="SD", device=0, latent_hw=None, lora_path=None, lora_scale=1.0):

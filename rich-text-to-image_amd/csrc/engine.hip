@@ -156,6 +156,7 @@ void launch_noise_latents(float* lat, float* lat_ref, const float* x0, const flo
 void launch_source_blend(float* lat, const float* x0, const float* noise, const float* keep, float a, float b, int HW, hipStream_t st);
 
 #include "step.h"
+#include "guided.h"
 
 // Cross-attention of a launch whose streams have DIFFERENT key counts (prompts of one to three 77-token windows), where the shape has
 // cross77_kernel: the kernel of a stream is a function of its OWN key count - maximal runs of 77-key streams go to cross77_kernel, the
@@ -238,6 +239,13 @@ struct rt_engine {
     int pndm_counter = 0, pndm_nets = 0, pndm_head = 0;
     int dpm_lower_order_nums = 0, dpm_head = 0;     // DPM-Solver++: steps taken (capped at 2), history slot this step writes
     int steps_done = 0;
+    // rt_set_prediction: what the UNet predicts (0 epsilon, 1 v) and the CFG rescale phi; (0, 0) launches nothing new.  Survive rt_set_schedule / rt_set_latents.
+    int prediction_type = 0;
+    float guidance_rescale = 0.f;
+    float* gpred = nullptr;          // [2][HW][4] guided prediction of the main stream / the reference pair
+    double* gpartials = nullptr;     // [cdiv(HW, 256)][8]
+    float* gfactors = nullptr;       // [2]
+    void guided_prepass(int i, StepArgs& a);
     unsigned long long noise_seed = 0;              // stochastic samplers: key of the per-step noise field (rt_set_noise_seed); survives rt_set_schedule / rt_set_latents
 
     // optional per-launch HIP-event profiling of the MFMA kernels (bench.py roofline leg)
@@ -458,6 +466,10 @@ struct rt_engine {
         eps = (float*)sarena.alloc((size_t)cfg.max_streams * HW * 4 * 4);
         ets = (float*)sarena.alloc((size_t)4 * 2 * 4 * HW * 4);
         cur_sample = (float*)sarena.alloc((size_t)2 * 4 * HW * 4);
+        // guided-prediction pre-pass (guided.hip): behind everything else, so the buffers above keep their offsets
+        gpred = (float*)sarena.alloc((size_t)2 * HW * 4 * 4);
+        gpartials = (double*)sarena.alloc((size_t)cdiv((int)HW, 256) * RT_GUIDED_SERIES * 8);
+        gfactors = (float*)sarena.alloc(2 * 4);
     }
 
     // ---------------------------------------------------------------------------- launch helpers
@@ -1249,6 +1261,13 @@ int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
     })
 }
 int rt_set_noise_seed(rt_engine* e, unsigned long long seed) { RT_TRY(e, { e->noise_seed = seed; }) }
+int rt_set_prediction(rt_engine* e, int prediction_type, float guidance_rescale) {
+    RT_TRY(e, {
+        RT_REQUIRE(prediction_type == RT_PRED_EPSILON || prediction_type == RT_PRED_V, "rt_set_prediction: prediction_type must be 0 (epsilon) or 1 (v)");
+        RT_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "rt_set_prediction: guidance_rescale must be in [0, 1]");
+        e->prediction_type = prediction_type; e->guidance_rescale = guidance_rescale;
+    })
+}
 int rt_set_source(rt_engine* e, const float* x0, const float* noise, const float* keep, int h, int w) {
     RT_TRY(e, {
         need_device(e);
@@ -1764,6 +1783,23 @@ int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out
     OP_TRY({
         RT_REQUIRE(out_dev && step >= 0 && h >= 1 && w >= 1 && (long long)h * w <= (1ll << 30), "rt_op_step_noise: bad arguments");
         launch_step_noise(seed, step, h * w, out_dev, words_dev, (hipStream_t)stream);
+    })
+}
+int rt_op_guided_prediction(const float* eps, const float* masks, const float* lat, const float* lat_ref, int h, int w, int R, int s_uncond,
+                            int s_base, int s_uref, int s_tref, const int* s_region_host, float g, int plain, int step_ref, float phi,
+                            int prediction_type, float cv, float cx, float* gpred_dev, double* partials_dev, float* factors_dev, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(eps && lat && gpred_dev && factors_dev && h >= 1 && w >= 1 && (long long)h * w <= (1ll << 26), "rt_op_guided_prediction: bad arguments");
+        RT_REQUIRE(prediction_type == RT_PRED_EPSILON || prediction_type == RT_PRED_V, "rt_op_guided_prediction: prediction_type must be 0 or 1");
+        RT_REQUIRE(phi >= 0.f && phi <= 1.f && (phi == 0.f || partials_dev), "rt_op_guided_prediction: phi in [0, 1], with the partials scratch when > 0");
+        RT_REQUIRE(plain || (masks && R >= 1 && R <= RT_MAXB && (R == 1 || s_region_host)), "rt_op_guided_prediction: rich mode needs masks and the region streams");
+        RT_REQUIRE(s_uncond >= 0 && s_base >= 0 && (s_uref < 0 || (s_tref >= 0 && lat_ref)), "rt_op_guided_prediction: stream indices");
+        GuidedArgs q{};
+        q.s.eps = eps; q.s.masks = masks; q.s.lat = const_cast<float*>(lat); q.s.lat_ref = const_cast<float*>(lat_ref); q.s.HW = h * w; q.s.R = plain ? 0 : R;
+        q.s.s_uncond = s_uncond; q.s.s_base = s_base; q.s.s_uref = s_uref; q.s.s_tref = s_tref; q.s.g = g; q.s.plain = plain ? 1 : 0; q.s.step_ref = step_ref ? 1 : 0;
+        if (!plain) for (int r = 0; r < R - 1; ++r) { RT_REQUIRE(s_region_host[r] >= 0, "rt_op_guided_prediction: region stream"); q.s.s_region[r] = s_region_host[r]; }
+        q.gpred = gpred_dev; q.partials = partials_dev; q.factors = factors_dev; q.phi = phi; q.vpred = prediction_type == RT_PRED_V; q.cv = cv; q.cx = cx;
+        launch_guided_prediction(q, (hipStream_t)stream);
     })
 }
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream) {

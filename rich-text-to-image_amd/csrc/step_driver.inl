@@ -171,10 +171,39 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     inject_out = feat && run_ref;
 }
 
+// The guided-prediction pre-pass (guided.hip) of step i, when the model predicts v or the guidance is rescaled: composes the guided
+// prediction of the main stream and of the stepped reference pair into `gpred`, rescales it, converts v to the epsilon-equivalent at the
+// point where the UNet was evaluated, and re-aims the epilogue's arguments at `gpred` as a plain two-stream buffer whose unconditional
+// and text slots coincide (E + g (E - E) = E).  R, masks, blend, step_ref and noise_pred stay as planned.  fp32 scalars, left to right:
+//   sigma space (Euler, Euler ancestral):          cv = 1 / sqrt(sigma_i^2 + 1),  cx = sigma_i / (sigma_i^2 + 1)
+//   VP (PNDM, DPM-Solver++, SDE-DPM-Solver++):      cv = sqrt(ac_t),  cx = sqrt(1 - ac_t),  t = timesteps[i] (PNDM's repeated one as listed)
+// [memory] diffusers' PNDM converts v after the multistep combination, with the current sample; here the history holds
+// epsilon-equivalents - the epsilon-model the v-model defines - so the five solvers stay untouched.
+void rt_engine::guided_prepass(int i, StepArgs& a) {
+    GuidedArgs q{};
+    q.s = a; q.gpred = gpred; q.partials = gpartials; q.factors = gfactors;
+    q.phi = guidance_rescale; q.vpred = prediction_type == RT_PRED_V ? 1 : 0;
+    if (q.vpred) {
+        if (rt_sched_is_euler(sched_kind)) {
+            const float sg = table[i];
+            q.cv = 1.f / std::sqrt(sg * sg + 1.f); q.cx = sg / (sg * sg + 1.f);
+        } else {
+            RT_REQUIRE((int)table.size() >= 1000, "v-prediction: alphas_cumprod table missing");
+            const int t = (int)timesteps[i];
+            RT_REQUIRE(t >= 0 && t < (int)table.size(), "v-prediction: timestep outside the table");
+            q.cv = std::sqrt(table[t]); q.cx = std::sqrt(1.f - table[t]);
+        }
+    }
+    launch_guided_prediction(q, stream);
+    const bool has_ref = a.s_uref >= 0 && a.step_ref;
+    a.eps = gpred; a.plain = 1; a.s_uncond = a.s_base = 0; a.s_uref = a.s_tref = has_ref ? 1 : -1;
+}
+
 // mask combine + CFG + scheduler step + blend on the eps of ALL streams of step i (models/region_diffusion.py:119-147,
 // region_diffusion_sdxl.py:810-846)
 void rt_engine::region_finish(int i, StepArgs& a, bool blend_deferred) {
     pending_blend = blend_deferred;
+    if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
     if (rt_sched_is_stoch(sched_kind)) {
         StochArgs d{};
         stoch_coeffs(this, i, a, d);
@@ -274,6 +303,7 @@ void rt_engine::plain_finish(int i, float g) {
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
     a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.sched = sched_kind; a.step_ref = 0; a.blend = 0;
+    if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
     if (rt_sched_is_stoch(sched_kind)) {
         StochArgs d{};
         stoch_coeffs(this, i, a, d);

@@ -10,6 +10,8 @@ RT_MAX_LEVELS = 4
 RT_MAX_STREAMS = 16
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
 SCHED_EULER, SCHED_PNDM = 0, 1
+PRED_EPSILON, PRED_V = 0, 1
+PREDICTION_TYPES = {"epsilon": PRED_EPSILON, "v_prediction": PRED_V}
 A_DENSE, A_CONV3, A_CONV3_S2, A_CONV3_UP2, A_CONV3_S2P0 = 0, 1, 2, 3, 4
 EPI_BF16, EPI_F32, EPI_BF16_TEMB, EPI_GEGLU, EPI_F16 = 0, 1, 2, 3, 4
 
@@ -79,6 +81,7 @@ _SYMBOLS = [
     "rt_op_gemm_debug2", "rt_op_pack_upconv", "rt_op_upconv",
     "rt_set_prompts_keys", "rt_op_attention_keys",
     "rt_set_noise_seed", "rt_op_step_noise",
+    "rt_set_prediction", "rt_op_guided_prediction",
 ]
 
 
@@ -297,6 +300,16 @@ class Engine:
         set_schedule / set_latents, and the deterministic kinds ignore it."""
         self._chk(self.lib.rt_set_noise_seed(self.h, C.c_uint64(int(seed or 0) & 0xFFFFFFFFFFFFFFFF)))
 
+    def set_prediction(self, prediction_type=PRED_EPSILON, guidance_rescale=0.0):
+        """What the UNet predicts (0 / 'epsilon', 1 / 'v_prediction') and the CFG rescale phi in [0, 1].  Engine state, default (0, 0),
+        under which a step launches what it always launched; otherwise the two launches of csrc/guided.hip run before the step epilogue
+        (include/rtdiff.h: rt_set_prediction).  Survives set_schedule / set_latents; a bad value raises and changes nothing."""
+        if isinstance(prediction_type, str):
+            if prediction_type not in PREDICTION_TYPES:
+                raise ValueError(f"prediction_type must be one of {sorted(PREDICTION_TYPES)}, got {prediction_type!r}")
+            prediction_type = PREDICTION_TYPES[prediction_type]
+        self._chk(self.lib.rt_set_prediction(self.h, int(prediction_type), C.c_float(float(guidance_rescale))))
+
     def set_latents(self, latents):
         l = latents.contiguous().float()
         assert l.shape[0] == 1 and l.shape[1] == 4
@@ -456,6 +469,40 @@ def step_noise(seed, step, h, w, words=False, device=0):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return (out, wd.to(torch.int64) & 0xFFFFFFFF) if words else out
+
+
+def guided_prediction(eps, lat, g, s_uncond=0, s_base=1, masks=None, lat_ref=None, s_uref=-1, s_tref=-1, s_region=(), plain=True,
+                      step_ref=False, guidance_rescale=0.0, prediction_type=PRED_EPSILON, cv=1.0, cx=0.0):
+    """The guided-prediction pre-pass alone (rt_op_guided_prediction), on the caller's tensors: eps [F, h*w, 4] fp32 (the layout of the
+    engine's eps buffer), lat / lat_ref [1, 4, h, w], masks [R, 4, h, w] (rich mode) -> (gpred [2, h*w, 4], factors [2]) on the GPU.
+    Slot 1 of gpred is only written when the reference pair is stepped (s_uref >= 0 and step_ref)."""
+    import torch
+    lib = load_library()
+    dev = eps.device
+    h, w = lat.shape[-2], lat.shape[-1]
+    eps, lat = eps.contiguous().float(), lat.contiguous().float()
+    assert eps.dim() == 3 and tuple(eps.shape[1:]) == (h * w, 4), tuple(eps.shape)
+    assert max(s_uncond, s_base, s_uref, s_tref, *s_region) < eps.shape[0], "a stream index lies outside eps"
+    lat_ref = lat_ref.contiguous().float() if lat_ref is not None else None
+    R = 0
+    if not plain:
+        masks = masks.contiguous().float()
+        R = masks.shape[0]
+        assert tuple(masks.shape) == (R, 4, h, w) and len(s_region) == R - 1, (tuple(masks.shape), len(s_region))
+    with torch.cuda.device(dev):
+        gpred = torch.full((2, h * w, 4), float("nan"), device=dev)
+        factors = torch.empty(2, device=dev)
+        partials = torch.empty(-(-h * w // 256) * 8, dtype=torch.float64, device=dev)
+        reg = (C.c_int * max(1, len(s_region)))(*[int(v) for v in s_region])
+        rc = lib.rt_op_guided_prediction(_ptr(eps), _ptr(masks if not plain else None), _ptr(lat), _ptr(lat_ref), int(h), int(w), int(R),
+                                         int(s_uncond), int(s_base), int(s_uref), int(s_tref), reg, C.c_float(float(g)), int(bool(plain)),
+                                         int(bool(step_ref)), C.c_float(float(guidance_rescale)), int(prediction_type), C.c_float(float(cv)),
+                                         C.c_float(float(cx)), _ptr(gpred), _ptr(partials), _ptr(factors),
+                                         C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return gpred, factors
 
 
 # ------------------------------------------------------------------------------------------------ VAE decoder

@@ -4,14 +4,19 @@ import torch
 
 from . import img2img
 from .engine import SD15_CONFIG
-from .schedulers import DPMSolverTables, PNDMTables
+from .schedulers import DPMSolverTables, PNDMTables, engine_prediction
 from .unet import HipUNet2DConditionModel
 
 
 class RegionDiffusion:
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
-                 latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None, max_prompt_chunks=1):
-        """`RegionDiffusion(device)` as sample.py:26-27 calls it: the reference loads runwayml/stable-diffusion-v1-5 there
+                 latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None, max_prompt_chunks=1, guidance_rescale=0.0,
+                 prediction_type=None):
+        """`guidance_rescale` (pipeline attribute, default 0): the CFG rescale (rescale_noise_cfg of the SDXL reference pipeline) of every
+        sampling call whose own `guidance_rescale` is 0.  `prediction_type` ('epsilon' / 'v_prediction'; None = what `load_path`'s
+        scheduler/scheduler_config.json says, else epsilon): the parameterisation of the default scheduler; a scheduler passed in or
+        assigned later carries its own `prediction_type`.
+        `RegionDiffusion(device)` as sample.py:26-27 calls it: the reference loads runwayml/stable-diffusion-v1-5 there
         (rd.py:26-33); here the same id is resolved to a local diffusers-layout directory (checkpoint.resolve_checkpoint:
         `load_path` directory / $RTDIFF_SD_PATH / the Hugging Face hub cache) and UNet, VAE decoder, tokenizer and text encoder are
         loaded from it.  Callers that hold the weights already pass `unet_state_dict` (reference key names) and, optionally, VAE /
@@ -32,11 +37,13 @@ class RegionDiffusion:
             unet_state_dict, config = comp["unet_state_dict"], config or comp["config"]
             vae, tokenizer, text_encoder = vae or comp["vae"], tokenizer or comp["tokenizer"], text_encoder or comp["text_encoder"]
             vae_dir = vae_dir or comp["vae_dir"]
+            prediction_type = prediction_type or comp.get("prediction_type")
+        self.guidance_rescale = float(guidance_rescale)
         self.vae, self.tokenizer, self.text_encoder = vae, tokenizer, text_encoder
         self.vae_dir, self.vae_encoder = vae_dir, vae_encoder
         self._lazy_encoder = None                  # (encoder built from vae_dir, or None: no encoder weights there)
         self.unet = HipUNet2DConditionModel(config or SD15_CONFIG, unet_state_dict, self.device_index)
-        self.scheduler = scheduler if scheduler is not None else PNDMTables(self.num_train_timesteps)          # rd.py:35-36
+        self.scheduler = scheduler if scheduler is not None else PNDMTables(self.num_train_timesteps, prediction_type=prediction_type or 'epsilon')          # rd.py:35-36
         self.alphas_cumprod = torch.tensor(self.scheduler.alphas_cumprod)
         self.masks = []
         self.attention_maps = None
@@ -131,8 +138,10 @@ class RegionDiffusion:
     def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                         latents=None, use_guidance=False, text_format_dict={}, inject_selfattn=0, inject_background=0,
                         elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None, key_counts=None,
-                        noise_seed=None):
-        """`noise_seed`: seed of the per-step noise of a stochastic scheduler (DPMSolverTables(algorithm='sde-dpmsolver++')); None = 0;
+                        noise_seed=None, guidance_rescale=0.0):
+        """`guidance_rescale`: CFG rescale of the composed prediction (and, with its own factor, of the reference pair); 0 = the
+        pipeline attribute `guidance_rescale`; applied only when guidance_scale > 1.
+        `noise_seed`: seed of the per-step noise of a stochastic scheduler (DPMSolverTables(algorithm='sde-dpmsolver++')); None = 0;
         a deterministic scheduler ignores it.  The plain pass of the same seed sees the same noise at every step.
         `image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
         `strength` of the schedule and pin the pixels of `keep_source` to the image at every step.  image=None: the reference's
@@ -163,6 +172,7 @@ class RegionDiffusion:
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
+        eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
         levels = self._start(eng, latents, None if image is None else x0, keep)
         for i, t in enumerate(self.scheduler.timesteps):
             if getattr(self, "split_image", False):      # intra-image split over the ranks of the process group (launcher.split_region_step)
@@ -223,18 +233,19 @@ class RegionDiffusion:
 
     # rd.py:180-225 (plain pass; attention-map capture = SURVEY 8a row a10, next)
     def produce_attn_maps(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50,
-                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None, max_prompt_chunks=None, noise_seed=None):
+                          guidance_scale=7.5, latents=None, image=None, strength=0.8, noise=None, max_prompt_chunks=None, noise_seed=None,
+                          guidance_rescale=0.0):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts]
         emb = self.get_text_embeds(prompts, negative_prompts, max_prompt_chunks)
         lat = self.plain_latents(emb, height, width, num_inference_steps, guidance_scale, latents, image=image, strength=strength, noise=noise,
-                                 noise_seed=noise_seed)
+                                 noise_seed=noise_seed, guidance_rescale=guidance_rescale)
         return self.latents_to_uint8(lat)
 
     def plain_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
-                      image=None, strength=0.8, noise=None, key_counts=None, noise_seed=None):
+                      image=None, strength=0.8, noise=None, key_counts=None, noise_seed=None, guidance_rescale=0.0):
         if isinstance(text_embeddings, tuple):                              # get_text_embeds(max_prompt_chunks > 1): (embeddings, key counts)
             text_embeddings, key_counts = text_embeddings
         img2img.check_start(image, latents)
@@ -252,6 +263,7 @@ class RegionDiffusion:
         eng.set_prompts(text_embeddings.to(self.device), key_counts=key_counts)
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
+        eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
         self._start(eng, latents, None if image is None else img2img.source_latents(self, image), None)
         if hooks:
             self._store_begin(eng)
@@ -282,7 +294,7 @@ class RegionDiffusion:
     # rd.py:248-273
     def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
                       latents=None, text_format_dict={}, use_guidance=False, inject_selfattn=0, inject_background=0,
-                      image=None, strength=0.8, noise=None, keep_source=None, max_prompt_chunks=None, noise_seed=None):
+                      image=None, strength=0.8, noise=None, keep_source=None, max_prompt_chunks=None, noise_seed=None, guidance_rescale=0.0):
         if isinstance(prompts, str):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
@@ -292,7 +304,8 @@ class RegionDiffusion:
                                        num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
                                        use_guidance=use_guidance, text_format_dict=text_format_dict,
                                        inject_selfattn=inject_selfattn, inject_background=inject_background,
-                                       image=image, strength=strength, noise=noise, keep_source=keep_source, noise_seed=noise_seed)
+                                       image=image, strength=strength, noise=noise, keep_source=keep_source, noise_seed=noise_seed,
+                                       guidance_rescale=guidance_rescale)
         return self.latents_to_uint8(latents)
 
     # hook surface of the reference (rd.py:397-443): token-map capture is the "next" row f1

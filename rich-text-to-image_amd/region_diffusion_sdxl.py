@@ -6,7 +6,7 @@ import torch
 
 from . import img2img
 from .engine import SDXL_CONFIG
-from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables
+from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables, engine_prediction
 from .unet import HipUNet2DConditionModel
 
 
@@ -19,8 +19,12 @@ class StableDiffusionXLPipelineOutput(dict):
 class RegionDiffusionXL:
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
                  vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None,
-                 max_prompt_chunks=1):
-        """`RegionDiffusionXL(load_path="stabilityai/stable-diffusion-xl-base-1.0")` as sample.py:28-30 calls it (xl.py:105-120
+                 max_prompt_chunks=1, guidance_rescale=0.0, prediction_type=None):
+        """`guidance_rescale` (pipeline attribute, default 0): the CFG rescale of both passes when the call's own `guidance_rescale` is 0 -
+        the only way to rescale the rich pass, whose call keyword the reference refuses (xl.py:827-830).  `prediction_type` ('epsilon' /
+        'v_prediction'; None = what `load_path`'s scheduler/scheduler_config.json says, else epsilon): the parameterisation of the
+        default scheduler; a scheduler passed in or assigned later carries its own `prediction_type`.
+        `RegionDiffusionXL(load_path="stabilityai/stable-diffusion-xl-base-1.0")` as sample.py:28-30 calls it (xl.py:105-120
         loads every component from `load_path`): a diffusers-layout directory, or a hub id resolved to one without a network
         (checkpoint.resolve_checkpoint: $RTDIFF_SDXL_PATH for the default id, then the Hugging Face hub cache).  Callers that hold
         the weights pass `unet_state_dict` (+ optional vae / text_encoders / tokenizer) and `load_path` is not read.
@@ -37,6 +41,8 @@ class RegionDiffusionXL:
             vae, text_encoders, tokenizer = vae or comp["vae"], text_encoders or comp["text_encoders"], tokenizer or comp["tokenizer"]
             vae_scaling_factor = comp["vae_scaling_factor"]
             vae_dir = vae_dir or comp.get("vae_dir")
+            prediction_type = prediction_type or comp.get("prediction_type")
+        self.guidance_rescale = float(guidance_rescale)
         self.unet = HipUNet2DConditionModel(config or SDXL_CONFIG, unet_state_dict, self.device_index)
         self.vae = vae
         self.vae_dir, self.vae_encoder = vae_dir, vae_encoder
@@ -50,7 +56,7 @@ class RegionDiffusionXL:
         self.vae_scaling_factor = vae_scaling_factor
         self.vae_scale_factor = 8
         self.default_sample_size = 128
-        self.scheduler = scheduler if scheduler is not None else EulerTables()
+        self.scheduler = scheduler if scheduler is not None else EulerTables(prediction_type=prediction_type or 'epsilon')
         self.masks = []
         self.selfattn_maps = self.crossattn_maps = self.n_maps = None
         self.attention_maps = None                                   # xl.py:132 (only the evaluation hooks ever set it)
@@ -121,7 +127,12 @@ class RegionDiffusionXL:
                target_size=None, use_guidance=False, inject_selfattn=0, inject_background=0, text_format_dict=None,
                run_rich_text=False, elide_dead_forwards=False, image=None, strength=0.8, noise=None, keep_source=None,
                max_prompt_chunks=None, prompt_key_counts=None, negative_key_counts=None, noise_seed=None):
-        """`noise_seed`: seed of the per-step noise of a stochastic scheduler (EulerAncestralTables, DPMSolverTables(algorithm=
+        """`guidance_rescale` (xl.py:42-53, :903-905): the plain pass rescales the guided prediction towards the standard deviation of
+        its conditional half; 0 falls back to the pipeline attribute `guidance_rescale`, which also rescales the rich pass (the mask-
+        composed prediction against the composed conditional half, the reference pair against its own: xl.py:827-830's commented
+        line).  With run_rich_text=True the keyword > 0 raises NotImplementedError, as in the reference.  Applied only when
+        guidance_scale > 1.  A v-prediction model is run by a scheduler whose `prediction_type` is 'v_prediction'.
+        `noise_seed`: seed of the per-step noise of a stochastic scheduler (EulerAncestralTables, DPMSolverTables(algorithm=
         'sde-dpmsolver++')); None = 0; a deterministic scheduler ignores it.  The plain pass (run_rich_text=False) of the same seed sees
         the same noise at every step.
         `image` / `strength` / `noise` / `keep_source` (img2img.py): start from an existing image instead of noise, run the last
@@ -151,6 +162,7 @@ class RegionDiffusionXL:
             raise RuntimeError("use_guidance=True needs a rich_text_to_image_amd.engine.VaeDecoder as `vae` (xl.py:849-867)")
         if not isinstance(self.scheduler, (EulerTables, EulerAncestralTables, DPMSolverTables)):
             raise ValueError(f"RegionDiffusionXL: scheduler must be EulerTables, EulerAncestralTables or DPMSolverTables, got {type(self.scheduler).__name__}")
+        prediction = engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale)
         img2img.check_start(image, latents)
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         if image is None:
@@ -183,6 +195,7 @@ class RegionDiffusionXL:
         eng.set_prompts(embeds, pooled, add_time_ids, key_counts=key_counts)
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
+        eng.set_prediction(*prediction)
         if image is None:
             eng.set_latents(latents)
         else:

@@ -34,7 +34,10 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     ("background" or a mask, img2img.py) pins those pixels of the rich pass to the image.
     `param['max_prompt_chunks']` (optional: 1, 2 or 3; default: the model's own `max_prompt_chunks`): texts of up to that many 75-token CLIP windows are chunked, in
     both passes, instead of cut at 77 tokens; a text that needs more raises ValueError.
-    The request's seed (`noise_index`) is also the noise seed of a stochastic scheduler, in both passes: they see the same per-step noise."""
+    The request's seed (`noise_index`) is also the noise seed of a stochastic scheduler, in both passes: they see the same per-step noise.
+    `param['guidance_rescale']` (optional): the CFG rescale of both passes, handed to the sampling calls as their `guidance_rescale`
+    keyword; the SDXL rich pass, whose keyword the reference refuses, takes it as the pipeline attribute, set around that one call and
+    restored after it."""
     # the request's own choice, else the one the model was built with; passed to every call below, the model is not changed
     chunks = check_max_prompt_chunks(param.get('max_prompt_chunks') or getattr(model, 'max_prompt_chunks', 1))
     if run_dir:
@@ -50,6 +53,8 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     timings = {}
 
     seed_everything(seed)
+    phi = param.get('guidance_rescale')
+    rescale = {} if phi is None else {'guidance_rescale': float(phi)}
     start = {}
     if init_image is not None:
         from . import img2img
@@ -62,11 +67,11 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         model.reset_attention_maps()
     if model_type == 'SD':
         plain_img = model.produce_attn_maps([base_text_prompt], [negative_text], height=height, width=width,
-                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
+                                            num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **rescale, **start)
     else:
         plain_img = model.sample([base_text_prompt], negative_prompt=[negative_text], height=height, width=width,
                                  num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'], run_rich_text=False,
-                                 latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
+                                 latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **rescale, **start)
     timings['plain'] = time.time() - t0
 
     t0 = time.time()
@@ -115,14 +120,27 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
         rich_img = model.prompt_to_img(region_text_prompts, [negative_text], height=height, width=width,
                                        num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                        use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn,
-                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
+                                       text_format_dict=text_format_dict, inject_background=inject_background, latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **rescale, **start)
     else:
-        rich_img = model.sample(region_text_prompts, negative_prompt=[negative_text], height=height, width=width,
+        rich_img = _xl_rich_pass(model, phi, region_text_prompts, negative_prompt=[negative_text], height=height, width=width,
                                 num_inference_steps=param['steps'], guidance_scale=param['guidance_weight'],
                                 use_guidance=use_grad_guidance, inject_selfattn=inject_selfattn, text_format_dict=text_format_dict,
                                 inject_background=inject_background, run_rich_text=True, latents=latents, max_prompt_chunks=chunks, noise_seed=seed, **start)
     timings['rich'] = time.time() - t0
     return plain_img, rich_img, timings
+
+
+def _xl_rich_pass(model, phi, *args, **kw):
+    """model.sample(run_rich_text=True) with the request's guidance_rescale as the pipeline attribute for the duration of the call (the
+    keyword raises there, xl.py:827-830); phi None: the call as it is."""
+    if phi is None:
+        return model.sample(*args, **kw)
+    keep = getattr(model, 'guidance_rescale', 0.0)
+    model.guidance_rescale = float(phi)
+    try:
+        return model.sample(*args, **kw)
+    finally:
+        model.guidance_rescale = keep
 
 
 def _load_json_arg(v):
@@ -143,7 +161,8 @@ def _request_scheduler(a, name):
     if name not in names:
         raise SystemExit(f"sample: --requests: unknown scheduler {name!r} (one of {', '.join(names)}; no key = the --scheduler flag's)")
     order = getattr(a, 'solver_order', None) if name in ('dpmsolver++', 'sde-dpmsolver++') else None
-    make_scheduler(types.SimpleNamespace(scheduler=name, solver_order=order, model=getattr(a, 'model', 'SDXL')))
+    make_scheduler(types.SimpleNamespace(scheduler=name, solver_order=order, model=getattr(a, 'model', 'SDXL'),
+                                         prediction_type=getattr(a, 'prediction_type', None), timestep_spacing=getattr(a, 'timestep_spacing', None)))
     return name
 
 
@@ -225,24 +244,36 @@ SCHEDULER_CHOICES = ['default', 'dpmsolver++', 'sde-dpmsolver++', 'euler-ancestr
 def make_scheduler(a):
     """--scheduler / --solver_order -> the scheduler object to put on the pipeline (None: the pipeline's default, PNDM for SD and
     Euler for SDXL).  A flag that cannot be honoured is an error, never ignored."""
-    from .schedulers import DPMSolverTables, EulerAncestralTables
+    from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables, PNDMTables
     order = getattr(a, 'solver_order', None)
     name = getattr(a, 'scheduler', 'default')
-    if name in ('dpmsolver++', 'sde-dpmsolver++'):
-        return DPMSolverTables(solver_order=2 if order is None else order, algorithm=name)
-    if order is not None:
-        raise SystemExit("sample: --solver_order needs --scheduler dpmsolver++ or sde-dpmsolver++")
-    if name == 'euler-ancestral':
-        if getattr(a, 'model', 'SD') == 'SD':
-            raise SystemExit("sample: --scheduler euler-ancestral runs in sigma space: --model SDXL or AnimeXL only "
-                             "(--model SD: sde-dpmsolver++ is its stochastic sampler)")
-        return EulerAncestralTables()
+    # --prediction_type / --timestep_spacing: keywords of whichever tables run (None: the tables' / the checkpoint's default)
+    kw = {k: getattr(a, k) for k in ('prediction_type', 'timestep_spacing') if getattr(a, k, None) is not None}
+    phi = getattr(a, 'guidance_rescale', None)
+    if phi is not None and not (0.0 <= phi <= 1.0):
+        raise SystemExit(f"sample: --guidance_rescale must be in [0, 1], got {phi}")
+    try:
+        if name in ('dpmsolver++', 'sde-dpmsolver++'):
+            return DPMSolverTables(solver_order=2 if order is None else order, algorithm=name, **kw)
+        if order is not None:
+            raise SystemExit("sample: --solver_order needs --scheduler dpmsolver++ or sde-dpmsolver++")
+        if name == 'euler-ancestral':
+            if getattr(a, 'model', 'SD') == 'SD':
+                raise SystemExit("sample: --scheduler euler-ancestral runs in sigma space: --model SDXL or AnimeXL only "
+                                 "(--model SD: sde-dpmsolver++ is its stochastic sampler)")
+            return EulerAncestralTables(**kw)
+        if kw:                            # the pipeline's default sampler with the flags' keywords (PNDM refuses trailing spacing)
+            return (PNDMTables if getattr(a, 'model', 'SD') == 'SD' else EulerTables)(**kw)
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
     return None
 
 
 def apply_scheduler(model, a):
     sched = make_scheduler(a)
     if sched is not None:
+        if getattr(a, 'prediction_type', None) is None:        # no flag: what the checkpoint's scheduler_config.json said stays
+            sched.prediction_type = getattr(getattr(model, 'scheduler', None), 'prediction_type', 'epsilon')
         model.scheduler = sched
     return model
 
@@ -254,7 +285,9 @@ def apply_request_scheduler(model, flag_scheduler, r, a):
     name = r.get('scheduler')
     if name is not None:
         apply_scheduler(model, types.SimpleNamespace(scheduler=name, model=a.model,
-                                                     solver_order=a.solver_order if name in ('dpmsolver++', 'sde-dpmsolver++') else None))
+                                                     solver_order=a.solver_order if name in ('dpmsolver++', 'sde-dpmsolver++') else None,
+                                                     prediction_type=getattr(a, 'prediction_type', None),
+                                                     timestep_spacing=getattr(a, 'timestep_spacing', None)))
     return model
 
 
@@ -294,6 +327,15 @@ def build_parser():
                         'from the request\'s seed. Holds on every rank of --gpus N')
     p.add_argument('--solver_order', type=int, default=None, choices=[1, 2],
                    help='DPM-Solver++ order (default 2); needs --scheduler dpmsolver++ or sde-dpmsolver++')
+    p.add_argument('--guidance_rescale', type=float, default=None,
+                   help='CFG rescale in [0, 1] (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4): the guided '
+                        'prediction is scaled towards the standard deviation of its conditional half, in both passes; made for '
+                        'v-prediction checkpoints, usually 0.7.  Default: off')
+    p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
+                   help='what the UNet predicts; default: the checkpoint\'s scheduler/scheduler_config.json, else epsilon')
+    p.add_argument('--timestep_spacing', type=str, default=None, choices=['leading', 'trailing'],
+                   help='trailing: the schedule starts at the last training timestep (Euler, Euler ancestral and the DPM-Solver++ kinds; '
+                        'the SD default sampler PNDM refuses it).  Default: each sampler\'s own list')
     p.add_argument('--init_image', type=str, default=None,
                    help='edit this image instead of starting from noise: it is resized to height x width, encoded once, and both passes '
                         'start from it at --strength')
@@ -366,7 +408,7 @@ def main(argv=None):
         apply_request_scheduler(model, flag_scheduler, r, a)
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
-                 'max_prompt_chunks': r.get('max_prompt_chunks', 1)}
+                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

@@ -24,6 +24,38 @@ def alphas_cumprod(num_train=1000, beta_start=0.00085, beta_end=0.012):
 #   start_level()   -> (a, b): the loop starts from a * x0 + b * noise
 #   source_levels() -> one (a, b) per loop iteration: the level the latents are at AFTER it (what a pinned pixel is reset to);
 #                      the last one is (1, 0) for every scheduler: a pinned pixel ends as the source itself.
+PREDICTION_TYPES = ('epsilon', 'v_prediction')
+TIMESTEP_SPACINGS = ('leading', 'trailing')
+
+
+def check_prediction_type(v, who='prediction_type'):
+    if v not in PREDICTION_TYPES:
+        raise ValueError(f"{who} must be one of {PREDICTION_TYPES}, got {v!r}")
+    return v
+
+
+def _check_spacing(name, v):
+    if v not in TIMESTEP_SPACINGS:
+        raise ValueError(f"{name}: timestep_spacing must be one of {TIMESTEP_SPACINGS}, got {v!r}")
+    return v
+
+
+def trailing_timesteps(n, num_train=1000):
+    """round(num_train - k num_train / n) - 1 for k = 0 .. n-1 ([memory]: diffusers' timestep_spacing="trailing"; the first step is the
+    last training timestep, which is what zero-terminal-SNR / v-prediction checkpoints are sampled with)."""
+    return (np.round(num_train - np.arange(n) * (num_train / n)) - 1).astype(np.int64)
+
+
+def engine_prediction(scheduler, guidance_scale, call_rescale=0.0, pipeline_rescale=0.0):
+    """(prediction_type, phi) for Engine.set_prediction: the scheduler's `prediction_type` attribute; phi = the call's guidance_rescale
+    if > 0, else the pipeline's, and only under classifier-free guidance (guidance_scale > 1, xl.py:903)."""
+    ptype = check_prediction_type(getattr(scheduler, 'prediction_type', 'epsilon'), f"{type(scheduler).__name__}.prediction_type")
+    phi = float(call_rescale) if call_rescale and call_rescale > 0 else float(pipeline_rescale or 0.0)
+    if not (0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {phi}")
+    return ptype, (phi if guidance_scale > 1.0 else 0.0)
+
+
 def _executed_steps(name, n, strength, least=1):
     if not (0.0 < strength <= 1.0):
         raise ValueError(f"{name}.set_timesteps: strength must be in (0, 1], got {strength}")
@@ -42,8 +74,14 @@ class PNDMTables:
     kind = 1
     init_noise_sigma = 1.0
 
-    def __init__(self, num_train=1000):
+    def __init__(self, num_train=1000, prediction_type='epsilon', timestep_spacing='leading'):
+        """`prediction_type` is an attribute the pipelines hand to the engine (Engine.set_prediction): the tables do not depend on it.
+        PLMS's `prev_t = t - num_train // n` arithmetic is leading-only: trailing spacing is refused."""
         self.num_train = num_train
+        self.prediction_type = check_prediction_type(prediction_type, "PNDMTables: prediction_type")
+        if _check_spacing("PNDMTables", timestep_spacing) != 'leading':
+            raise ValueError("PNDMTables: timestep_spacing='trailing' is not supported (the PLMS step assumes t - num_train // n)")
+        self.timestep_spacing = timestep_spacing
         self.alphas_cumprod = alphas_cumprod(num_train)
 
     def set_timesteps(self, n, strength=1.0):
@@ -74,8 +112,12 @@ class PNDMTables:
 class EulerTables:
     kind = 0
 
-    def __init__(self, num_train=1000):
+    def __init__(self, num_train=1000, prediction_type='epsilon', timestep_spacing='leading'):
+        """`prediction_type`: an attribute for Engine.set_prediction, the tables do not depend on it.  timestep_spacing='trailing':
+        trailing_timesteps() instead of the SDXL config's leading list with steps_offset 1."""
         self.num_train = num_train
+        self.prediction_type = check_prediction_type(prediction_type, f"{type(self).__name__}: prediction_type")
+        self.timestep_spacing = _check_spacing(type(self).__name__, timestep_spacing)
         ac = alphas_cumprod(num_train).astype(np.float64)
         self.alphas_cumprod = alphas_cumprod(num_train)
         self._train_sigmas = ((1 - ac) / ac) ** 0.5
@@ -86,7 +128,10 @@ class EulerTables:
         full schedule's (an image start does not use it: start_level())."""
         k = _executed_steps("EulerTables", n, strength)
         self.num_inference_steps = n
-        ts = (np.arange(0, n) * (self.num_train // n)).round()[::-1].copy().astype(np.float32) + 1
+        if self.timestep_spacing == 'trailing':
+            ts = trailing_timesteps(n, self.num_train).astype(np.float32)
+        else:
+            ts = (np.arange(0, n) * (self.num_train // n)).round()[::-1].copy().astype(np.float32) + 1
         sig = np.interp(ts, np.arange(0, self.num_train), self._train_sigmas)
         self.sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
         self.timesteps = ts
@@ -117,7 +162,11 @@ class DPMSolverTables:
     algorithm='sde-dpmsolver++': the stochastic variant ("DPM++ 2M SDE") on the same tables, levels and history."""
     init_noise_sigma = 1.0
 
-    def __init__(self, solver_order=2, num_train=1000, algorithm='dpmsolver++'):
+    def __init__(self, solver_order=2, num_train=1000, algorithm='dpmsolver++', prediction_type='epsilon', timestep_spacing='leading'):
+        """`prediction_type`: an attribute for Engine.set_prediction, the tables do not depend on it.  timestep_spacing: 'leading' names
+        today's list (diffusers 0.18.2's linspace over [0, num_train - 1]); 'trailing': trailing_timesteps()."""
+        self.prediction_type = check_prediction_type(prediction_type, "DPMSolverTables: prediction_type")
+        self.timestep_spacing = _check_spacing("DPMSolverTables", timestep_spacing)
         if solver_order not in (1, 2):
             raise ValueError(f"DPMSolverTables: solver_order must be 1 or 2, got {solver_order}")
         if algorithm not in ('dpmsolver++', 'sde-dpmsolver++'):
@@ -140,7 +189,10 @@ class DPMSolverTables:
         last step when fewer than 15 steps run) on the EXECUTED list, where diffusers' img2img counts the full one: a deliberate
         deviation, [memory], parity unpinned."""
         k = _executed_steps("DPMSolverTables", n, strength)
-        ts = np.linspace(0, self.num_train - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        if self.timestep_spacing == 'trailing':
+            ts = trailing_timesteps(n, self.num_train)
+        else:
+            ts = np.linspace(0, self.num_train - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
         _, first = np.unique(ts, return_index=True)
         self.timesteps = ts[np.sort(first)]
         if k < n:
