@@ -339,6 +339,20 @@ int rt_op_causal_attention(const void* q, const void* k, const void* v, int ld, 
  * 1024), NKpad = key count padded to a multiple of 32. */
 int rt_op_attention_probs_avg(const void* Q, int ldq, long long q_row0, const void* K, int ldk, long long k_row0, float* out,
                               int H, int N, int NK, int NKpad, int NKrows, int DP, int accumulate, void* stream);
+/* A recorded layer of the plain pass as the UNet forward runs it: the attention launch over B batch entries (O is written), then the store of
+ * batch entry `store_stream` into map_out (=|+= as rt_op_attention_probs_avg).  Where the forward hands the softmax statistics of that entry
+ * from the attention launch to the store (stats_ready: the store then runs its apply kernel only) this call does too, by the same
+ * predicates; *handover = 1 then, 0 when the store computed its own (rt_op_gemm_debug bit 17 forces that).
+ * cross = 0: Q / K [B*N, ld] and V^T as rt_op_attention, entry b attends with Q and K of entry qk_src_host[b] (NULL: its own) and its own V;
+ *   NK must equal N; map_out [N, N]; handed over when 256 <= N <= 1024, N % 32 == 0, DP in {32, 64, 96} and qk_src_host[store_stream] == store_stream.
+ * cross = 1: K / V^T are prompt caches of NK = 96, 192 or 288 rows per prompt as rt_op_attention_keys (prompt_host, key_counts_host, plain
+ *   softmax; wabs / wsgn [1, NK] are read by the generic kernel's argument check only and may be NULL where cross77_kernel runs);
+ *   map_out [N, key_counts_host[store_stream]]; handed over when the launch runs on cross77_kernel (d = 64, N % 64 == 0, every entry 77 keys).
+ * d = the unpadded head dim. */
+int rt_op_attention_store_handover(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo,
+                                   const int* qk_src_host, const int* prompt_host, const int* key_counts_host, const float* wabs,
+                                   const float* wsgn, int B, int H, int N, int NK, int d, int DP, int cross, int store_stream,
+                                   float* map_out, int accumulate, int* handover, void* stream);
 const char* rt_op_last_error(void);
 /* GEMM tile choice: -1 (default) = a pure function of the problem shape (csrc/gemm16.hip: 16x16x32-MFMA family, 224-row tiles;
  * csrc/gemm.hip: 32x32x16 family for everything else) - no timing, no per-process state; 0..8 = force one tile configuration of

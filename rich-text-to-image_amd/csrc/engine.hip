@@ -133,6 +133,18 @@ struct FwdIn {
 
 extern int g_store_own_stats;
 static inline bool g_store_own_stats_flag() { return g_store_own_stats != 0; }
+// The statistics hand-over of a recorded layer (attn_store.hip, stats_ready), shared by the UNet forward and rt_op_attention_store_handover:
+// self-attention - the launch leaves (m, 1 / (H l)) of the recorded stream when the store would run its statistics + apply pair for the map
+// and the stream attends with its own Q / K (an injected stream's scores are another stream's);
+static inline bool store_handover_self(int tokens, int DP, const int* qk_src, int stream) {
+    return attn_store_takes_stats(tokens, tokens, DP) && qk_src[stream] == stream;
+}
+// cross-attention - the launch runs on cross77_kernel (head dim 64, every stream of the launch with 77 keys) ...
+static inline bool cross77_route(int heads, int DP, int d, int tokens, int prompt_rows, bool all77) {
+    return all77 && gemm_cross77_enabled() && cross77_supported(heads, DP, tokens, prompt_rows, 77) && d == 64;
+}
+// ... and debug bit 17 is clear.
+static inline bool store_handover_cross(bool on_cross77) { return on_cross77 && !g_store_own_stats_flag(); }
 // step epilogue kernels (defined in step.hip)
 struct StepArgs;
 void launch_step_epilogue(const StepArgs& a, hipStream_t st);
@@ -694,7 +706,7 @@ struct rt_engine {
                     // a layer whose map is recorded in this call: the attention launch leaves the softmax statistics of the recorded stream,
                     // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
                     const bool will_store = in.store_stream >= 0 && k.store_mode[0] && k.store_calls[0] + 1 > 10;      // n_maps[name] > 10 (rd.py:422, xl.py:988)
-                    const bool stats_from_attn = will_store && attn_store_takes_stats(HW, HW, t.DP) && in.qk_src[in.store_stream] == in.store_stream;
+                    const bool stats_from_attn = will_store && store_handover_self(HW, t.DP, in.qk_src, in.store_stream);
                     if (stats_from_attn) { a.stats = store_stats; a.stats_b = in.store_stream; }
                     prof_begin(RT_PROF_ATTN_SELF, 4.0 * B * t.heads * (double)HW * HW * t.d);
                     launch_attention(a, stream);
@@ -729,8 +741,8 @@ struct rt_engine {
                 for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; all77 = all77 && nkeys[b] == 77; }
                 // round 5: the 77-key attention on its own kernel (cross77_kernel, xblock.hip: 64 queries x 2 heads per workgroup, K / V^T in
                 // LDS) behind the plain to_q GEMM is faster than the fused launch of round 4 and serves the capturing layers too (Q is in HBM)
-                const bool c77ok = gemm_cross77_enabled() && cross77_supported(t.heads, t.DP, HW, KPr, 77) && t.d == 64;
-                const bool c77 = all77 && c77ok;
+                const bool c77ok = cross77_route(t.heads, t.DP, t.d, HW, KPr, true);
+                const bool c77 = cross77_route(t.heads, t.DP, t.d, HW, KPr, all77);
                 const bool fused2 = all77 && KPr == 96 && !c77 && !fold2 && gemm_xattn_enabled() && xattn_fused_supported(C, t.heads, t.DP, HW) && !capture2;
                 // the 640-channel level: to_q, attention AND to_out + residual as one launch with Q / P / O in registers (xblock.hip)
                 const bool block2 = all77 && KPr == 96 && !fold2 && gemm_xblock_enabled() && xblock_supported(C, t.heads, t.DP, HW) && t.d == 64 && !capture2;
@@ -772,7 +784,7 @@ struct rt_engine {
                     a.B = B; a.H = t.heads; a.N = HW; a.NK = KPr; a.nk_valid = 77; a.DP = t.DP; a.cross = 1;
                     // a recorded layer on cross77_kernel: the launch leaves the softmax statistics of the recorded stream (as the self-attention
                     // launch does for attn1), the store runs its apply kernel only
-                    const bool stats2 = c77 && capture2 && k.store_calls[1] + 1 > 10 && !g_store_own_stats_flag();
+                    const bool stats2 = capture2 && k.store_calls[1] + 1 > 10 && store_handover_cross(c77);
                     if (stats2) { a.stats = store_stats; a.stats_b = in.store_stream; }
                     double keysum = 0; for (int b = 0; b < B; ++b) keysum += nkeys[b];
                     prof_begin(RT_PROF_ATTN_CROSS, 4.0 * t.heads * (double)HW * keysum * t.d);
@@ -1812,6 +1824,59 @@ int rt_op_attention_probs_avg(const void* Q, int ldq, long long q_row0, const vo
         a.out = out; a.H = H; a.N = N; a.NK = NK; a.NKpad = NKpad; a.NKrows = NKrows; a.DP = DP; a.overwrite = accumulate ? 0 : 1;
         a.stats = op_store_stats((size_t)H * N * 2, (hipStream_t)stream);
         launch_attn_store(a, (hipStream_t)stream);
+    })
+}
+// A recorded layer as the UNet forward runs it: the attention launch, then the store of stream `store_stream`.
+int rt_op_attention_store_handover(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo,
+                                   const int* qk_src_host, const int* prompt_host, const int* key_counts_host, const float* wabs,
+                                   const float* wsgn, int B, int H, int N, int NK, int d, int DP, int cross, int store_stream,
+                                   float* map_out, int accumulate, int* handover, void* stream) {
+    OP_TRY({
+        hipStream_t st = (hipStream_t)stream;
+        RT_REQUIRE(B >= 1 && B <= RT_MAXB && store_stream >= 0 && store_stream < B && map_out && handover, "rt_op_attention_store_handover: batch / recorded stream / outputs");
+        RT_REQUIRE(H >= 1 && H <= 32 && N >= 1, "rt_op_attention_store_handover: at most 32 heads");
+        AttnArgs a{}; a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.VT = (const bf16_t*)VT; a.ldvt = ldvt;
+        a.O = (bf16_t*)O; a.ldo = ldo; a.wabs = wabs; a.wsgn = wsgn; a.B = B; a.H = H; a.N = N; a.DP = DP; a.cross = cross;
+        AttnStoreArgs sa{}; sa.Q = a.Q; sa.ldq = ldq; sa.q_row0 = (long)store_stream * N; sa.K = a.K; sa.ldk = ldk;
+        sa.out = map_out; sa.H = H; sa.N = N; sa.DP = DP; sa.overwrite = accumulate ? 0 : 1;
+        float* scratch = op_store_stats((size_t)H * N * 2, st);
+        bool taken = false;
+        if (!cross) {
+            RT_REQUIRE(NK == N, "rt_op_attention_store_handover: self-attention has as many keys as queries");
+            int src[RT_MAXB];
+            for (int b = 0; b < B; ++b) {
+                src[b] = qk_src_host ? qk_src_host[b] : b;
+                RT_REQUIRE(src[b] >= 0 && src[b] < B, "rt_op_attention_store_handover: Q / K source");
+                a.q_src[b] = a.k_src[b] = src[b]; a.v_src[b] = b; a.wset[b] = 0;
+            }
+            a.NK = N; a.nk_valid = N;
+            taken = scratch && store_handover_self(N, DP, src, store_stream);
+            if (taken) { a.stats = scratch; a.stats_b = store_stream; }
+            launch_attention(a, st);
+            // the key COUNT is padded to the store's 32-key step, the key rows are not (a map of N % 32 == 0 tokens: NKpad = N as in the forward)
+            sa.k_row0 = (long)store_stream * N; sa.NK = N; sa.NKpad = (N + 31) / 32 * 32; sa.NKrows = N;
+            sa.stats = scratch; sa.stats_ready = taken ? 1 : 0;
+        } else {
+            RT_REQUIRE(prompt_host && key_counts_host && (NK == 96 || NK == 192 || NK == 288), "rt_op_attention_store_handover: prompts of 96, 192 or 288 rows");
+            bool all77 = true;
+            for (int b = 0; b < B; ++b) {
+                const int c = key_counts_host[b];
+                RT_REQUIRE(c >= 77 && c % 77 == 0 && c / 77 * 96 <= NK && prompt_host[b] >= 0, "rt_op_attention_store_handover: a key count must be 77 per 96-row chunk of NK");
+                a.q_src[b] = b; a.k_src[b] = a.v_src[b] = prompt_host[b]; a.wset[b] = -1; a.nkeys[b] = c; all77 = all77 && c == 77;
+            }
+            a.NK = NK; a.nk_valid = 77;
+            const bool c77 = cross77_route(H, DP, d, N, NK, all77);
+            taken = scratch && store_handover_cross(c77);
+            if (taken) { a.stats = scratch; a.stats_b = store_stream; }
+            if (c77) launch_cross77(a, st);
+            else if (cross77_route(H, DP, d, N, NK, true)) launch_cross_runs(a, st);      // mixed key counts; no hand-over
+            else launch_attention(a, st);                                                // the generic launch: no hand-over
+            const int snk = key_counts_host[store_stream], srows = 96 * (snk / 77);
+            sa.k_row0 = (long)prompt_host[store_stream] * NK; sa.NK = snk; sa.NKpad = srows; sa.NKrows = srows;
+            if (taken) { sa.stats = scratch; sa.stats_ready = 1; }
+        }
+        launch_attn_store(sa, st);
+        *handover = taken ? 1 : 0;
     })
 }
 

@@ -82,6 +82,7 @@ _SYMBOLS = [
     "rt_set_prompts_keys", "rt_op_attention_keys",
     "rt_set_noise_seed", "rt_op_step_noise",
     "rt_set_prediction", "rt_op_guided_prediction",
+    "rt_op_attention_store_handover",
 ]
 
 

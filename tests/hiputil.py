@@ -105,3 +105,28 @@ def report(name, got, ref, atol, rtol):
            f"bad={int(bad.sum())}/{bad.numel()}")
     print(msg)
     assert not bad.any(), msg
+
+
+def probs_avg_rc(Q, K, out, H, N, NK, NKpad, NKrows, DP, accumulate=0, q_row0=0, k_row0=0):
+    """rt_op_attention_probs_avg on the caller's buffers (`out` may be a view into a guard-banded allocation); returns the error code."""
+    lib = load_library()
+    rc = lib.rt_op_attention_probs_avg(_ptr(Q), Q.stride(0), C.c_longlong(q_row0), _ptr(K), K.stride(0), C.c_longlong(k_row0), _ptr(out),
+                                       H, N, NK, NKpad, NKrows, DP, int(accumulate), None)
+    torch.cuda.synchronize()
+    return rc
+
+
+def store_handover(Q, K, VT, O, out, B, H, N, NK, d, DP, store_stream, cross=False, qk_src=None, prompt=None, key_counts=None, accumulate=0):
+    """rt_op_attention_store_handover: the attention launch (writes O) + the store of `store_stream` (writes out); True when the
+    attention launch handed its softmax statistics to the store."""
+    lib = load_library()
+
+    def ia(v):
+        return (C.c_int * B)(*v) if v is not None else None
+    taken = C.c_int(-1)
+    chk(lib.rt_op_attention_store_handover(_ptr(Q), Q.stride(0), _ptr(K), K.stride(0), _ptr(VT), VT.stride(0), _ptr(O), O.stride(0),
+                                           ia(qk_src), ia(prompt), ia(key_counts), None, None, B, H, N, NK, d, DP, int(cross),
+                                           store_stream, _ptr(out), int(accumulate), C.byref(taken), None))
+    torch.cuda.synchronize()
+    assert taken.value in (0, 1)
+    return bool(taken.value)
