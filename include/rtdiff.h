@@ -251,6 +251,23 @@ int rt_op_gemm16_pick(int conv3x3, int epi, int streams, int rows_per_stream, in
  * 3 the nearest-2x up-sample folded in (rows_per_stream = OUTPUT pixels, a square map).  Route and slice count are functions of ONE
  * stream's shape (a nominal batch of four), never of `streams`: a stream's k order does not depend on the batch. */
 int rt_op_split_plan(int conv3x3, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int* route, int* slices);
+/* Host-only query (no device needed; tests/test_gemm_route.py): the route rt_op_gemm takes for exactly these arguments - gemm_route of
+ * the GemmArgs rt_op_gemm itself builds (one helper makes them for both: no stream shares, unlike rt_op_split_plan / rt_op_gemm16_pick,
+ * which describe the engine's launches) - under the same switches (rt_op_gemm_force_config, rt_op_gemm_debug / _debug2).  A route is a
+ * function of the shape, never of a leading dimension or a pointer.
+ * *kind: RT_ROUTE_* below; *variant_or_cfg: the tile variant of csrc/gemm16.hip (G16, G16_UP2; ids at rt_op_gemm16_variant), the tile
+ * configuration 0..8 of csrc/gemm.hip (TILE), -1 elsewhere; *slices: K slices (KSPLIT) / input-channel chunks (PATCH_SPLIT), 1 elsewhere.
+ * Any of the three may be NULL.  RT_E_INVALID for an unknown mode / epilogue or an empty shape. */
+enum { RT_ROUTE_TILE = 0        /* one launch of a csrc/gemm.hip tile configuration (dense or implicit-GEMM convolution) */,
+       RT_ROUTE_G16 = 1         /* csrc/gemm16.hip: dense, or the stride-1 3x3 convolution on its main loop */,
+       RT_ROUTE_G16_UP2 = 2     /* csrc/gemm16.hip: the 2x-upsample convolution as four 2x2 phase convolutions (needs the phase pack:
+                                 * rt_op_upconv only, which reports it as *phase_route) */,
+       RT_ROUTE_PATCH = 3       /* the 16x16-patch convolution kernel */,
+       RT_ROUTE_PATCH_SPLIT = 4 /* ... split over its input-channel chunks + reduction launch */,
+       RT_ROUTE_KSPLIT = 5      /* K slices of the 128x128 (implicit) GEMM + reduction launch */,
+       RT_ROUTE_TRIPLE = 6      /* the precise VAE's hi / lo contraction as three launches (rt_vae_* only) */ };
+int rt_op_gemm_route(int mode, int epi, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win, int Cin,
+                     int Hout, int Wout, int* kind, int* variant_or_cfg, int* slices);
 /* One tile variant of the 16x16x32-MFMA GEMM family (csrc/gemm16.hip; tests / micro-benchmarks - rt_op_gemm picks by shape):
  * 0: 224x160 K-split  1: 128x160 K-split  2: 224x256  3: 256x256  4: 224x320  5: 256x320  6: 160x224 K-split (V^T)  7: 160x128 K-split
  * 8: 128x256  9: 64x160 K-split  10: 128x320  11: 64x320  12: 160x64 K-split (V^T) - 9..12: the small batches of the plain pass / SD-v1.5;
@@ -285,6 +302,10 @@ int rt_op_cross_attn_block(const void* x, const void* wq, const void* wo, const 
 int rt_op_groupnorm(const void* x1, const void* x2, int in_type, int C1, int C2, int G, int B, int HW,
                     const float* gamma, const float* beta, float eps, int silu, void* out_bf16, void* raw_out_bf16,
                     void* stream);
+/* Host-only (no device needed): the form rt_op_groupnorm takes for these arguments, from the launcher's own predicate - 1: one launch
+ * (statistics and apply in one kernel), 2: two launches (statistics, then apply); rt_op_gemm_debug bit 23 forces 2.  RT_E_INVALID (< 0) for
+ * arguments rt_op_groupnorm would refuse. */
+int rt_op_groupnorm_form(int in_type, int C1, int C2, int G, int B, int HW);
 int rt_op_layernorm(const float* x, const float* gamma, const float* beta, void* out_bf16, int rows, int C, float eps,
                     void* stream);
 int rt_op_layernorm_f16(const void* x_f16, const float* gamma, const float* beta, void* out_bf16, int rows, int C, float eps, void* stream);

@@ -346,6 +346,7 @@ struct GroupNormArgs {
 int groupnorm_rows_per_chunk(int HW);
 int groupnorm_bwd_rows_per_chunk(int HW);              // chunking of launch_groupnorm_bwd (its own partial-sum layout; one image: the forward's (mean, rstd) sit at offset 0 either way)
 void launch_groupnorm(const GroupNormArgs& a, hipStream_t st);
+int groupnorm_form(const GroupNormArgs& a);            // host-only: 1 = launch_groupnorm runs the one-launch form, 2 = the two-launch form (reads the shape, in_bf16 and out_lo / raw_lo)
 void groupnorm_set_chunk_div(int d);                    // A/B
 void groupnorm_set_fused(int on);                       // A/B: 0 = always the two-launch form (rt_op_gemm_debug bit 23)
 int groupnorm_nchunk(int HW);

@@ -1515,16 +1515,50 @@ int rt_op_gemm_force_config(int cfg) {
     return RT_OK;
 }
 
+// The GemmArgs of an rt_op_gemm call: what the launch and the host-only route query (rt_op_gemm_route) both build, so that they cannot drift.
+// `zero` is the zero page of the launch (the query, which touches no device, leaves it null: no routing rule reads a pointer's value here).
+static GemmArgs op_gemm_args(const void* A, const void* W, const float* bias, void* out, const void* res, const float* temb, const bf16_t* zero, int mode,
+                             int epi, int M, int N, int K, int lda, int ldw, int ldo, int ldres, int temb_ld, int rows_per_batch, int Hin,
+                             int Win, int Cin, int Hout, int Wout) {
+    GemmArgs g{}; g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.out = out; g.res = res; g.temb = temb;
+    g.zero = zero; g.mode = mode; g.epi = epi; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
+    g.ldres = ldres; g.temb_ld = temb_ld; g.rows_per_batch = rows_per_batch; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
+    g.Hout = Hout; g.Wout = Wout;
+    return g;
+}
 int rt_op_gemm(const void* A, const void* W, const float* bias, void* out, const void* res, const float* temb, int mode,
                int epi, int M, int N, int K, int lda, int ldw, int ldo, int ldres, int temb_ld, int rows_per_batch, int Hin,
                int Win, int Cin, int Hout, int Wout, void* stream) {
     OP_TRY({
-        GemmArgs g{}; g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.out = out; g.res = res; g.temb = temb;
-        g.zero = op_zero_page(); g.mode = mode; g.epi = epi; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo;
-        g.ldres = ldres; g.temb_ld = temb_ld; g.rows_per_batch = rows_per_batch; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-        g.Hout = Hout; g.Wout = Wout;
+        const GemmArgs g = op_gemm_args(A, W, bias, out, res, temb, op_zero_page(), mode, epi, M, N, K, lda, ldw, ldo, ldres, temb_ld, rows_per_batch,
+                                        Hin, Win, Cin, Hout, Wout);
         launch_gemm(g, (hipStream_t)stream);
     })
+}
+// The route of that call as a host-only query (no device needed): gemm_route of the same GemmArgs, under the same switches.
+int rt_op_gemm_route(int mode, int epi, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win, int Cin, int Hout,
+                     int Wout, int* kind, int* variant_or_cfg, int* slices) {
+    try {
+        if (mode < A_DENSE || mode > A_CONV3_S2P0 || epi < EPI_BF16 || epi > EPI_F16 || M <= 0 || N <= 0 || K <= 0) return RT_E_INVALID;
+        if (mode != A_DENSE && (rows_per_batch <= 0 || Cin <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0)) return RT_E_INVALID;
+        const GemmArgs g = op_gemm_args(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mode, epi, M, N, K, lda, ldw, ldo, 0, 0,
+                                        rows_per_batch, Hin, Win, Cin, Hout, Wout);
+        const GemmRoute r = gemm_route(g);
+        int k = RT_ROUTE_TILE, v = -1;
+        switch (r.kind) {
+            case GemmRoute::TILE: k = RT_ROUTE_TILE; v = r.cfg; break;
+            case GemmRoute::G16: k = RT_ROUTE_G16; v = r.variant; break;
+            case GemmRoute::G16_UP2: k = RT_ROUTE_G16_UP2; v = r.variant; break;
+            case GemmRoute::PATCH: k = RT_ROUTE_PATCH; break;
+            case GemmRoute::PATCH_SPLIT: k = RT_ROUTE_PATCH_SPLIT; break;
+            case GemmRoute::KSPLIT: k = RT_ROUTE_KSPLIT; break;
+            case GemmRoute::TRIPLE: k = RT_ROUTE_TRIPLE; break;
+        }
+        if (kind) *kind = k;
+        if (variant_or_cfg) *variant_or_cfg = v;
+        if (slices) *slices = r.slices;
+        return RT_OK;
+    } catch (...) { return RT_E_INVALID; }
 }
 int rt_op_pack_upconv(const void* w, int dtype, int Cout, int Cin, void* out_bf16, void* stream) {
     OP_TRY({ launch_pack_up2(w, dtype, (bf16_t*)out_bf16, Cout, Cin, (hipStream_t)stream); })
@@ -1767,6 +1801,12 @@ int rt_op_groupnorm(const void* x1, const void* x2, int in_bf16, int C1, int C2,
         HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
         HIP_CHECK(hipFree(partial));
     })
+}
+// Host-only: the form launch_groupnorm takes for that call (the predicate of the launcher itself; rt_op_gemm_debug bit 23 counts).
+int rt_op_groupnorm_form(int in_type, int C1, int C2, int G, int B, int HW) {
+    if (in_type < 0 || in_type > 2 || C1 <= 0 || C2 < 0 || G < 1 || (C1 + C2) % G || B < 1 || HW < 1) return RT_E_INVALID;
+    GroupNormArgs a{}; a.in_bf16 = in_type; a.C1 = C1; a.C2 = C2; a.G = G; a.B = B; a.HW = HW;
+    return groupnorm_form(a);
 }
 int rt_op_layernorm(const float* x, const float* gamma, const float* beta, void* out, int rows, int C, float eps, void* stream) {
     OP_TRY({ launch_layernorm(x, 0, gamma, beta, (bf16_t*)out, rows, C, eps, (hipStream_t)stream); })

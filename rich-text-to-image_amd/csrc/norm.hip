@@ -500,6 +500,7 @@ static int gn_fused_vw(const GroupNormArgs& a) {
     if (!vw || cpg / vw > 512) return 0;
     return vw;
 }
+int groupnorm_form(const GroupNormArgs& a) { return gn_fused_vw(a) ? 1 : 2; }
 
 void launch_groupnorm(const GroupNormArgs& a, hipStream_t st) {
     const int C = a.C1 + a.C2;

@@ -83,6 +83,7 @@ _SYMBOLS = [
     "rt_set_noise_seed", "rt_op_step_noise",
     "rt_set_prediction", "rt_op_guided_prediction",
     "rt_op_attention_store_handover",
+    "rt_op_gemm_route", "rt_op_groupnorm_form",
 ]
 
 

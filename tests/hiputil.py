@@ -8,6 +8,12 @@ from rich_text_to_image_amd.engine import load_library, _ptr
 DEV = "cuda:0"
 
 
+def blank(*shape, dtype=torch.float32):
+    """An output buffer pre-filled with NaN (torch.empty hands back a cached block that may still hold the previous launch's correct
+    values): an element a kernel never writes fails the comparison that follows."""
+    return torch.full(shape, float("nan"), device=DEV, dtype=dtype)
+
+
 def chk(rc):
     if rc != 0:
         raise RuntimeError(f"rt_op error {rc}: {load_library().rt_op_last_error().decode()}")
@@ -17,8 +23,9 @@ def bf(t):
     return t.to(DEV).to(torch.bfloat16).contiguous()
 
 
-def gemm(A, W, bias=None, epi=0, res=None, temb=None, rows_per_batch=0, mode=0, conv=None, out_cols=None):
-    """A: bf16 [M,K] (dense) or NHWC [B,Hin,Win,Cin] (conv); W bf16 [N,K]."""
+def gemm(A, W, bias=None, epi=0, res=None, temb=None, rows_per_batch=0, mode=0, conv=None, out_cols=None, out=None):
+    """A: bf16 [M,K] (dense) or NHWC [B,Hin,Win,Cin] (conv); W bf16 [N,K].  Leading dimensions are the operands' own row strides (A, W,
+    res, temb may be windows of wider buffers); out: the caller's [M, columns] window instead of a fresh exact allocation."""
     lib = load_library()
     N, K = W.shape
     if mode == 0:
@@ -32,7 +39,10 @@ def gemm(A, W, bias=None, epi=0, res=None, temb=None, rows_per_batch=0, mode=0, 
         rows_per_batch = Hout * Wout
         lda = 0
     oc = out_cols if out_cols is not None else (N // 2 if epi == 3 else N)
-    out = torch.empty(M, oc, device=DEV, dtype={1: torch.float32, 4: torch.float16}.get(epi, torch.bfloat16))
+    odt = {1: torch.float32, 4: torch.float16}.get(epi, torch.bfloat16)
+    if out is None:
+        out = blank(M, oc, dtype=odt)
+    assert out.shape == (M, oc) and out.dtype == odt and out.stride(1) == 1
     chk(lib.rt_op_gemm(_ptr(A), _ptr(W), _ptr(bias), _ptr(out), _ptr(res), _ptr(temb), mode, epi, M, N, K, lda, W.stride(0),
                        out.stride(0), res.stride(0) if res is not None else 0, temb.stride(0) if temb is not None else 0,
                        rows_per_batch, Hin, Win, Cin, Hout, Wout, None))
@@ -41,9 +51,12 @@ def gemm(A, W, bias=None, epi=0, res=None, temb=None, rows_per_batch=0, mode=0, 
 
 
 def attention(Q, K, VT, B, H, N, NK, DP, ldq=None, ldk=None, q_src=None, k_src=None, v_src=None, cross=False, wabs=None,
-              wsgn=None, wset=None, nk_valid=None):
+              wsgn=None, wset=None, nk_valid=None, O=None):
+    """O: the caller's [B*N, H*DP] window instead of a fresh exact allocation; V^T's leading dimension is VT's own row stride."""
     lib = load_library()
-    O = torch.zeros(B * N, H * DP, device=DEV, dtype=torch.bfloat16)
+    if O is None:
+        O = blank(B * N, H * DP, dtype=torch.bfloat16)
+    assert O.shape == (B * N, H * DP) and O.dtype == torch.bfloat16 and O.stride(1) == 1
 
     def ia(v):
         return (C.c_int * B)(*v) if v is not None else None
@@ -59,8 +72,8 @@ def groupnorm(x1, x2, G, gamma, beta, eps, silu, want_raw=False):
     in_bf16 = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[x1.dtype]
     B, HW, C1 = x1.shape
     C2 = x2.shape[2] if x2 is not None else 0
-    out = torch.empty(B, HW, C1 + C2, device=DEV, dtype=torch.bfloat16)
-    raw = torch.empty_like(out) if want_raw else None
+    out = blank(B, HW, C1 + C2, dtype=torch.bfloat16)
+    raw = blank(B, HW, C1 + C2, dtype=torch.bfloat16) if want_raw else None
     chk(lib.rt_op_groupnorm(_ptr(x1), _ptr(x2), int(in_bf16), C1, C2, G, B, HW, _ptr(gamma), _ptr(beta), C.c_float(eps),
                             int(silu), _ptr(out), _ptr(raw), None))
     torch.cuda.synchronize()
@@ -70,26 +83,31 @@ def groupnorm(x1, x2, G, gamma, beta, eps, silu, want_raw=False):
 def layernorm(x, gamma, beta, eps=1e-5):
     lib = load_library()
     rows, Cc = x.shape
-    out = torch.empty(rows, Cc, device=DEV, dtype=torch.bfloat16)
+    out = blank(rows, Cc, dtype=torch.bfloat16)
     fn = lib.rt_op_layernorm_f16 if x.dtype == torch.float16 else lib.rt_op_layernorm
     chk(fn(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), rows, Cc, C.c_float(eps), None))
     torch.cuda.synchronize()
     return out
 
 
-def small_linear(a, W, bias, silu_in=False):
+def small_linear(a, W, bias, silu_in=False, out=None, accumulate=False):
+    """out: the caller's [B, N] fp32 window (accumulate: out += ...) instead of a fresh exact allocation."""
     lib = load_library()
     B, K = a.shape
     N = W.shape[0]
-    out = torch.zeros(B, N, device=DEV)
-    chk(lib.rt_op_small_linear(_ptr(a), a.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(out), N, B, N, K, int(silu_in), 0, None))
+    if out is None:
+        assert not accumulate
+        out = blank(B, N)
+    assert out.shape == (B, N) and out.dtype == torch.float32 and out.stride(1) == 1
+    chk(lib.rt_op_small_linear(_ptr(a), a.stride(0), _ptr(W), W.stride(0), _ptr(bias), _ptr(out), out.stride(0), B, N, K, int(silu_in),
+                               int(accumulate), None))
     torch.cuda.synchronize()
     return out
 
 
 def timestep_embed(t, dim):
     lib = load_library()
-    out = torch.zeros(t.numel(), dim, device=DEV)
+    out = blank(t.numel(), dim)
     chk(lib.rt_op_timestep_embed(_ptr(t), t.numel(), dim, _ptr(out), dim, None))
     torch.cuda.synchronize()
     return out

@@ -59,6 +59,13 @@ def test_gemm_bf16_out_and_strided_output():
     A, W = bf(rnd(M, K, seed=5)), bf(rnd(N, K, seed=6, scale=K ** -0.5))
     out = gemm(A, W, None, epi=0)
     report("gemm_bf16", out, A.float() @ W.float().t(), **BF16_OUT)
+    # the same problem into a window of a wider buffer (ldo = 232 > N): the same bits, and not a byte outside the window
+    from memguard import damage, guarded, intact, unwritten
+    big, win = guarded((M, N), torch.bfloat16, ld=232, device=DEV)
+    gemm(A, W, None, epi=0, out=win)
+    assert intact(big, win), damage(big, win)
+    assert unwritten(win) == 0
+    assert torch.equal(win, out)
 
 
 def test_gemm_geglu_epilogue():
@@ -835,6 +842,12 @@ def test_cross_attn_block_fused_kernel_against_reference_arithmetic(B, N, Cc, H)
 
 
 # ----------------------------------------------------------------------------------------------- norms
+# The launch form (csrc/norm.hip gn_fused_vw through the host query: 1 = one launch, 2 = two launches) of test_groupnorm's cases whose HW is
+# not a power of two, keyed (HW, C1, C2): HW 1008 (40 and 80 channels per group), 96 (80) and 384 (60: 4-wide loads) take the ONE-launch
+# form, HW 4032 and the fp32-input 16128 the two-launch form.  A change of the rule fails the assertion instead of silently moving a case.
+GN_FORM_NOT_POW2 = {(1008, 1280, 0): 1, (1008, 1280, 1280): 1, (4032, 640, 640): 2, (96, 1280, 1280): 1, (384, 1280, 640): 1, (16128, 320, 0): 2}
+
+
 @pytest.mark.parametrize("B,HW,C1,C2,G,silu,bf16in", [(2, 256, 64, 0, 8, True, False), (3, 1024, 320, 0, 32, True, False),
                                                       (2, 64, 1280, 640, 32, True, False), (2, 4096, 640, 320, 32, True, False),
                                                       (2, 256, 320, 0, 32, False, False), (2, 1024, 96, 0, 8, True, True),
@@ -845,15 +858,17 @@ def test_cross_attn_block_fused_kernel_against_reference_arithmetic(B, N, Cc, H)
                                                       (3, 256, 1280, 1280, 32, True, "f16"), (7, 1024, 1280, 0, 32, False, "f16"),
                                                       (2, 4096, 640, 0, 32, True, "f16"), (3, 1024, 640, 640, 32, True, "f16"),
                                                       (2, 1024, 1280, 640, 32, True, "f16"),
-                                                      # HW that are not powers of two: the maps of SDXL 96x168 (1008 / 4032 / 16128) and SD-v1.5 64x96 (96 / 384).
-                                                      # By csrc/norm.hip gn_fused_vw (HW <= 1024 and HW x channels per group <= 98304) the cases with
-                                                      # HW 1008 (40 and 80 channels per group), 96 (80) and 384 (60: 4-wide loads) take the ONE-launch form,
-                                                      # HW 4032 and the fp32-input 16128 the two-launch form; there is no host query of that rule, so a
-                                                      # change of it has to revisit this list
+                                                      # HW that are not powers of two: the maps of SDXL 96x168 (1008 / 4032 / 16128) and SD-v1.5 64x96 (96 / 384);
+                                                      # the form each of them takes is asserted through rt_op_groupnorm_form (GN_FORM_NOT_POW2 below)
                                                       (7, 1008, 1280, 0, 32, True, "f16"), (7, 1008, 1280, 1280, 32, True, "f16"),
                                                       (2, 4032, 640, 640, 32, True, "f16"), (3, 96, 1280, 1280, 32, True, "f16"),
                                                       (3, 384, 1280, 640, 32, True, "f16"), (1, 16128, 320, 0, 32, True, False)])
 def test_groupnorm(B, HW, C1, C2, G, silu, bf16in):
+    from rich_text_to_image_amd.engine import load_library
+    lib = load_library()
+    if (HW, C1, C2) in GN_FORM_NOT_POW2:
+        in_type = 2 if bf16in == "f16" else 1 if bf16in else 0
+        assert lib.rt_op_groupnorm_form(in_type, C1, C2, G, B, HW) == GN_FORM_NOT_POW2[(HW, C1, C2)], (HW, C1, C2)
     x1 = rnd(B, HW, C1, seed=60) * 2 + 0.5
     x2 = rnd(B, HW, C2, seed=61) - 0.3 if C2 else None
     gamma, beta = (1 + 0.1 * rnd(C1 + C2, seed=62)).to(DEV), (0.1 * rnd(C1 + C2, seed=63)).to(DEV)
@@ -874,8 +889,6 @@ def test_groupnorm(B, HW, C1, C2, G, silu, bf16in):
     report("groupnorm raw copy", raw, xc, atol=1e-2, rtol=8e-3)
     # round 6: shapes where one workgroup owns a whole (batch entry, group) run as ONE launch; rt_op_gemm_debug bit 23 = the two-launch
     # form.  Same statistics to fp32 rounding, and an image alone equals the same image in the batch in either form.
-    from rich_text_to_image_amd.engine import load_library
-    lib = load_library()
     try:
         lib.rt_op_gemm_debug(1 << 23)
         two = groupnorm(xin1, xin2, G, gamma, beta, eps, silu)
