@@ -145,13 +145,10 @@ static inline bool cross77_route(int heads, int DP, int d, int tokens, int promp
 }
 // ... and debug bit 17 is clear.
 static inline bool store_handover_cross(bool on_cross77) { return on_cross77 && !g_store_own_stats_flag(); }
-// step epilogue kernels (defined in step.hip)
+// step epilogue (defined in step.hip)
 struct StepArgs;
-void launch_step_epilogue(const StepArgs& a, hipStream_t st);
-struct DpmArgs;
-void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st);
-struct StochArgs;
-void launch_step_epilogue_stoch(const StepArgs& a, const StochArgs& d, hipStream_t st);
+struct SolverArgs;
+void launch_step_epilogue(const StepArgs& a, const SolverArgs& d, hipStream_t st);
 void launch_step_noise(unsigned long long seed, int step, int HW, float* out, unsigned* words, hipStream_t st);
 // the SDE kinds share the DPM kinds' tables, x0 history and family rule; Euler ancestral shares Euler's tables, input scaling and family rule
 static inline bool rt_sched_is_dpm(int kind) {
@@ -191,6 +188,14 @@ static void launch_cross_runs(const AttnArgs& a, hipStream_t st) {
         b0 = b1;
     }
 }
+
+// multistep state of the running schedule
+struct SolverState {
+    int pndm_counter = 0, pndm_nets = 0, pndm_head = 0;
+    int dpm_lower_order_nums = 0, dpm_head = 0;     // DPM-Solver++: steps taken (capped at 2), history slot this step writes
+    int steps_done = 0;
+    void reset() { *this = SolverState{}; }
+};
 
 struct rt_engine {
     rt_config cfg;
@@ -248,9 +253,7 @@ struct rt_engine {
     // schedule (host)
     int sched_kind = 0, num_inference_steps = 0;
     std::vector<float> timesteps, table;
-    int pndm_counter = 0, pndm_nets = 0, pndm_head = 0;
-    int dpm_lower_order_nums = 0, dpm_head = 0;     // DPM-Solver++: steps taken (capped at 2), history slot this step writes
-    int steps_done = 0;
+    SolverState solver;              // reset by rt_set_schedule / rt_set_latents / rt_noise_latents
     // rt_set_prediction: what the UNet predicts (0 epsilon, 1 v) and the CFG rescale phi; (0, 0) launches nothing new.  Survive rt_set_schedule / rt_set_latents.
     int prediction_type = 0;
     float guidance_rescale = 0.f;
@@ -1055,6 +1058,7 @@ struct rt_engine {
     void region_step(int i, float g, double inject_selfattn, double inject_background, bool xl, bool elide, bool defer_blend);
     void region_plan(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend, FwdIn& in, StepArgs& a, bool& blend_out, bool& inject_out);
     void region_finish(int i, StepArgs& a, bool blend_deferred);
+    void finish_step(int i, StepArgs& a);
     // intra-image split (step_driver.inl): the forwards of this rank's contiguous stream range, then - after the ranks exchanged their
     // slices of `eps` - the epilogue on all of them
     void region_step_part(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend, int part, int nparts, int* first, int* count, int* plan_info);
@@ -1256,8 +1260,7 @@ int rt_set_schedule(rt_engine* e, int kind, const float* ts, int nts, const floa
         }
         e->sched_kind = kind; e->num_inference_steps = nsteps;
         e->timesteps.assign(ts, ts + nts); e->table.assign(table, table + ntab);
-        e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
-        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
+        e->solver.reset();
     })
 }
 int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
@@ -1268,8 +1271,7 @@ int rt_set_latents(rt_engine* e, const float* l, int h, int w) {
         HIP_CHECK(hipMemcpyAsync(e->lat, l, n, hipMemcpyDeviceToDevice, e->stream));
         HIP_CHECK(hipMemcpyAsync(e->lat_ref, l, n, hipMemcpyDeviceToDevice, e->stream));
         e->lat_h = h; e->lat_w = w;
-        e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
-        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
+        e->solver.reset();
     })
 }
 int rt_set_noise_seed(rt_engine* e, unsigned long long seed) { RT_TRY(e, { e->noise_seed = seed; }) }
@@ -1304,8 +1306,7 @@ int rt_noise_latents(rt_engine* e, float a, float b) {
         if (!e->has_source) throw rt_error(RT_E_STATE, "rt_noise_latents: no source (rt_set_source)");
         launch_noise_latents(e->lat, e->lat_ref, e->src_x0, e->src_noise, a, b, 4 * e->src_h * e->src_w, e->stream);
         e->lat_h = e->src_h; e->lat_w = e->src_w;
-        e->pndm_counter = 0; e->pndm_nets = 0; e->pndm_head = 0; e->steps_done = 0;
-        e->dpm_lower_order_nums = 0; e->dpm_head = 0;
+        e->solver.reset();
     })
 }
 int rt_source_blend(rt_engine* e, float a, float b) {

@@ -1,7 +1,7 @@
 // Guided-prediction pre-pass: CFG rescale (rescale_noise_cfg, models/region_diffusion_sdxl.py:42-53) and v-prediction for every sampler.
-// Runs only when the engine's prediction type is v or its rescale phi > 0 (rt_set_prediction); the three step epilogues of step.hip are
-// untouched and afterwards read `gpred` as a plain two-stream eps buffer whose "unconditional" and "text" slots coincide
-// (E + g (E - E) = E), so they reproduce the value made here.
+// Runs only when the engine's prediction type is v or its rescale phi > 0 (rt_set_prediction); the step epilogue of step.hip (whichever solver) is
+// untouched and afterwards reads `gpred` as a plain two-stream eps buffer whose "unconditional" and "text" slots coincide
+// (E + g (E - E) = E), so it reproduces the value made here.
 //
 //   compose:  per pixel the mask combine + CFG of step_combine (step.hip) in its fp32 operation order, every product-sum one fma:
 //               text = nt, cfg = nu + g (nt - nu);  while the reference pair is stepped: text_r = eps[s_tref], cfg_r = a + g (b - a)

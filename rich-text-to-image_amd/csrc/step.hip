@@ -1,94 +1,16 @@
 // a11 + a12 + a14 of SURVEY.md section 8a: mask-weighted region combine (models/region_diffusion.py:119-132,
 // models/region_diffusion_sdxl.py:810-825), classifier-free guidance, scheduler update (third-party
-// diffusers 0.18.2 PNDM/PLMS and Euler restated, see oracle/schedulers.py; DPM-Solver++ in a second kernel, the stochastic samplers in a third) and background blend
+// diffusers 0.18.2 PNDM/PLMS, Euler, DPM-Solver++, Euler ancestral and SDE-DPM-Solver++ restated, see oracle/schedulers.py,
+// tests/dpm_solver_ref.py and tests/sde_ref.py) and background blend
 // (rd.py:171-173, xl.py:870-872) fused into one elementwise launch over 4*h*w elements.
 // The arithmetic follows the reference's fp32 operation order so that the epilogue itself is exact.
+// One kernel body, instantiated per solver: the guard that kept the PLMS / Euler kernel's ISA byte-identical (and with it three copies
+// of the head and tail) was lifted here; what holds is the latents' bits and the step's time (profiles/step_epilogue_unified.txt).
 #include "step.h"
 #include "philox.h"
 #include "../../include/rtdiff.h"
 
-__global__ void step_epilogue_kernel(StepArgs p) {
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= p.HW) return;
-    auto ld4 = [&](int s) { return *(const float4*)(p.eps + ((size_t)s * p.HW + pix) * 4); };
-    float e[4], er[4];
-    const float4 eu = ld4(p.s_uncond), eb = ld4(p.s_base);
-    const float euv[4] = {eu.x, eu.y, eu.z, eu.w}, ebv[4] = {eb.x, eb.y, eb.z, eb.w};
-    if (p.plain) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) e[c] = euv[c] + p.g * (ebv[c] - euv[c]);
-    } else {
-        float nu[4], nt[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float ml = p.masks[((size_t)(p.R - 1) * 4 + c) * p.HW + pix];
-            nu[c] = euv[c] * ml; nt[c] = ebv[c] * ml;
-        }
-        for (int r = 0; r < p.R - 1; ++r) {
-            const float4 q = ld4(p.s_region[r]);
-            const float qv[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float m = p.masks[((size_t)r * 4 + c) * p.HW + pix];
-                nu[c] = nu[c] + euv[c] * m; nt[c] = nt[c] + qv[c] * m;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) e[c] = nu[c] + p.g * (nt[c] - nu[c]);
-    }
-    if (p.noise_pred) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) p.noise_pred[(size_t)c * p.HW + pix] = e[c];
-    }
-    const bool has_ref = p.s_uref >= 0 && p.step_ref;
-    if (has_ref) {
-        const float4 a = ld4(p.s_uref), b = ld4(p.s_tref);
-        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) er[c] = av[c] + p.g * (bv[c] - av[c]);
-    }
-    const int nstream = has_ref ? 2 : 1;
-    float newv[2][4];
-    for (int s = 0; s < nstream; ++s) {
-        float* x = s == 0 ? p.lat : p.lat_ref;
-        const float* ee = s == 0 ? e : er;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const size_t li = (size_t)c * p.HW + pix;
-            const size_t hi = (size_t)s * 4 * p.HW + li;
-            float sample = x[li];
-            float ep = ee[c];
-            if (p.sched == RT_SCHED_EULER) {
-                // pred_x0 = x - sigma*eps; derivative = (x - pred_x0)/sigma; x += derivative * dsigma  (gamma = 0)
-                newv[s][c] = sample + ep * p.dsigma;
-            } else {
-                if (p.push) p.ets[0][hi] = ep;
-                if (p.pndm_mode == 0) { p.cur_sample[hi] = sample; }
-                else if (p.pndm_mode == 1) { ep = (ep + p.ets[1][hi]) / 2.f; sample = p.cur_sample[hi]; }
-                else if (p.pndm_mode == 2) { ep = (3.f * ep - p.ets[1][hi]) / 2.f; }
-                else if (p.pndm_mode == 3) { ep = (23.f * ep - 16.f * p.ets[1][hi] + 5.f * p.ets[2][hi]) / 12.f; }
-                else { ep = (1.f / 24.f) * (55.f * ep - 59.f * p.ets[1][hi] + 37.f * p.ets[2][hi] - 9.f * p.ets[3][hi]); }
-                newv[s][c] = p.ca * sample - p.cb * ep;
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const size_t li = (size_t)c * p.HW + pix;
-        float l = newv[0][c];
-        const float lr = has_ref ? newv[1][c] : p.lat_ref[li];
-        if (p.blend) {
-            const float ml = p.masks[((size_t)(p.R - 1) * 4 + c) * p.HW + pix];
-            l = lr * ml + l * (1.f - ml);
-        }
-        p.lat[li] = l;
-        if (has_ref) p.lat_ref[li] = lr;
-    }
-}
-// DPM-Solver++ epilogue (diffusers 0.18.2 DPMSolverMultistepScheduler: dpmsolver++, midpoint, epsilon; [memory], see
-// tests/dpm_solver_ref.py).  A kernel of its own so that step_epilogue_kernel above keeps its code unchanged (an inlined shared body
-// reorders its instructions and moves its SGPR count; profiles/dpm_epilogue_isa_diff.txt): the combine + CFG head and the blend / store
-// tail below are step_epilogue_kernel's, only the scheduler update differs.
+// mask combine + CFG of the main stream into e and, while the reference pair is stepped, of the pair into er; returns has_ref
 __device__ __forceinline__ bool step_combine(const StepArgs& p, int pix, float (&e)[4], float (&er)[4]) {
     auto ld4 = [&](int s) { return *(const float4*)(p.eps + ((size_t)s * p.HW + pix) * 4); };
     const float4 eu = ld4(p.s_uncond), eb = ld4(p.s_base);
@@ -128,6 +50,7 @@ __device__ __forceinline__ bool step_combine(const StepArgs& p, int pix, float (
     }
     return has_ref;
 }
+// background blend + store of the stepped streams
 __device__ __forceinline__ void step_store(const StepArgs& p, int pix, const float (&newv)[2][4], bool has_ref) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -142,45 +65,56 @@ __device__ __forceinline__ void step_store(const StepArgs& p, int pix, const flo
         if (has_ref) p.lat_ref[li] = lr;
     }
 }
-// Per stream, in diffusers' fp32 operation order: this step's x0 goes to the stream's history slot ets[0]; m1 (the stream's x0 of the
-// previous step) comes from ets[1] in the same pass.
-__global__ void step_epilogue_dpm_kernel(StepArgs p, DpmArgs d) {
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pix >= p.HW) return;
-    float e[4], er[4];
-    const bool has_ref = step_combine(p, pix, e, er);
-    float newv[2][4];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        if (s == 1 && !has_ref) break;
-        const float* x = s == 0 ? p.lat : p.lat_ref;
-        const float* ee = s == 0 ? e : er;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const size_t li = (size_t)c * p.HW + pix;
-            const size_t hi = (size_t)s * 4 * p.HW + li;
-            const float sample = x[li];
-            const float x0 = (sample - d.sigma_s0 * ee[c]) / d.alpha_s0;
-            float v = d.ratio * sample - d.c1 * x0;
-            if (d.order == 2) v = v - d.c2 * (d.inv_r0 * (x0 - p.ets[1][hi]));
-            p.ets[0][hi] = x0;
-            newv[s][c] = v;
+// One element of one stream through solver S, in diffusers' fp32 operation order.  hi = the element's index in the stream's half of a
+// history slot.  PLMS keeps its eps history in ets[0..3] and the warm-up sample in cur_sample; DPM / SDE write this step's x0 to ets[0]
+// and read m1 (the stream's x0 of the previous step) from ets[1] in the same pass.
+template <int S>
+__device__ __forceinline__ float step_update(const SolverArgs& d, float sample, float ep, float z, size_t hi) {
+    if constexpr (S == STEP_PLMS) {
+        if (d.push) d.ets[0][hi] = ep;
+        if (d.pndm_mode == 0) { d.cur_sample[hi] = sample; }
+        else if (d.pndm_mode == 1) { ep = (ep + d.ets[1][hi]) / 2.f; sample = d.cur_sample[hi]; }
+        else if (d.pndm_mode == 2) { ep = (3.f * ep - d.ets[1][hi]) / 2.f; }
+        else if (d.pndm_mode == 3) { ep = (23.f * ep - 16.f * d.ets[1][hi] + 5.f * d.ets[2][hi]) / 12.f; }
+        else { ep = (1.f / 24.f) * (55.f * ep - 59.f * d.ets[1][hi] + 37.f * d.ets[2][hi] - 9.f * d.ets[3][hi]); }
+        {
+            // pinned to three roundings (two products, a subtraction) in every element: the bits the separate PLMS / Euler kernel gave,
+            // whose compiler happened not to fuse this line.  Left to the compiler, this body fuses some elements and not others; the
+            // fp64 tests tolerate either form, the pin keeps the latents' bits
+#pragma clang fp contract(off)
+            return d.ca * sample - d.cb * ep;
         }
+    } else if constexpr (S == STEP_EULER) {
+        // pred_x0 = x - sigma*eps; derivative = (x - pred_x0)/sigma; x += derivative * dsigma  (gamma = 0)
+        return sample + ep * d.dsigma;
+    } else if constexpr (S == STEP_EULER_A) {
+        return sample + ep * d.dsigma + z * d.cn;
+    } else {
+        const float x0 = (sample - d.sigma_s0 * ep) / d.alpha_s0;
+        float v;
+        if constexpr (S == STEP_DPM) {
+            v = d.ratio * sample - d.c1 * x0;
+            if (d.order == 2) v = v - d.c2 * (d.inv_r0 * (x0 - d.ets[1][hi]));
+        } else {
+            v = d.ratio * sample + d.c1 * x0;
+            if (d.order == 2) v = v + d.c2 * (d.inv_r0 * (x0 - d.ets[1][hi]));
+        }
+        d.ets[0][hi] = x0;
+        if constexpr (S == STEP_SDE) v = v + d.cn * z;
+        return v;
     }
-    step_store(p, pix, newv, has_ref);
 }
-// Stochastic epilogue (Euler ancestral; SDE-DPM-Solver++ of order 1 / 2: diffusers' EulerAncestralDiscreteScheduler and
-// DPMSolverMultistepScheduler with algorithm_type="sde-dpmsolver++", [memory], see tests/sde_ref.py).  A third kernel for the reason the
-// DPM one is a second.  One Philox call per pixel gives the four channels' normals of this step; the SAME values go to the main and the
-// reference latents, so streams that are equal before the step are equal after it and the reference stream of a rich pass sees the
+// The stochastic solvers draw one Philox call per pixel for the four channels' normals of this step; the SAME values go to the main and
+// the reference latents, so streams that are equal before the step are equal after it and the reference stream of a rich pass sees the
 // noise the plain pass saw.
-__global__ void step_epilogue_stoch_kernel(StepArgs p, StochArgs d) {
+template <int S>
+__global__ void step_epilogue_kernel(StepArgs p, SolverArgs d) {
     const int pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= p.HW) return;
     float e[4], er[4];
     const bool has_ref = step_combine(p, pix, e, er);
-    float z[4];
-    step_noise4(d.seed_lo, d.seed_hi, (unsigned)d.step, (unsigned)pix, z);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (S == STEP_EULER_A || S == STEP_SDE) step_noise4(d.seed_lo, d.seed_hi, (unsigned)d.step, (unsigned)pix, z);
     float newv[2][4];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -190,17 +124,7 @@ __global__ void step_epilogue_stoch_kernel(StepArgs p, StochArgs d) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const size_t li = (size_t)c * p.HW + pix;
-            const size_t hi = (size_t)s * 4 * p.HW + li;
-            const float sample = x[li];
-            if (d.euler) {
-                newv[s][c] = sample + ee[c] * d.dsig + z[c] * d.cn;
-            } else {
-                const float x0 = (sample - d.sigma_s0 * ee[c]) / d.alpha_s0;
-                float v = d.ratio * sample + d.c1 * x0;
-                if (d.order == 2) v = v + d.c2 * (d.inv_r0 * (x0 - p.ets[1][hi]));
-                p.ets[0][hi] = x0;
-                newv[s][c] = v + d.cn * z[c];
-            }
+            newv[s][c] = step_update<S>(d, x[li], ee[c], z[c], (size_t)s * 4 * p.HW + li);
         }
     }
     step_store(p, pix, newv, has_ref);
@@ -214,17 +138,20 @@ __global__ void step_noise_kernel(unsigned seed_lo, unsigned seed_hi, int step, 
 #pragma unroll
     for (int c = 0; c < 4; ++c) out[(size_t)c * HW + pix] = z[c];
 }
-void launch_step_epilogue(const StepArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(step_epilogue_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a);
+template <int S>
+static void launch_step_solver(const StepArgs& a, const SolverArgs& d, hipStream_t st) {
+    hipLaunchKernelGGL(step_epilogue_kernel<S>, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
     HIP_CHECK(hipGetLastError());
 }
-void launch_step_epilogue_dpm(const StepArgs& a, const DpmArgs& d, hipStream_t st) {
-    hipLaunchKernelGGL(step_epilogue_dpm_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
-    HIP_CHECK(hipGetLastError());
-}
-void launch_step_epilogue_stoch(const StepArgs& a, const StochArgs& d, hipStream_t st) {
-    hipLaunchKernelGGL(step_epilogue_stoch_kernel, dim3(cdiv(a.HW, 256)), dim3(256), 0, st, a, d);
-    HIP_CHECK(hipGetLastError());
+void launch_step_epilogue(const StepArgs& a, const SolverArgs& d, hipStream_t st) {
+    switch (d.solver) {
+    case STEP_PLMS: return launch_step_solver<STEP_PLMS>(a, d, st);
+    case STEP_EULER: return launch_step_solver<STEP_EULER>(a, d, st);
+    case STEP_DPM: return launch_step_solver<STEP_DPM>(a, d, st);
+    case STEP_EULER_A: return launch_step_solver<STEP_EULER_A>(a, d, st);
+    case STEP_SDE: return launch_step_solver<STEP_SDE>(a, d, st);
+    }
+    RT_REQUIRE(false, "step epilogue: no such solver");
 }
 void launch_step_noise(unsigned long long seed, int step, int HW, float* out, unsigned* words, hipStream_t st) {
     hipLaunchKernelGGL(step_noise_kernel, dim3(cdiv(HW, 256)), dim3(256), 0, st, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step, HW, out,

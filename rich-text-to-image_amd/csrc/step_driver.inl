@@ -1,25 +1,26 @@
 // Host step drivers (included by engine.hip).  Flag logic follows the reference loops line by line:
 //   SD  : models/region_diffusion.py:99-173        XL : models/region_diffusion_sdxl.py:779-872
 
-static void pndm_coeffs(rt_engine* e, int i, StepArgs& a) {
+static void pndm_coeffs(rt_engine* e, int i, SolverArgs& a) {
     // PNDMScheduler.step_plms (diffusers 0.18.2, [memory]); see oracle/schedulers.py:OraclePNDM
+    SolverState& st = e->solver;
     const int ratio = 1000 / e->num_inference_steps;
     int t = (int)e->timesteps[i];
     int prev_t = t - ratio;
     a.push = 0;
-    if (e->pndm_counter != 1) {
+    if (st.pndm_counter != 1) {
         a.push = 1;
-        if (e->pndm_nets < 4) e->pndm_nets++;
-        e->pndm_head = (e->pndm_head + 3) & 3;        // new newest slot
+        if (st.pndm_nets < 4) st.pndm_nets++;
+        st.pndm_head = (st.pndm_head + 3) & 3;        // new newest slot
     } else {
         prev_t = t; t = t + ratio;
     }
     const size_t per = (size_t)2 * 4 * e->lat_h * e->lat_w;
-    for (int k = 0; k < 4; ++k) a.ets[k] = e->ets + (size_t)((e->pndm_head + k) & 3) * per;
+    for (int k = 0; k < 4; ++k) a.ets[k] = e->ets + (size_t)((st.pndm_head + k) & 3) * per;
     if (!a.push) { for (int k = 3; k >= 1; --k) a.ets[k] = a.ets[k - 1]; }   // ets[1] = newest stored
-    if (e->pndm_nets == 1 && e->pndm_counter == 0) a.pndm_mode = 0;
-    else if (e->pndm_nets == 1 && e->pndm_counter == 1) a.pndm_mode = 1;
-    else a.pndm_mode = e->pndm_nets;   // 2, 3, 4
+    if (st.pndm_nets == 1 && st.pndm_counter == 0) a.pndm_mode = 0;
+    else if (st.pndm_nets == 1 && st.pndm_counter == 1) a.pndm_mode = 1;
+    else a.pndm_mode = st.pndm_nets;   // 2, 3, 4
     RT_REQUIRE((int)e->table.size() >= 1000, "pndm: alphas_cumprod table missing");
     const double a_t = e->table[t], a_p = prev_t >= 0 ? e->table[prev_t] : e->table[0];
     const double b_t = 1 - a_t, b_p = 1 - a_p;
@@ -29,27 +30,28 @@ static void pndm_coeffs(rt_engine* e, int i, StepArgs& a) {
     const float denom = fa_t * std::sqrt(fb_p) + std::sqrt(fa_t * fb_t * fa_p);
     a.ca = sample_coeff; a.cb = (fa_p - fa_t) / denom;
     a.cur_sample = e->cur_sample;
-    e->pndm_counter++;
+    st.pndm_counter++;
 }
 
-static void dpm_coeffs(rt_engine* e, int i, StepArgs& a, DpmArgs& d) {
-    // DPMSolverMultistepScheduler (diffusers 0.18.2, [memory]: dpmsolver++, midpoint, epsilon, lower_order_final, no thresholding);
-    // see tests/dpm_solver_ref.py.  fp32 scalars in diffusers' tensor order: alpha = sqrt(ac), sigma = sqrt(1 - ac),
-    // lambda = log(alpha) - log(sigma); s0 = t_i, s1 = t_{i-1}, p = t_{i+1} (0 after the last step).
-    RT_REQUIRE((int)e->table.size() >= 1000, "dpm-solver++: alphas_cumprod table missing");
+// What DPM-Solver++ and SDE-DPM-Solver++ share (DPMSolverMultistepScheduler, diffusers 0.18.2, [memory]: midpoint, epsilon,
+// lower_order_final, no thresholding; see tests/dpm_solver_ref.py and tests/sde_ref.py).  fp32 scalars in diffusers' tensor order:
+// alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha) - log(sigma); s0 = t_i, s1 = t_{i-1}, p = t_{i+1} (0 after the last step).
+// Fills alpha_s0, sigma_s0, order, inv_r0 and the history slots, advances the solver state; the callers add ratio / c1 / c2 (and cn).
+struct MultistepPoint { float h, alpha_p, sigma_p; };
+static MultistepPoint multistep_coeffs(rt_engine* e, int i, bool single_step, SolverArgs& d) {
+    const std::string who = rt_sched_is_stoch(e->sched_kind) ? "sde-dpm-solver++" : "dpm-solver++";
+    RT_REQUIRE((int)e->table.size() >= 1000, who + ": alphas_cumprod table missing");
     const int n = (int)e->timesteps.size();
-    RT_REQUIRE(i >= 0 && i < n, "dpm-solver++: step index out of range");
+    RT_REQUIRE(i >= 0 && i < n, who + ": step index out of range");
+    SolverState& st = e->solver;
     auto alpha = [&](int t) { return std::sqrt(e->table[t]); };
     auto sigma = [&](int t) { return std::sqrt(1.f - e->table[t]); };
     auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
     const int s0 = (int)e->timesteps[i], p = i == n - 1 ? 0 : (int)e->timesteps[i + 1];
     const bool lower_order_final = i == n - 1 && n < 15;
-    const bool first = e->sched_kind == RT_SCHED_DPMPP_1 || e->dpm_lower_order_nums < 1 || lower_order_final || i == 0;
+    const bool first = single_step || st.dpm_lower_order_nums < 1 || lower_order_final || i == 0;
     const float h = lambda(p) - lambda(s0);
     d.alpha_s0 = alpha(s0); d.sigma_s0 = sigma(s0);
-    d.ratio = sigma(p) / sigma(s0);
-    d.c1 = alpha(p) * (std::exp(-h) - 1.f);
-    d.c2 = 0.5f * d.c1;
     d.order = first ? 1 : 2;
     d.inv_r0 = 0.f;
     if (!first) {
@@ -60,62 +62,52 @@ static void dpm_coeffs(rt_engine* e, int i, StepArgs& a, DpmArgs& d) {
     // two history slots per stream in the PNDM buffer ([slot][stream][4*HW]): this step writes x0 into one and reads m1 from the other.
     // A stream that is not stepped (the reference pair once it stops) leaves its half of both slots alone and is never stepped again.
     const size_t per = (size_t)2 * 4 * e->lat_h * e->lat_w;
-    a.ets[0] = e->ets + (size_t)e->dpm_head * per;
-    a.ets[1] = e->ets + (size_t)(e->dpm_head ^ 1) * per;
-    e->dpm_head ^= 1;
-    if (e->dpm_lower_order_nums < 2) e->dpm_lower_order_nums++;
+    d.ets[0] = e->ets + (size_t)st.dpm_head * per;
+    d.ets[1] = e->ets + (size_t)(st.dpm_head ^ 1) * per;
+    st.dpm_head ^= 1;
+    if (st.dpm_lower_order_nums < 2) st.dpm_lower_order_nums++;
+    return {h, alpha(p), sigma(p)};
 }
 
-static void stoch_coeffs(rt_engine* e, int i, StepArgs& a, StochArgs& d) {
-    // The stochastic samplers ([memory], see tests/sde_ref.py); fp32 scalars, evaluated left to right.  The noise field of the step is
-    // a function of (noise_seed, i, pixel): csrc/philox.h.
-    const int n = (int)e->timesteps.size();
-    RT_REQUIRE(i >= 0 && i < n, "stochastic sampler: step index out of range");
-    d.seed_lo = (unsigned)(e->noise_seed & 0xffffffffull); d.seed_hi = (unsigned)(e->noise_seed >> 32); d.step = i;
-    if (e->sched_kind == RT_SCHED_EULER_A) {
+// The solver of sched_kind and its scalars of step i; fp32, evaluated left to right.
+static void solver_coeffs(rt_engine* e, int i, SolverArgs& d) {
+    const int kind = e->sched_kind;
+    if (kind == RT_SCHED_PNDM) { d.solver = STEP_PLMS; pndm_coeffs(e, i, d); return; }
+    if (kind == RT_SCHED_EULER) { d.solver = STEP_EULER; d.dsigma = e->table[i + 1] - e->table[i]; return; }
+    if (rt_sched_is_stoch(kind)) {
+        // the noise field of the step is a function of (noise_seed, i, pixel): csrc/philox.h
+        RT_REQUIRE(i >= 0 && i < (int)e->timesteps.size(), "stochastic sampler: step index out of range");
+        d.seed_lo = (unsigned)(e->noise_seed & 0xffffffffull); d.seed_hi = (unsigned)(e->noise_seed >> 32); d.step = i;
+    }
+    if (kind == RT_SCHED_EULER_A) {
         // EulerAncestralDiscreteScheduler: sigma_up = sqrt(s'^2 (s^2 - s'^2) / s^2), sigma_down = sqrt(s'^2 - sigma_up^2);
         // x' = x + eps (sigma_down - s) + z sigma_up.  The last step has s' = 0: no noise.
         const float sg = e->table[i], sp = e->table[i + 1];
         const float up = std::sqrt(sp * sp * (sg * sg - sp * sp) / (sg * sg));
         const float down = std::sqrt(sp * sp - up * up);
-        d.euler = 1; d.dsig = down - sg; d.cn = up;
+        d.solver = STEP_EULER_A; d.dsigma = down - sg; d.cn = up;
         return;
     }
-    // DPMSolverMultistepScheduler, algorithm_type="sde-dpmsolver++", midpoint: alpha, sigma, lambda, s0, s1, p, h, r0, the order rule and
-    // the x0 history exactly as dpm_coeffs above.
-    //   x' = (sigma_p / sigma_s0 exp(-h)) x + alpha_p (1 - exp(-2h)) x0 [+ 0.5 alpha_p (1 - exp(-2h)) (1 / r0) (x0 - m1)] + sigma_p sqrt(1 - exp(-2h)) z
-    RT_REQUIRE((int)e->table.size() >= 1000, "sde-dpm-solver++: alphas_cumprod table missing");
-    auto alpha = [&](int t) { return std::sqrt(e->table[t]); };
-    auto sigma = [&](int t) { return std::sqrt(1.f - e->table[t]); };
-    auto lambda = [&](int t) { return std::log(alpha(t)) - std::log(sigma(t)); };
-    const int s0 = (int)e->timesteps[i], p = i == n - 1 ? 0 : (int)e->timesteps[i + 1];
-    const bool lower_order_final = i == n - 1 && n < 15;
-    const bool first = e->sched_kind == RT_SCHED_DPMPP_SDE_1 || e->dpm_lower_order_nums < 1 || lower_order_final || i == 0;
-    const float h = lambda(p) - lambda(s0);
-    const float q = 1.f - std::exp(-2.f * h);
-    d.euler = 0;
-    d.alpha_s0 = alpha(s0); d.sigma_s0 = sigma(s0);
-    d.ratio = sigma(p) / sigma(s0) * std::exp(-h);
-    d.c1 = alpha(p) * q;
-    d.c2 = 0.5f * d.c1;
-    d.cn = sigma(p) * std::sqrt(q);
-    d.order = first ? 1 : 2;
-    d.inv_r0 = 0.f;
-    if (!first) {
-        const int s1 = (int)e->timesteps[i - 1];
-        const float r0 = (lambda(s0) - lambda(s1)) / h;
-        d.inv_r0 = 1.f / r0;
+    const bool sde = rt_sched_is_stoch(kind);
+    const MultistepPoint m = multistep_coeffs(e, i, kind == RT_SCHED_DPMPP_1 || kind == RT_SCHED_DPMPP_SDE_1, d);
+    if (!sde) {
+        d.solver = STEP_DPM;
+        d.ratio = m.sigma_p / d.sigma_s0;
+        d.c1 = m.alpha_p * (std::exp(-m.h) - 1.f);
+    } else {
+        //   x' = (sigma_p / sigma_s0 exp(-h)) x + alpha_p (1 - exp(-2h)) x0 [+ 0.5 alpha_p (1 - exp(-2h)) (1 / r0) (x0 - m1)] + sigma_p sqrt(1 - exp(-2h)) z
+        const float q = 1.f - std::exp(-2.f * m.h);
+        d.solver = STEP_SDE;
+        d.ratio = m.sigma_p / d.sigma_s0 * std::exp(-m.h);
+        d.c1 = m.alpha_p * q;
+        d.cn = m.sigma_p * std::sqrt(q);
     }
-    const size_t per = (size_t)2 * 4 * e->lat_h * e->lat_w;
-    a.ets[0] = e->ets + (size_t)e->dpm_head * per;
-    a.ets[1] = e->ets + (size_t)(e->dpm_head ^ 1) * per;
-    e->dpm_head ^= 1;
-    if (e->dpm_lower_order_nums < 2) e->dpm_lower_order_nums++;
+    d.c2 = 0.5f * d.c1;
 }
 
 // The streams of rich-text step i and the flags of its epilogue (everything of region_step that is a pure function of the schedule
 // position): `in` = the F batched forwards with their mode words, `a` = the epilogue's arguments without the scheduler coefficients
-// (PNDM's are stateful: region_finish computes them once).
+// (PNDM's are stateful: finish_step computes them once).
 void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend, FwdIn& in, StepArgs& a, bool& blend_out,
                             bool& inject_out) {
     require_bound();
@@ -166,7 +158,7 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     in.B = F;
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = R; a.g = g; a.plain = 0;
     a.noise_pred = noise_pred;
-    a.sched = sched_kind; a.step_ref = step_ref ? 1 : 0; a.blend = (blend && !defer_blend) ? 1 : 0;
+    a.step_ref = step_ref ? 1 : 0; a.blend = (blend && !defer_blend) ? 1 : 0;
     blend_out = blend && defer_blend;
     inject_out = feat && run_ref;
 }
@@ -199,29 +191,20 @@ void rt_engine::guided_prepass(int i, StepArgs& a) {
     a.eps = gpred; a.plain = 1; a.s_uncond = a.s_base = 0; a.s_uref = a.s_tref = has_ref ? 1 : -1;
 }
 
+// The epilogue of step i on the planned arguments: the guided pre-pass when the prediction needs it, then the solver of sched_kind
+void rt_engine::finish_step(int i, StepArgs& a) {
+    if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
+    SolverArgs d{};
+    solver_coeffs(this, i, d);
+    launch_step_epilogue(a, d, stream);
+    solver.steps_done++;
+}
+
 // mask combine + CFG + scheduler step + blend on the eps of ALL streams of step i (models/region_diffusion.py:119-147,
 // region_diffusion_sdxl.py:810-846)
 void rt_engine::region_finish(int i, StepArgs& a, bool blend_deferred) {
     pending_blend = blend_deferred;
-    if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
-    if (rt_sched_is_stoch(sched_kind)) {
-        StochArgs d{};
-        stoch_coeffs(this, i, a, d);
-        launch_step_epilogue_stoch(a, d, stream);
-        steps_done++;
-        return;
-    }
-    if (rt_sched_is_dpm(sched_kind)) {
-        DpmArgs d{};
-        dpm_coeffs(this, i, a, d);
-        launch_step_epilogue_dpm(a, d, stream);
-        steps_done++;
-        return;
-    }
-    if (sched_kind == RT_SCHED_EULER) a.dsigma = table[i + 1] - table[i];
-    else pndm_coeffs(this, i, a);
-    launch_step_epilogue(a, stream);
-    steps_done++;
+    finish_step(i, a);
 }
 
 void rt_engine::region_step(int i, float g, double isa, double ibg, bool xl, bool elide, bool defer_blend) {
@@ -299,29 +282,10 @@ void rt_engine::plain_forward(int i, int first, int count) {
 }
 void rt_engine::plain_finish(int i, float g) {
     RT_REQUIRE(i >= 0 && i < (int)timesteps.size(), "plain_step: step index out of range");     // PNDM / Euler index their tables with it
-    const bool xl = rt_sched_is_euler(sched_kind);
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
-    a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.sched = sched_kind; a.step_ref = 0; a.blend = 0;
-    if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
-    if (rt_sched_is_stoch(sched_kind)) {
-        StochArgs d{};
-        stoch_coeffs(this, i, a, d);
-        launch_step_epilogue_stoch(a, d, stream);
-        steps_done++;
-        return;
-    }
-    if (rt_sched_is_dpm(sched_kind)) {
-        DpmArgs d{};
-        dpm_coeffs(this, i, a, d);
-        launch_step_epilogue_dpm(a, d, stream);
-        steps_done++;
-        return;
-    }
-    if (xl) a.dsigma = table[i + 1] - table[i];
-    else pndm_coeffs(this, i, a);
-    launch_step_epilogue(a, stream);
-    steps_done++;
+    a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.step_ref = 0; a.blend = 0;
+    finish_step(i, a);
 }
 void rt_engine::plain_step(int i, float g) {
     plain_forward(i, 0, 2);

@@ -2,7 +2,7 @@
 on the HIP engine.  Same method names / argument meaning / attributes as the reference."""
 import torch
 
-from . import img2img
+from . import denoise_loop, img2img
 from .engine import SD15_CONFIG
 from .schedulers import DPMSolverTables, PNDMTables, engine_prediction
 from .unet import HipUNet2DConditionModel
@@ -100,33 +100,9 @@ class RegionDiffusion:
                 out.append(self.text_encoder(ti.input_ids.to(self.device))[0])
         return out
 
-    # rd.py:238-246.  In order: a VAE object with `.encode` (the reference behaviour), the `vae_encoder` given to the constructor, an
-    # encoder built from `vae_dir` on the first call (sized to the largest image seen: rebuilt when a larger one arrives; the rich-text
-    # flow never encodes, so it pays nothing for this), else NotImplementedError.  The 2x - 1 and the 0.18215 run in the HIP kernels.
+    # rd.py:238-246 (denoise_loop.encode_imgs: `.encode` of the VAE object, `vae_encoder`, or an encoder built from `vae_dir`)
     def encode_imgs(self, imgs):
-        if hasattr(self.vae, "encode"):
-            imgs = 2 * imgs - 1
-            return self.vae.encode(imgs).latent_dist.sample() * 0.18215
-        enc = self.vae_encoder or self._encoder_from_dir(imgs.shape[-2], imgs.shape[-1])
-        if enc is None:
-            raise NotImplementedError("encode_imgs needs VAE encoder weights: a VAE with `.encode`, `vae_encoder=`, or an AutoencoderKL "
-                                      "directory whose weights hold `encoder.*` (this one is decoder-only)")
-        return enc.encode(imgs, in_scale=2.0, in_shift=-1.0).latent_dist.sample(scale=0.18215)
-
-    def _encoder_from_dir(self, H, W):
-        if self.vae_dir is None:
-            return None
-        lat = (-(-H // 8), -(-W // 8))
-        if self._lazy_encoder is not None:
-            enc = self._lazy_encoder[0]
-            if enc is None or (lat[0] <= enc.cfg.latent_h and lat[1] <= enc.cfg.latent_w):
-                return enc
-            lat = (max(lat[0], enc.cfg.latent_h), max(lat[1], enc.cfg.latent_w))
-            enc.close()
-        from .checkpoint import load_vae_encoder
-        enc = load_vae_encoder(self.vae_dir, "SD", self.device_index, lat, precise=getattr(self.vae, "precise", False))
-        self._lazy_encoder = (enc,)
-        return enc
+        return denoise_loop.encode_imgs(self, imgs, "SD", 0.18215, getattr(self.vae, "precise", False))
 
     def _schedule_kind(self):
         """The engine's schedule kind of self.scheduler: SD-v1.5 runs PNDM (the reference) or DPM-Solver++, nothing else."""
@@ -173,34 +149,10 @@ class RegionDiffusion:
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
-        levels = self._start(eng, latents, None if image is None else x0, keep)
-        for i, t in enumerate(self.scheduler.timesteps):
-            if getattr(self, "split_image", False):      # intra-image split over the ranks of the process group (launcher.split_region_step)
-                from .launcher import assert_ranks_agree, split_region_step
-                if i % 10 == 0:                          # every rank must hold the same masks / latents (homogeneous ranks): fail loudly otherwise
-                    if i == 0:
-                        assert_ranks_agree(torch.cat([m.reshape(-1).float().cpu() for m in self.masks]), "the region masks")
-                    assert_ranks_agree(eng.read_latents(latents.shape[-2], latents.shape[-1]), f"the latents before step {i}")
-                split_region_step(eng, i, guidance_scale, inject_selfattn, inject_background, False, elide=elide_dead_forwards, defer_blend=use_guidance)
-            else:
-                eng.region_step(i, guidance_scale, inject_selfattn, inject_background, xl=False, elide=elide_dead_forwards,
-                                defer_blend=use_guidance)
-            if use_guidance:
-                if t < tfd['guidance_start_step']:                           # rd.py:151
-                    lat_ptr, eps_ptr = eng.state_ptrs()
-
-                    def guide(lat_ptr=lat_ptr, eps_ptr=eps_ptr, t=t):
-                        self.vae.color_guidance(lat_ptr, eps_ptr, float(self.scheduler.alphas_cumprod[int(t)]), h, w, tfd['color_obj_atten'],
-                                                tfd['target_RGB'], tfd['color_guidance_weight'], tfd['color_obj_atten_all'])
-                    if getattr(self, "split_image", False):              # rank 0 runs the VAE pass, the others receive the updated latents
-                        from .launcher import guidance_from_rank0
-                        guidance_from_rank0(eng, guide, h, w)
-                    else:
-                        guide()
-                eng.background_blend()
-            if keep is not None:
-                eng.source_blend(*levels[i])
-        return self._finish(eng, h, w, image is not None)
+        levels = denoise_loop.start(self, eng, latents, None if image is None else x0, keep)
+        denoise_loop.rich_steps(self, eng, h, w, guidance_scale, inject_selfattn, inject_background, xl=False, elide=elide_dead_forwards,
+                                use_guidance=use_guidance, tfd=tfd, guidance_vae=self.vae, keep=keep, levels=levels)
+        return denoise_loop.finish(eng, h, w, image is not None)
 
     # image start (img2img.py): the noise is drawn where `latents` is drawn, so the plain and the rich pass of one seed share their start
     def _start_noise(self, image, noise):
@@ -210,22 +162,6 @@ class RegionDiffusion:
         if tuple(noise.shape) != (1, 4, h, w):
             raise ValueError(f"noise: expected {(1, 4, h, w)}, got {tuple(noise.shape)}")
         return noise
-
-    def _start(self, eng, latents, x0, keep):
-        """Sets the engine's start latents: `latents` as given, or - with a source x0 - a*x0 + b*latents at the scheduler's start level
-        (`latents` is the noise then).  Returns the per-iteration source levels (None without a source)."""
-        if x0 is None:
-            eng.set_latents(latents.to(self.device))
-            return None
-        eng.set_source(x0, latents.to(self.device), keep)
-        eng.noise_latents(*self.scheduler.start_level())
-        return self.scheduler.source_levels()
-
-    def _finish(self, eng, h, w, had_source):
-        out = eng.read_latents(h, w)
-        if had_source:
-            eng.set_source(None)
-        return out
 
     def predict_x0(self, x_t, eps_t, t):                                    # rd.py:176-178
         a = self.alphas_cumprod[int(t)].to(x_t.device)
@@ -257,25 +193,15 @@ class RegionDiffusion:
         n_prompts = text_embeddings.shape[0]
         eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
         self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
-        hooks = getattr(self, "_tokenmap_hooks", False)
         if image is not None:
-            img2img.check_tokenmap_iterations(hooks, len(self.scheduler.timesteps))
+            img2img.check_tokenmap_iterations(getattr(self, "_tokenmap_hooks", False), len(self.scheduler.timesteps))
         eng.set_prompts(text_embeddings.to(self.device), key_counts=key_counts)
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
-        self._start(eng, latents, None if image is None else img2img.source_latents(self, image), None)
-        if hooks:
-            self._store_begin(eng)
-        for i in range(len(self.scheduler.timesteps)):
-            if getattr(self, "split_image", False):                      # one stream per rank, the text stream's rank records the maps
-                from .launcher import split_plain_step
-                split_plain_step(eng, i, guidance_scale)
-            else:
-                eng.plain_step(i, guidance_scale)
-        if hooks:
-            self._store_end(eng, len(self.scheduler.timesteps))
-        return self._finish(eng, h, w, image is not None)
+        denoise_loop.start(self, eng, latents, None if image is None else img2img.source_latents(self, image))
+        denoise_loop.plain_steps(self, eng, guidance_scale)
+        return denoise_loop.finish(eng, h, w, image is not None)
 
     def decode_latents(self, latents):                                      # rd.py:227-236
         if self.vae is None:

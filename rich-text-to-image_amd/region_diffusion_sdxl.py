@@ -4,7 +4,7 @@ import types
 
 import torch
 
-from . import img2img
+from . import denoise_loop, img2img
 from .engine import SDXL_CONFIG
 from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables, engine_prediction
 from .unet import HipUNet2DConditionModel
@@ -92,32 +92,9 @@ class RegionDiffusionXL:
         return self.text_encoders(prompt, negative_prompt, max_prompt_chunks=max_prompt_chunks)
 
     # RegionDiffusion.encode_imgs (rd.py:238-246) with the SDXL VAE: its config and scaling factor, fp32-class contractions like the
-    # pipeline's decoder (xl.py:856).  In order: a VAE object with `.encode`, the `vae_encoder` given to the constructor, an encoder
-    # built from `vae_dir` on the first call (checkpoint.load_vae_encoder(..., "SDXL", ...)), else NotImplementedError.
+    # pipeline's decoder (xl.py:856)
     def encode_imgs(self, imgs):
-        if hasattr(self.vae, "encode"):
-            imgs = 2 * imgs - 1
-            return self.vae.encode(imgs).latent_dist.sample() * self.vae_scaling_factor
-        enc = self.vae_encoder or self._encoder_from_dir(imgs.shape[-2], imgs.shape[-1])
-        if enc is None:
-            raise NotImplementedError("encode_imgs needs VAE encoder weights: a VAE with `.encode`, `vae_encoder=`, or an AutoencoderKL "
-                                      "directory whose weights hold `encoder.*` (this one is decoder-only)")
-        return enc.encode(imgs, in_scale=2.0, in_shift=-1.0).latent_dist.sample(scale=self.vae_scaling_factor)
-
-    def _encoder_from_dir(self, H, W):
-        if self.vae_dir is None:
-            return None
-        lat = (-(-H // 8), -(-W // 8))
-        if self._lazy_encoder is not None:
-            enc = self._lazy_encoder[0]
-            if enc is None or (lat[0] <= enc.cfg.latent_h and lat[1] <= enc.cfg.latent_w):
-                return enc
-            lat = (max(lat[0], enc.cfg.latent_h), max(lat[1], enc.cfg.latent_w))
-            enc.close()
-        from .checkpoint import load_vae_encoder
-        enc = load_vae_encoder(self.vae_dir, "SDXL", self.device_index, lat, precise=True)
-        self._lazy_encoder = (enc,)
-        return enc
+        return denoise_loop.encode_imgs(self, imgs, "SDXL", self.vae_scaling_factor, True)
 
     def sample(self, prompt=None, prompt_2=None, height=None, width=None, num_inference_steps=50, guidance_scale=5.0,
                negative_prompt=None, negative_prompt_2=None, num_images_per_prompt=1, eta=0.0, generator=None,
@@ -196,65 +173,19 @@ class RegionDiffusionXL:
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*prediction)
-        if image is None:
-            eng.set_latents(latents)
-        else:
-            eng.set_source(x0, noise, keep)
-            eng.noise_latents(*self.scheduler.start_level())
-            levels = self.scheduler.source_levels()
-        n = len(self.scheduler.timesteps)
+        levels = denoise_loop.start(self, eng, latents if image is None else noise, None if image is None else x0, keep)
         if run_rich_text:
             n_styles = embeds.shape[0] - 1
             assert n_styles == len(self.masks), (n_styles, len(self.masks))
             eng.set_masks([m.to(self.device) for m in self.masks])
             tfd = text_format_dict or {}
             eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
-            for i in range(n):
-                if getattr(self, "split_image", False):
-                    # intra-image split (launcher.split_region_step): the ranks of the process group share THIS image's step - each runs
-                    # the forwards of its stream range, one exchange of the noise predictions, every rank finishes the step
-                    from .launcher import assert_ranks_agree, split_region_step
-                    if i % 10 == 0:                      # every rank must hold the same masks / latents (homogeneous ranks): fail loudly otherwise
-                        if i == 0:
-                            assert_ranks_agree(torch.cat([m.reshape(-1).float().cpu() for m in self.masks]), "the region masks")
-                        assert_ranks_agree(eng.read_latents(h, w), f"the latents before step {i}")
-                    split_region_step(eng, i, guidance_scale, inject_selfattn, inject_background, True, elide=elide_dead_forwards, defer_blend=use_guidance)
-                else:
-                    eng.region_step(i, guidance_scale, inject_selfattn, inject_background, xl=True, elide=elide_dead_forwards,
-                                    defer_blend=use_guidance)
-                if use_guidance:
-                    t = float(self.scheduler.timesteps[i])
-                    if t < tfd['guidance_start_step']:                   # xl.py:849; predict_x0 on the unscaled Euler latents (quirk 4; DPM: unscaled anyway)
-                        lat_ptr, eps_ptr = eng.state_ptrs()
-
-                        def guide(lat_ptr=lat_ptr, eps_ptr=eps_ptr, t=t):
-                            (self.guidance_vae or self.vae).color_guidance(lat_ptr, eps_ptr, float(self.scheduler.alphas_cumprod[int(t)]), h, w, tfd['color_obj_atten'],
-                                                    tfd['target_RGB'], tfd['color_guidance_weight'], tfd['color_obj_atten_all'])
-                        if getattr(self, "split_image", False):          # rank 0 runs the VAE pass, the others receive the updated latents
-                            from .launcher import guidance_from_rank0
-                            guidance_from_rank0(eng, guide, h, w)
-                        else:
-                            guide()
-                    eng.background_blend()
-                if keep is not None:
-                    eng.source_blend(*levels[i])
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, self.scheduler.timesteps[i], eng.read_latents(h, w))
+            denoise_loop.rich_steps(self, eng, h, w, guidance_scale, inject_selfattn, inject_background, xl=True, elide=elide_dead_forwards,
+                                    use_guidance=use_guidance, tfd=tfd, guidance_vae=self.guidance_vae or self.vae, keep=keep, levels=levels,
+                                    callback=callback, callback_steps=callback_steps)
         else:
-            hooks = getattr(self, "_tokenmap_hooks", False)
-            if hooks:
-                self._store_begin(eng)
-            for i in range(n):
-                if getattr(self, "split_image", False):                  # one stream per rank, the text stream's rank records the maps
-                    from .launcher import split_plain_step
-                    split_plain_step(eng, i, guidance_scale)
-                else:
-                    eng.plain_step(i, guidance_scale)
-            if hooks:
-                self._store_end(eng, n)
-        latents = eng.read_latents(h, w)
-        if image is not None:
-            eng.set_source(None)
+            denoise_loop.plain_steps(self, eng, guidance_scale)
+        latents = denoise_loop.finish(eng, h, w, image is not None)
         if output_type == "latent":
             return StableDiffusionXLPipelineOutput(images=latents)
         if self.vae is None:

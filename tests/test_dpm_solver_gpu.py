@@ -1,4 +1,4 @@
-"""DPM-Solver++ on the GPU: the engine's DPM epilogue (csrc/step.hip step_epilogue_dpm_kernel + step_driver.inl dpm_coeffs) against the
+"""DPM-Solver++ on the GPU: the engine's DPM epilogue (csrc/step.hip step_epilogue_kernel<STEP_DPM> + step_driver.inl solver_coeffs / multistep_coeffs) against the
 test-side restatement (tests/dpm_solver_ref.py), with and without the UNet; both façades against the oracle loops driven by the restated
 scheduler; the split-image command line; and the default schedulers after a DPM run."""
 import json

@@ -1,5 +1,5 @@
-"""The PLMS and Euler step epilogues (csrc/step.hip step_epilogue_kernel + csrc/step_driver.inl region_plan / region_finish /
-pndm_coeffs / plain_finish) in isolation, every step, against the fp64 restatement of tests/step_ref.py.
+"""The PLMS and Euler step epilogues (csrc/step.hip step_epilogue_kernel<STEP_PLMS / STEP_EULER> + csrc/step_driver.inl region_plan /
+finish_step / pndm_coeffs / plain_finish) in isolation, every step, against the fp64 restatement of tests/step_ref.py.
 
 A tiny engine whose arena is only marked bound (the UNet never runs); seeded noise predictions go straight into the eps slots of the
 step's streams, every other slot holds NaN, then region_step_finish / plain_step_finish.  Each step is checked twice: one step of the

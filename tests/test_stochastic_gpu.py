@@ -1,5 +1,5 @@
-"""The stochastic samplers on the GPU: the device noise field (csrc/philox.h) against the uint64 / fp64 restatement; the third step
-epilogue (csrc/step.hip step_epilogue_stoch_kernel + step_driver.inl stoch_coeffs) against tests/sde_ref.py, without the UNet; seeds;
+"""The stochastic samplers on the GPU: the device noise field (csrc/philox.h) against the uint64 / fp64 restatement; the stochastic step
+epilogues (csrc/step.hip step_epilogue_kernel<STEP_EULER_A / STEP_SDE> + step_driver.inl solver_coeffs / multistep_coeffs) against tests/sde_ref.py, without the UNet; seeds;
 the field shared by the plain pass and the reference stream of the rich pass; both façades against the oracle loops driven by the
 restated schedulers and fed the engine's own fields; the image start; the split-image command line."""
 import json

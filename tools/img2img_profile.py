@@ -1,6 +1,6 @@
 """One colour-guided image-start run of RegionDiffusionXL at the SDXL shape (128 x 128 latents, random weights), meant to be run under
 `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/img2img_profile.py`: the trace then holds source_blend_kernel next
-to step_epilogue_kernel, background_blend_kernel and noise_latents_kernel (profiles/img2img_kernel_stats.txt).  R = 2 regions,
+to step_epilogue_kernel<STEP_EULER>, background_blend_kernel and noise_latents_kernel (profiles/img2img_kernel_stats.txt).  R = 2 regions,
 `--steps` x `--strength` iterations, colour guidance on every step, self-attention injection and the background blend on, every pixel of
 the left half pinned."""
 import argparse
