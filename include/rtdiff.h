@@ -123,6 +123,16 @@ int rt_set_noise_seed(rt_engine* e, unsigned long long seed);
  * and the scheduler update, its history and the noise_pred of rt_get_state_ptrs see eps.  Every rank of a split step computes the same bits. */
 enum { RT_PRED_EPSILON = 0, RT_PRED_V = 1 };
 int rt_set_prediction(rt_engine* e, int prediction_type, float guidance_rescale);
+/* FreeU (no counterpart in the reference; diffusers >= 0.21 `pipe.enable_freeu(s1, s2, b1, b2)`, same argument order): in front of EVERY
+ * resnet of up block i in {0, 1} - before the concatenation feeds GroupNorm, conv1 and the shortcut - with (b, s) = (b1, s1) / (b2, s2):
+ *   hidden[:, :, c] <- fp16(fp32(hidden[:, :, c]) b)            for c < C1 / 2
+ *   skip[y, x]      <- skip[y, x] + (s - 1) / (H W) Re( sum_{(ky, kx) in {-1, 0}^2} fftn(skip)[ky, kx] exp(2 pi i (ky y / H + kx x / W)) )
+ * per stream and channel (fourier_filter with its fixed threshold = 1: the four lowest bins times s), fp32, one rounding to fp16; every
+ * stream of a forward alike, each a function of that stream alone.  All four finite and > 0, else RT_E_INVALID and the state stays.
+ * Engine state, default (1, 1, 1, 1) = off: a forward then launches exactly what it launched before this call existed; s == 1 launches no
+ * filter and b == 1 no scaling for that block.  Survives every other call.  While enabled, a forward whose deepest grid has a side < 2
+ * is RT_E_UNSUPPORTED before anything is launched.  csrc/freeu.hip. */
+int rt_set_freeu(rt_engine* e, float s1, float s2, float b1, float b2);
 /* sampler state: latents [1,4,h,w] f32 (copied in); the reference stream starts as a clone (rd.py:93, xl.py:774) */
 int rt_set_latents(rt_engine* e, const float* latents, int h, int w);
 int rt_get_latents(rt_engine* e, float* latents_out, float* latents_ref_out /* may be NULL */);
@@ -193,7 +203,8 @@ int rt_attn_module_info(rt_engine* e, int idx, char* name, int name_cap, int* ma
  * Algorithmic FLOPs are counted per launch (2*M*N*K for GEMM/conv, 4*B*H*N*NK*d for attention; padded
  * head dims / keys are not counted). */
 enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_PROF_ATTN_CROSS = 3,
-       RT_PROF_ATTN_STORE = 4 /* head-averaged map accumulation of the plain pass (attn_store_kernel, HBM-side accumulators) */,
+       RT_PROF_ATTN_STORE = 4 /* head-averaged map accumulation of the plain pass (attn_store_kernel, HBM-side accumulators); the
+                                  * elementwise class, priced in bytes: the FreeU launches of rt_set_freeu are counted here too */,
        RT_PROF_XATTN_FUSED = 5 /* to_q + 77-key cross-attention as one launch (gemm16 EPI_XATTN): FLOPs = 2*M*HD*C + 4*B*H*N*77*d */,
        RT_PROF_XBLOCK = 6 /* the whole cross-attention block as one launch (xblock.hip): FLOPs = 4*M*HD*C + 4*B*H*N*77*d */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
@@ -333,6 +344,11 @@ int rt_op_small_linear(const float* a, int lda, const void* W_bf16, int ldw, con
                        int B, int N, int K, int silu_in, int accumulate, void* stream);
 int rt_op_timestep_embed(const float* t, int n, int dim, float* out, int ldo, void* stream);
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream);
+/* The FreeU operator of rt_set_freeu alone, in place on fp16 token-major tensors: hidden_f16 [B, H W, C1] (channels < C1 / 2 times b),
+ * skip_f16 [B, H W, C2] (the four lowest bins times s).  A NULL pointer skips that half, and so do b == 1 / s == 1 (nothing launched, bytes
+ * untouched).  C1, C2 multiples of 8, pointers 16-byte aligned, b, s finite and > 0 (RT_E_INVALID); the filter needs 2 <= H, W <= 2048
+ * (RT_E_UNSUPPORTED). */
+int rt_op_freeu(void* hidden_f16, int C1, void* skip_f16, int C2, int B, int H, int W, float b, float s, void* stream);
 /* The noise field a stochastic step with (seed, step index) adds on an h x w latent grid, from the same device function as the step
  * epilogue: out_dev [4, h, w] f32 normals; words_dev [h*w, 4] the raw Philox words of every pixel, or NULL. */
 int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev /* [4,h,w] */, unsigned int* words_dev /* [h*w,4] or NULL */,

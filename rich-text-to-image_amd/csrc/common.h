@@ -354,6 +354,10 @@ int groupnorm_nchunk(int HW);
 void launch_layernorm(const void* x, int x_f16 /* 0: fp32 rows, 1: fp16 rows (UNet trunk) */, const float* gamma, const float* beta,
                       bf16_t* out, int rows, int C, float eps, hipStream_t st);
 void launch_cast_f16_bf16(const f16_t* x, bf16_t* out, size_t n, hipStream_t st);
+// FreeU (freeu.hip), in place on fp16 token-major tensors of B streams on an H x W grid: hidden [B, HW, C1] - channels < C1 / 2 times b -
+// and skip [B, HW, C2] - the four lowest frequency bins {-1, 0}^2 of every (stream, channel) map scaled by s.  A null pointer, b == 1
+// or s == 1 launches nothing for that half; C1, C2 % 8 == 0, 16-byte aligned; the filter needs H, W >= 2 (RT_E_UNSUPPORTED below)
+void launch_freeu(f16_t* hidden, int C1, f16_t* skip, int C2, int B, int H, int W, float b, float s, hipStream_t st);
 void launch_cast_f32_bf16(const float* x, bf16_t* out, size_t n, hipStream_t st, bf16_t* out_lo = nullptr);
 // out[b][n] (+)= sum_k act(a[b][k]) * W[n][k] + bias[n];  B <= 8
 void launch_small_linear(const float* a, int lda, const bf16_t* W, int ldw, const float* bias, float* out, int ldo,

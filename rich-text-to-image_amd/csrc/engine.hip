@@ -261,6 +261,9 @@ struct rt_engine {
     double* gpartials = nullptr;     // [cdiv(HW, 256)][8]
     float* gfactors = nullptr;       // [2]
     void guided_prepass(int i, StepArgs& a);
+    // rt_set_freeu: (s1, s2, b1, b2) of the first two up blocks; all 1 = off, under which a forward launches nothing new.  Survives everything but rt_set_freeu.
+    float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f};
+    bool freeu_on() const { return fu_s[0] != 1.f || fu_s[1] != 1.f || fu_b[0] != 1.f || fu_b[1] != 1.f; }
     unsigned long long noise_seed = 0;              // stochastic samplers: key of the per-step noise field (rt_set_noise_seed); survives rt_set_schedule / rt_set_latents
 
     // optional per-launch HIP-event profiling of the MFMA kernels (bench.py roofline leg)
@@ -843,6 +846,9 @@ struct rt_engine {
         RT_REQUIRE(B >= 1 && B <= cfg.max_streams && B <= RT_MAXB, "forward: too many streams");
         RT_REQUIRE(Hh <= cfg.latent_h && Ww <= cfg.latent_w, "forward: latent larger than configured");
         RT_REQUIRE((Hh % (1 << (cfg.n_levels - 1))) == 0 && (Ww % (1 << (cfg.n_levels - 1))) == 0, "forward: latent size not divisible");
+        // FreeU (rt_set_freeu): the skip filter scales the bins {-1, 0} of both axes, which a side of 1 does not have - refused before any launch
+        if (!dry() && freeu_on() && ((Hh >> (cfg.n_levels - 1)) < 2 || (Ww >> (cfg.n_levels - 1)) < 2))
+            throw rt_error(RT_E_UNSUPPORTED, "forward: FreeU needs a deepest grid of at least 2 x 2 (latents of " + std::to_string(2 << (cfg.n_levels - 1)) + " or more per side)");
         if (!dry()) ensure_fold();       // (normally a no-op: rt_set_prompts derived the folded projections already)
         const size_t m0 = ws.mark();
         // time / addition embeddings (unet_2d_condition.py:784-877)
@@ -912,6 +918,14 @@ struct rt_engine {
             for (size_t j = 0; j < u.res.size(); ++j) {
                 Tensor sk = skips.back(); skips.pop_back();
                 const bool inject_here = (i == 1 && j == 1);        // 'up_blocks.1.resnets.1' (rd.py:350, xl.py:1101)
+                // FreeU, in place in front of EVERY resnet of up blocks 0 and 1: the hidden tensor is consumed by this resnet only and the
+                // skip was popped for it (its other reader, the down path, is behind us in stream order).  All streams, injected ones included.
+                if (i < 2 && !dry() && (fu_b[i] != 1.f || fu_s[i] != 1.f)) {
+                    const double by = (fu_b[i] != 1.f ? 2.0 * (x.C / 2) : 0.0) + (fu_s[i] != 1.f ? 3.0 * sk.C : 0.0);
+                    prof_begin(RT_PROF_ATTN_STORE, 0.0, 2.0 * B * ch * cw * by);      // priced in bytes like the token-map store: skip read twice + written, half the hidden read + written
+                    launch_freeu(x.p, x.C, sk.p, sk.C, B, ch, cw, fu_b[i], fu_s[i], stream);
+                    prof_end();
+                }
                 x = resnet(u.res[j], in, ch * cw, ch, cw, x, &sk, emb, inject_here);
                 if (u.has_attn) x = transformer(u.attn[j], in, ch * cw, x);
             }
@@ -1280,6 +1294,12 @@ int rt_set_prediction(rt_engine* e, int prediction_type, float guidance_rescale)
         RT_REQUIRE(prediction_type == RT_PRED_EPSILON || prediction_type == RT_PRED_V, "rt_set_prediction: prediction_type must be 0 (epsilon) or 1 (v)");
         RT_REQUIRE(guidance_rescale >= 0.f && guidance_rescale <= 1.f, "rt_set_prediction: guidance_rescale must be in [0, 1]");
         e->prediction_type = prediction_type; e->guidance_rescale = guidance_rescale;
+    })
+}
+int rt_set_freeu(rt_engine* e, float s1, float s2, float b1, float b2) {
+    RT_TRY(e, {
+        for (float v : {s1, s2, b1, b2}) RT_REQUIRE(std::isfinite(v) && v > 0.f, "rt_set_freeu: s1, s2, b1, b2 must be finite and > 0");
+        e->fu_s[0] = s1; e->fu_s[1] = s2; e->fu_b[0] = b1; e->fu_b[1] = b2;
     })
 }
 int rt_set_source(rt_engine* e, const float* x0, const float* noise, const float* keep, int h, int w) {
@@ -1853,6 +1873,12 @@ int rt_op_guided_prediction(const float* eps, const float* masks, const float* l
         if (!plain) for (int r = 0; r < R - 1; ++r) { RT_REQUIRE(s_region_host[r] >= 0, "rt_op_guided_prediction: region stream"); q.s.s_region[r] = s_region_host[r]; }
         q.gpred = gpred_dev; q.partials = partials_dev; q.factors = factors_dev; q.phi = phi; q.vpred = prediction_type == RT_PRED_V; q.cv = cv; q.cx = cx;
         launch_guided_prediction(q, (hipStream_t)stream);
+    })
+}
+int rt_op_freeu(void* hidden_f16, int C1, void* skip_f16, int C2, int B, int H, int W, float b, float s, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(std::isfinite(b) && b > 0.f && std::isfinite(s) && s > 0.f, "rt_op_freeu: b and s must be finite and > 0");
+        launch_freeu((f16_t*)hidden_f16, C1, (f16_t*)skip_f16, C2, B, H, W, b, s, (hipStream_t)stream);
     })
 }
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream) {

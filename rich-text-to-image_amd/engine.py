@@ -84,6 +84,7 @@ _SYMBOLS = [
     "rt_set_prediction", "rt_op_guided_prediction",
     "rt_op_attention_store_handover",
     "rt_op_gemm_route", "rt_op_groupnorm_form",
+    "rt_set_freeu", "rt_op_freeu",
 ]
 
 
@@ -312,6 +313,15 @@ class Engine:
             prediction_type = PREDICTION_TYPES[prediction_type]
         self._chk(self.lib.rt_set_prediction(self.h, int(prediction_type), C.c_float(float(guidance_rescale))))
 
+    def set_freeu(self, s1, s2, b1, b2):
+        """FreeU in the first two up blocks (include/rtdiff.h: rt_set_freeu; diffusers' argument order): the four lowest frequency bins of
+        the skip features times s1 / s2, half of the backbone channels times b1 / b2.  All finite and > 0; (1, 1, 1, 1) = off, under
+        which a forward launches what it always launched.  Engine state: it holds until set again; a bad value raises and changes nothing."""
+        self._chk(self.lib.rt_set_freeu(self.h, C.c_float(float(s1)), C.c_float(float(s2)), C.c_float(float(b1)), C.c_float(float(b2))))
+
+    def disable_freeu(self):
+        self.set_freeu(1.0, 1.0, 1.0, 1.0)
+
     def set_latents(self, latents):
         l = latents.contiguous().float()
         assert l.shape[0] == 1 and l.shape[1] == 4
@@ -376,7 +386,7 @@ class Engine:
     # ---- profiling (HIP events around every MFMA kernel launch on the engine stream)
     PROF_CLASSES = {0: "gemm_kernel<A_DENSE>", 1: "gemm_kernel<A_CONV3*>", 2: "attn_kernel<self>", 3: "attn_kernel<cross>",
                     5: "gemm16_kernel<EPI_XATTN> (to_q + cross-attention)", 6: "xblock_kernel (to_q + cross-attention + to_out)"}
-    PROF_STORE = 4          # attn_store_kernel (plain pass, token-map capture): priced in algorithmic HBM bytes
+    PROF_STORE = 4          # attn_store_kernel (plain pass, token-map capture) and, with set_freeu on, the FreeU launches: priced in algorithmic HBM bytes
 
     def profile_read_store(self):
         n, ms, fl, by = C.c_int(), C.c_double(), C.c_double(), C.c_double()
@@ -471,6 +481,27 @@ def step_noise(seed, step, h, w, words=False, device=0):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return (out, wd.to(torch.int64) & 0xFFFFFFFF) if words else out
+
+
+def freeu(hidden, skip, H, W, b=1.0, s=1.0):
+    """The FreeU operator alone (rt_op_freeu), IN PLACE on the caller's fp16 token-major tensors: hidden [B, H W, C1] - channels
+    < C1 // 2 times b - and skip [B, H W, C2] - the four lowest frequency bins of every (stream, channel) map times s.  Either may be
+    None; b == 1 / s == 1 launch nothing for their half.  Returns (hidden, skip)."""
+    import torch
+    lib = load_library()
+    ref = hidden if hidden is not None else skip
+    for t in (hidden, skip):
+        assert t is None or (t.dtype == torch.float16 and t.dim() == 3 and t.is_contiguous() and t.shape[1] == H * W and t.device == ref.device), \
+            "freeu: contiguous fp16 [B, H W, C] tensors on one device"
+    assert hidden is None or skip is None or hidden.shape[0] == skip.shape[0], "freeu: hidden and skip differ in streams"
+    with torch.cuda.device(ref.device):
+        rc = lib.rt_op_freeu(_ptr(hidden), int(hidden.shape[2]) if hidden is not None else 0, _ptr(skip),
+                             int(skip.shape[2]) if skip is not None else 0, int(ref.shape[0]), int(H), int(W), C.c_float(float(b)),
+                             C.c_float(float(s)), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return hidden, skip
 
 
 def guided_prediction(eps, lat, g, s_uncond=0, s_base=1, masks=None, lat_ref=None, s_uref=-1, s_tref=-1, s_region=(), plain=True,

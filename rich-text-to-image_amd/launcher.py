@@ -206,15 +206,36 @@ def broadcast_weights(engine, src=0):
     return time.perf_counter() - t0
 
 
-def broadcast_pipeline(unet_engine, vae=None, text_encoders=(), src=0):
+PIPELINE_SETTINGS = ("freeu",)      # pipeline attributes that are settings, not weights: they travel with the pipeline
+
+
+def pipeline_settings(pipeline):
+    """The settings of `pipeline` that every rank must share, as a small picklable dict."""
+    return {k: getattr(pipeline, k, None) for k in PIPELINE_SETTINGS}
+
+
+def apply_pipeline_settings(pipeline, settings):
+    """Puts what pipeline_settings() of the source rank returned onto this rank's pipeline, through the same checks a local call makes."""
+    fu = settings.get("freeu")
+    if fu is None:
+        pipeline.disable_freeu()
+    else:
+        pipeline.enable_freeu(*fu)
+
+
+def broadcast_pipeline(unet_engine, vae=None, text_encoders=(), src=0, pipeline=None):
     """Everything a rank needs to sample without touching the checkpoint files: the UNet arena, the VAE decoder arena and the
     text-encoder weights (HipCLIPTextEncoder.parameter_tensors()), three collectives in total.  Ranks != src construct the same
     objects from the configs alone (any state dict of the right shapes, e.g. engine.random_state_dict(config), or the
-    constructors' lazily zero-filled arenas): only the tensor SHAPES must agree, which the configs determine."""
+    constructors' lazily zero-filled arenas): only the tensor SHAPES must agree, which the configs determine.
+    `pipeline` (optional): its settings (PIPELINE_SETTINGS: the FreeU values) go from `src` to every rank as one small object
+    broadcast, not counted in LAST_BROADCAST_CALLS - every rank of --gpus N and of --split_image then samples with the same values."""
     global LAST_BROADCAST_CALLS
     t = broadcast_weights(unet_engine, src)
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return t
+    if pipeline is not None:
+        apply_pipeline_settings(pipeline, broadcast_objects(pipeline_settings(pipeline) if dist.get_rank() == src else None, src))
     import time
     t0 = time.perf_counter()
     n = 0

@@ -4,11 +4,12 @@ import torch
 
 from . import denoise_loop, img2img
 from .engine import SD15_CONFIG
+from .freeu import FreeUMixin
 from .schedulers import DPMSolverTables, PNDMTables, engine_prediction
 from .unet import HipUNet2DConditionModel
 
 
-class RegionDiffusion:
+class RegionDiffusion(FreeUMixin):
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
                  latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None, max_prompt_chunks=1, guidance_rescale=0.0,
                  prediction_type=None):
@@ -149,6 +150,7 @@ class RegionDiffusion:
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
+        self.apply_freeu(eng)
         levels = denoise_loop.start(self, eng, latents, None if image is None else x0, keep)
         denoise_loop.rich_steps(self, eng, h, w, guidance_scale, inject_selfattn, inject_background, xl=False, elide=elide_dead_forwards,
                                 use_guidance=use_guidance, tfd=tfd, guidance_vae=self.vae, keep=keep, levels=levels)
@@ -199,6 +201,7 @@ class RegionDiffusion:
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))
+        self.apply_freeu(eng)
         denoise_loop.start(self, eng, latents, None if image is None else img2img.source_latents(self, image))
         denoise_loop.plain_steps(self, eng, guidance_scale)
         return denoise_loop.finish(eng, h, w, image is not None)

@@ -6,6 +6,7 @@ import torch
 
 from . import denoise_loop, img2img
 from .engine import SDXL_CONFIG
+from .freeu import FreeUMixin
 from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables, engine_prediction
 from .unet import HipUNet2DConditionModel
 
@@ -16,7 +17,7 @@ class StableDiffusionXLPipelineOutput(dict):
         self.images = images
 
 
-class RegionDiffusionXL:
+class RegionDiffusionXL(FreeUMixin):
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
                  vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None,
                  max_prompt_chunks=1, guidance_rescale=0.0, prediction_type=None):
@@ -173,6 +174,7 @@ class RegionDiffusionXL:
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*prediction)
+        self.apply_freeu(eng)
         levels = denoise_loop.start(self, eng, latents if image is None else noise, None if image is None else x0, keep)
         if run_rich_text:
             n_styles = embeds.shape[0] - 1

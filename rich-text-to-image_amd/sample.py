@@ -37,7 +37,26 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     The request's seed (`noise_index`) is also the noise seed of a stochastic scheduler, in both passes: they see the same per-step noise.
     `param['guidance_rescale']` (optional): the CFG rescale of both passes, handed to the sampling calls as their `guidance_rescale`
     keyword; the SDXL rich pass, whose keyword the reference refuses, takes it as the pipeline attribute, set around that one call and
-    restored after it."""
+    restored after it.
+    `param['freeu']` (optional, four numbers s1 s2 b1 b2): FreeU in both passes of THIS request - the pipeline attribute
+    (enable_freeu) for the duration of the call, restored after it; absent / None: the pipeline as it is."""
+    fu = param.get('freeu')
+    args = (model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background, latents,
+            init_image, strength, keep_source)
+    if fu is None:
+        return _generate(model, param, *args)
+    from .freeu import check_freeu
+    fu, keep = check_freeu(fu, "param['freeu']"), getattr(model, 'freeu', None)
+    model.enable_freeu(*fu)
+    try:
+        return _generate(model, param, *args)
+    finally:
+        model.freeu = keep
+
+
+def _generate(model, param, model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background,
+              latents, init_image, strength, keep_source):
+    """The body of generate(): the request as given, on the pipeline as it stands."""
     # the request's own choice, else the one the model was built with; passed to every call below, the model is not changed
     chunks = check_max_prompt_chunks(param.get('max_prompt_chunks') or getattr(model, 'max_prompt_chunks', 1))
     if run_dir:
@@ -166,12 +185,31 @@ def _request_scheduler(a, name):
     return name
 
 
+def check_freeu_arg(values, who):
+    """--freeu / a --requests line's "freeu": four finite numbers > 0, else the run ends (SystemExit); None stays None."""
+    if values is None:
+        return None
+    from .freeu import check_freeu
+    try:
+        return list(check_freeu(values, who))
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
+
+
+def check_requests_freeu(path):
+    """The "freeu" keys of a --requests file, checked on their own: main() calls this before any rank starts."""
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            if line.strip():
+                check_freeu_arg(json.loads(line).get("freeu"), f"--requests line {n}: freeu")
+
+
 def build_requests(a):
     """The (rich-text JSON, seed) list of one invocation.  One JSON + one --seed = the reference's single image.  Several JSONs and / or
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
     one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
-    (missing keys: the flags; a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
+    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -183,12 +221,14 @@ def build_requests(a):
                 js = r["rich_text_json"]
                 reqs.append(dict(text_input=_load_json_arg(js) if isinstance(js, str) else js, seed=int(r.get("seed", a.seed)),
                                  negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
-                                 max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1))))))
+                                 max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1)))),
+                                 freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu")))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
-        reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1)) for j, sd in pairs]
+        reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1),
+                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu")) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -226,7 +266,7 @@ def build_model(a, rank=0, local_rank=0, world=1):
         model = RegionDiffusionXL(None, local_rank, **comp)
         encoders = list(comp["text_encoders"].encoders)
     eng = model.unet.engine(hw[0], hw[1])                            # the engine (and its arena) must exist on every rank before the broadcast
-    seconds = launcher.broadcast_pipeline(eng, model.vae, encoders, src=0)
+    seconds = launcher.broadcast_pipeline(eng, model.vae, encoders, src=0, pipeline=model)
     return apply_scheduler(model, a), seconds
 
 
@@ -331,6 +371,10 @@ def build_parser():
                    help='CFG rescale in [0, 1] (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", 3.4): the guided '
                         'prediction is scaled towards the standard deviation of its conditional half, in both passes; made for '
                         'v-prediction checkpoints, usually 0.7.  Default: off')
+    p.add_argument('--freeu', type=float, nargs=4, default=None, metavar=('S1', 'S2', 'B1', 'B2'),
+                   help='FreeU (diffusers enable_freeu, same order): in the first two up blocks of the UNet the four lowest frequency bins of '
+                        'the skip features are scaled by S1 / S2 and half of the backbone channels by B1 / B2, in both passes; all > 0. '
+                        'Usual values: SD-v1.5 0.9 0.2 1.5 1.6, SDXL 0.6 0.4 1.1 1.2.  Default: off.  Holds on every rank of --gpus N')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
                    help='what the UNet predicts; default: the checkpoint\'s scheduler/scheduler_config.json, else epsilon')
     p.add_argument('--timestep_spacing', type=str, default=None, choices=['leading', 'trailing'],
@@ -372,6 +416,9 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     a = p.parse_args(argv)
     make_scheduler(a)                 # an unusable --scheduler / --solver_order combination fails here, before any rank starts
+    a.freeu = check_freeu_arg(a.freeu, "--freeu")      # ... and so do bad FreeU values, the flag's and a --requests line's
+    if a.requests:
+        check_requests_freeu(a.requests)
     if a.init_image is None and a.keep_source != 'none':
         raise SystemExit("sample: --keep_source needs --init_image")
     if a.init_image is not None and a.keep_source != 'none' and a.split_image:
@@ -408,7 +455,7 @@ def main(argv=None):
         apply_request_scheduler(model, flag_scheduler, r, a)
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
-                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale}
+                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu')}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)
@@ -465,7 +512,11 @@ def _dry_launch(a, rank, world, reqs, mine):
     from . import launcher
     unet, vae = _StandInArena(1 << 16, 0xA5 if rank == 0 else None), _StandInArena(1 << 12, 0x3C if rank == 0 else None)
     encs = [_StandInEncoder(rank == 0), _StandInEncoder(rank == 0)]
-    seconds = launcher.broadcast_pipeline(unet, vae, encs, src=0)
+    from .freeu import FreeUMixin
+    pipe = FreeUMixin()                              # rank 0 alone holds the flag's values: the others receive them with the pipeline
+    if rank == 0 and a.freeu is not None:
+        pipe.enable_freeu(*a.freeu)
+    seconds = launcher.broadcast_pipeline(unet, vae, encs, src=0, pipeline=pipe)
     ref = _StandInEncoder(True)
     sched = apply_scheduler(types.SimpleNamespace(scheduler=None), a).scheduler        # what build_model puts on this rank's pipeline
     ok = bool((unet.t == 0xA5).all() and (vae.t == 0x3C).all() and unet.bound and vae.bound and
@@ -474,7 +525,7 @@ def _dry_launch(a, rank, world, reqs, mine):
     # ranks' lines run into each other once in ~25 runs
     sys.stdout.write(json.dumps({"rank": rank, "world": world, "requests_total": len(reqs), "requests_mine": [r["index"] for r in mine],
                                  "seeds_mine": [r["seed"] for r in mine], "pipeline_received": ok, "broadcast_collectives": launcher.LAST_BROADCAST_CALLS,
-                                 "broadcast_s": seconds,
+                                 "broadcast_s": seconds, "freeu": None if pipe.freeu is None else list(pipe.freeu),
                                  "scheduler": None if sched is None else {"class": type(sched).__name__, "kind": sched.kind,
                                                                           "solver_order": getattr(sched, "solver_order", None)}}) + "\n")
     sys.stdout.flush()

@@ -18,6 +18,20 @@ class HipUNet2DConditionModel:
         self.max_streams, self.max_prompts, self.max_keys = max_streams, max_prompts, max_keys
         self._state_dict = state_dict
         self._engines = {}
+        self.freeu = None                          # (s1, s2, b1, b2) or None = off: on every engine of this model, present and future
+
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' `unet.enable_freeu(s1, s2, b1, b2)` (argument order included): FreeU in the first two up blocks of every forward
+        of this model (Engine.set_freeu), until disable_freeu()."""
+        from .freeu import check_freeu
+        self.freeu = check_freeu((s1, s2, b1, b2), "HipUNet2DConditionModel.enable_freeu")
+        for e in self._engines.values():
+            e.set_freeu(*self.freeu)
+
+    def disable_freeu(self):
+        self.freeu = None
+        for e in self._engines.values():
+            e.disable_freeu()
 
     def load_state_dict(self, sd):
         self._state_dict = sd
@@ -73,6 +87,8 @@ class HipUNet2DConditionModel:
                         e.init_random_weights(seed=int(self._state_dict[6:] or 0))      # "random<seed>": benchmarks without checkpoints
                     else:
                         e.load_state_dict(self._state_dict)
+                    if self.freeu is not None:
+                        e.set_freeu(*self.freeu)
                 except BaseException:
                     e.close()
                     raise
