@@ -276,7 +276,7 @@ enum { RT_ROUTE_TILE = 0        /* one launch of a csrc/gemm.hip tile configurat
        RT_ROUTE_PATCH = 3       /* the 16x16-patch convolution kernel */,
        RT_ROUTE_PATCH_SPLIT = 4 /* ... split over its input-channel chunks + reduction launch */,
        RT_ROUTE_KSPLIT = 5      /* K slices of the 128x128 (implicit) GEMM + reduction launch */,
-       RT_ROUTE_TRIPLE = 6      /* the precise VAE's hi / lo contraction as three launches (rt_vae_* only) */ };
+       RT_ROUTE_TRIPLE = 6      /* the precise VAE's hi / lo contraction as three launches (rt_vae_* and rt_op_gemm_hilo) */ };
 int rt_op_gemm_route(int mode, int epi, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win, int Cin,
                      int Hout, int Wout, int* kind, int* variant_or_cfg, int* slices);
 /* One tile variant of the 16x16x32-MFMA GEMM family (csrc/gemm16.hip; tests / micro-benchmarks - rt_op_gemm picks by shape):
@@ -317,6 +317,57 @@ int rt_op_groupnorm(const void* x1, const void* x2, int in_type, int C1, int C2,
  * (statistics and apply in one kernel), 2: two launches (statistics, then apply); rt_op_gemm_debug bit 23 forces 2.  RT_E_INVALID (< 0) for
  * arguments rt_op_groupnorm would refuse. */
 int rt_op_groupnorm_form(int in_type, int C1, int C2, int G, int B, int HW);
+
+/* ---- The VAE's kernels one call at a time (tests/test_vae_ops_gpu.py).  rt_vae_* reaches them only through a whole decode / guidance /
+ * encode; these entries issue the same launches from the same argument builders (csrc/vae.h), so they take the routes, chunkings and
+ * block counts the VAE takes and no others.  Scratch is allocated and freed per call where an entry needs some (not for hot paths).
+ *
+ * rt_op_gemm_hilo: the VAE's contraction, out_f32 [M, ldo] = A W^T + A_lo W^T + A W_lo^T (+ bias) (+ res, fp32 [M, ldres]) accumulated in
+ * fp32 from bf16 planes (a value v is the pair hi = bf16(v), lo = bf16(v - hi)).  A_lo == W_lo == NULL: the single-pass call A W^T as the
+ * default mode issues it (fp32 output).  mode 0 dense (A [M, lda], W [N, ldw]); 1 / 3 / 4: the 3x3 convolution of ONE NHWC image
+ * [Hin, Win, Cin] (Cin % 8 == 0, K = 9 Cin, W [N, ldw] tap-major) - stride 1 / behind a nearest-2x up-sample / stride 2 with bottom-right
+ * zero padding; M = rows_per_batch = Hout Wout of that mode (RT_E_INVALID otherwise).  out == res is allowed (the backward pass
+ * accumulates in place).  pair_lo != NULL (convolutions): the result leaves as its bf16 pair - out_f32 is then the bf16 hi plane [M, ldo],
+ * pair_lo the lo plane with the same ldo - where the route can (pair_ok below), else RT_E_UNSUPPORTED and nothing is launched.
+ * rt_op_gemm_hilo_route: host-only, the route of that call for hilo = (A_lo != NULL), pair = (pair_lo != NULL) under the current switches.
+ * *kind: RT_ROUTE_TRIPLE when the three passes run as three launches, else the route of the ONE launch that runs them; *pass_kind: the
+ * route of each of the three launches (TRIPLE), else = *kind; *variant_or_cfg / *slices belong to *pass_kind; *pair_ok: 1 when this
+ * problem's route writes pairs (gemm_pair_output_ok).  Any output may be NULL. */
+int rt_op_gemm_hilo(const void* A, const void* A_lo, const void* W, const void* W_lo, const float* bias, float* out_f32, void* pair_lo,
+                    const float* res, int mode, int M, int N, int K, int lda, int ldw, int ldo, int ldres, int rows_per_batch, int Hin,
+                    int Win, int Cin, int Hout, int Wout, void* stream);
+int rt_op_gemm_hilo_route(int hilo, int pair, int mode, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win,
+                          int Cin, int Hout, int Wout, int* kind, int* variant_or_cfg, int* slices, int* pass_kind, int* pair_ok);
+/* hi = bf16(x), lo = bf16(x - hi); n % 4 == 0 */
+int rt_op_split_bf16(const float* x, void* hi_bf16, void* lo_bf16, long long n, void* stream);
+/* GroupNorm (+ SiLU) of x [B, HW, C] (x_bf16: 0 fp32, 1 bf16) as the VAE launches it: chunks by the VAE's rule
+ * (rt_op_vae_groupnorm_nchunk(HW) of them), optional low planes out_lo / raw_lo, optional un-normalised copy raw.  stats: caller's
+ * [B, nchunk, G, 2] floats; on return stats[b][0][g] = (mean, rstd), which is what the backward reads.
+ * Backward wrt x: dx = rstd (dxh - mean_g(dxh) - xh mean_g(dxh xh)) (+ add), dxh = (dA + dA_lo) silu'(y) gamma; stats as the forward left
+ * them; any of out (fp32), out_bf16 (+ out_bf16_lo) may be NULL. */
+int rt_op_vae_groupnorm_nchunk(int HW);
+int rt_op_vae_groupnorm(const void* x, int x_bf16, int C, int G, int B, int HW, const float* gamma, const float* beta, float eps, int silu,
+                        void* out_bf16, void* out_lo, void* raw_bf16, void* raw_lo, float* stats, void* stream);
+int rt_op_vae_groupnorm_bwd(const void* x, int x_bf16, const void* dA_bf16, const void* dA_lo, const float* stats, const float* gamma,
+                            const float* beta, float eps, int silu, int C, int G, int B, int HW, const float* add, float* out,
+                            void* out_bf16, void* out_bf16_lo, void* stream);
+/* p (+ p_lo) = softmax(scale s) per row of s [rows, cols] fp32; ds (+ ds_lo) = scale P o (dp - rowsum(dp o P)), P = p + p_lo */
+int rt_op_softmax_rows(const float* s, void* p_bf16, void* p_lo, int rows, int cols, float scale, void* stream);
+int rt_op_softmax_bwd(const void* p_bf16, const void* p_lo, const float* dp, void* ds_bf16, void* ds_lo, int rows, int cols, float scale,
+                      void* stream);
+int rt_op_transpose_bf16(const void* in, void* out, int R, int C, void* stream);                  /* [R, C] -> [C, R] */
+int rt_op_sumpool2x2(const float* in, float* out, int B, int H, int W, int C, void* stream);      /* [B, 2H, 2W, C] -> [B, H, W, C]; C % 4 == 0 */
+/* post_quant_conv: out [HW, 8] bf16 (+ out_lo) = W (c_lat lat + c_eps eps) + b per pixel, channels 4..7 zero; lat / eps [4, HW] (eps may be
+ * NULL).  Its adjoint + the guidance update: g[c] = gscale sum_o W[o][c] dz[pix][o]; grad_out[c][pix] = g (optional);
+ * lat[c][pix] -= g weight mask_all[c][pix] */
+int rt_op_pq_conv_fwd(const float* lat, const float* eps, float c_lat, float c_eps, const float* W, const float* b, void* out_bf16,
+                      void* out_lo, int HW, void* stream);
+int rt_op_pq_conv_bwd_update(const float* dz, int ldz, const float* W, float gscale, float weight, const float* mask_all, float* lat,
+                             float* grad_out, int HW, void* stream);
+/* Colour loss of the guidance step and its gradient wrt the decoder output img [HWi, ldi] fp32 (3 channels used): dimg [HWi, 8] bf16
+ * (+ dimg_lo), channels 3..7 zero; masks [n, HWi], target_dev [n, 3] on the device, 1 <= n <= 16; *loss_dev (device, optional) */
+int rt_op_color_loss_grad(const float* img, int ldi, const float* masks, const float* target_dev, int n, int HWi, void* dimg_bf16,
+                          void* dimg_lo, float* loss_dev, void* stream);
 int rt_op_layernorm(const float* x, const float* gamma, const float* beta, void* out_bf16, int rows, int C, float eps,
                     void* stream);
 int rt_op_layernorm_f16(const void* x_f16, const float* gamma, const float* beta, void* out_bf16, int rows, int C, float eps, void* stream);

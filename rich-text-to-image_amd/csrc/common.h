@@ -431,7 +431,6 @@ void launch_softmax_rows(const float* s, bf16_t* p, int rows, int cols, float sc
 void launch_softmax_bwd(const bf16_t* p, const float* dp, bf16_t* ds, int rows, int cols, float scale, hipStream_t st, const bf16_t* p_lo = nullptr,
                         bf16_t* ds_lo = nullptr);
 void launch_sumpool2x2(const float* in, float* out, int B, int H, int W, int C, hipStream_t st);   // [B,2H,2W,C] -> [B,H,W,C]
-void launch_add_f32(const float* a, const float* b, float* out, size_t n, hipStream_t st);
 // per pixel: out[pix][0..7] = bf16(W[4x4] * (in[c][pix] * scale) + b), channels 4..7 zero  (post_quant_conv 1x1)
 void launch_pq_conv_fwd(const float* lat_nchw, const float* eps_nchw, float c_lat, float c_eps, const float* W, const float* b,
                         bf16_t* out, int HW, hipStream_t st, bf16_t* out_lo = nullptr);

@@ -166,6 +166,7 @@ void launch_source_blend(float* lat, const float* x0, const float* noise, const 
 
 #include "step.h"
 #include "guided.h"
+#include "vae.h"
 
 // Cross-attention of a launch whose streams have DIFFERENT key counts (prompts of one to three 77-token windows), where the shape has
 // cross77_kernel: the kernel of a stream is a function of its OWN key count - maximal runs of 77-key streams go to cross77_kernel, the
@@ -1556,6 +1557,20 @@ int rt_op_gemm(const void* A, const void* W, const float* bias, void* out, const
         launch_gemm(g, (hipStream_t)stream);
     })
 }
+// GemmRoute -> RT_ROUTE_* (+ the tile variant / configuration of the kinds that have one)
+static int op_route_kind(const GemmRoute& r, int* v) {
+    *v = -1;
+    switch (r.kind) {
+        case GemmRoute::TILE: *v = r.cfg; return RT_ROUTE_TILE;
+        case GemmRoute::G16: *v = r.variant; return RT_ROUTE_G16;
+        case GemmRoute::G16_UP2: *v = r.variant; return RT_ROUTE_G16_UP2;
+        case GemmRoute::PATCH: return RT_ROUTE_PATCH;
+        case GemmRoute::PATCH_SPLIT: return RT_ROUTE_PATCH_SPLIT;
+        case GemmRoute::KSPLIT: return RT_ROUTE_KSPLIT;
+        case GemmRoute::TRIPLE: return RT_ROUTE_TRIPLE;
+    }
+    return RT_ROUTE_TILE;
+}
 // The route of that call as a host-only query (no device needed): gemm_route of the same GemmArgs, under the same switches.
 int rt_op_gemm_route(int mode, int epi, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win, int Cin, int Hout,
                      int Wout, int* kind, int* variant_or_cfg, int* slices) {
@@ -1565,21 +1580,65 @@ int rt_op_gemm_route(int mode, int epi, int M, int N, int K, int lda, int ldw, i
         const GemmArgs g = op_gemm_args(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mode, epi, M, N, K, lda, ldw, ldo, 0, 0,
                                         rows_per_batch, Hin, Win, Cin, Hout, Wout);
         const GemmRoute r = gemm_route(g);
-        int k = RT_ROUTE_TILE, v = -1;
-        switch (r.kind) {
-            case GemmRoute::TILE: k = RT_ROUTE_TILE; v = r.cfg; break;
-            case GemmRoute::G16: k = RT_ROUTE_G16; v = r.variant; break;
-            case GemmRoute::G16_UP2: k = RT_ROUTE_G16_UP2; v = r.variant; break;
-            case GemmRoute::PATCH: k = RT_ROUTE_PATCH; break;
-            case GemmRoute::PATCH_SPLIT: k = RT_ROUTE_PATCH_SPLIT; break;
-            case GemmRoute::KSPLIT: k = RT_ROUTE_KSPLIT; break;
-            case GemmRoute::TRIPLE: k = RT_ROUTE_TRIPLE; break;
-        }
+        int v = -1;
+        const int k = op_route_kind(r, &v);
         if (kind) *kind = k;
         if (variant_or_cfg) *variant_or_cfg = v;
         if (slices) *slices = r.slices;
         return RT_OK;
     } catch (...) { return RT_E_INVALID; }
+}
+// ---- the VAE's contraction call (vae.hip gemm1 / conv1) behind the operator ABI: the GemmArgs come from the VAE's own builders (vae.h), so
+// the entry takes exactly the routes rt_vae takes (prefer_patch_conv by conv1's rule, one image, fp32 output).  The launch and the
+// host-only query build them through this one function.
+static GemmArgs op_hilo_args(const void* A, const void* A_lo, const void* W, const void* W_lo, const float* bias, void* out, void* pair_lo, const float* res,
+                             const bf16_t* zero, int mode, int M, int N, int K, int lda, int ldw, int ldo, int ldres, int rows_per_batch, int Hin, int Win,
+                             int Cin, int Hout, int Wout) {
+    RT_REQUIRE(mode == A_DENSE || mode == A_CONV3 || mode == A_CONV3_UP2 || mode == A_CONV3_S2P0, "rt_op_gemm_hilo: mode 0 dense / 1 conv / 3 up-2 conv / 4 stride-2-pad-0 conv");
+    RT_REQUIRE(M > 0 && N > 0 && K > 0, "rt_op_gemm_hilo: empty problem");
+    RT_REQUIRE((A_lo == nullptr) == (W_lo == nullptr), "rt_op_gemm_hilo: both low planes or neither");
+    if (mode == A_DENSE) {
+        RT_REQUIRE(!pair_lo, "rt_op_gemm_hilo: the pair output exists for convolutions only");
+        return vae_gemm_args((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, M, N, K, out, ldo, EPI_F32, res, ldres, (const bf16_t*)A_lo, (const bf16_t*)W_lo, zero);
+    }
+    RT_REQUIRE(Hin > 0 && Win > 0 && Cin > 0, "rt_op_gemm_hilo: empty image");
+    const GemmArgs g = vae_conv_args((const bf16_t*)A, mode, (const bf16_t*)W, ldw, bias, N, K, Hin, Win, Cin, out, ldo, EPI_F32, res, ldres, (const bf16_t*)A_lo,
+                                     (const bf16_t*)W_lo, (bf16_t*)pair_lo, zero);
+    RT_REQUIRE(g.M == M && g.rows_per_batch == rows_per_batch && g.Hout == Hout && g.Wout == Wout, "rt_op_gemm_hilo: M, rows_per_batch, Hout, Wout must be those of ONE image in this mode");
+    return g;
+}
+int rt_op_gemm_hilo(const void* A, const void* A_lo, const void* W, const void* W_lo, const float* bias, float* out_f32, void* pair_lo, const float* res,
+                    int mode, int M, int N, int K, int lda, int ldw, int ldo, int ldres, int rows_per_batch, int Hin, int Win, int Cin, int Hout, int Wout,
+                    void* stream) {
+    OP_TRY({
+        const GemmArgs g = op_hilo_args(A, A_lo, W, W_lo, bias, out_f32, pair_lo, res, op_zero_page(), mode, M, N, K, lda, ldw, ldo, ldres, rows_per_batch, Hin,
+                                        Win, Cin, Hout, Wout);
+        if (pair_lo && !gemm_pair_output_ok(g)) throw rt_error(RT_E_UNSUPPORTED, "rt_op_gemm_hilo: this problem's route cannot write the pair (rt_op_gemm_hilo_route)");
+        launch_gemm(g, (hipStream_t)stream);
+    })
+}
+int rt_op_gemm_hilo_route(int hilo, int pair, int mode, int M, int N, int K, int lda, int ldw, int ldo, int rows_per_batch, int Hin, int Win, int Cin, int Hout,
+                          int Wout, int* kind, int* variant_or_cfg, int* slices, int* pass_kind, int* pair_ok) {
+    try {
+        const void* some = (const void*)(uintptr_t)256;              // (any non-null value: no routing rule reads a pointer's value)
+        const GemmArgs g = op_hilo_args(nullptr, hilo ? some : nullptr, nullptr, hilo ? some : nullptr, nullptr, nullptr, pair ? (void*)some : nullptr, nullptr, nullptr,
+                                        mode, M, N, K, lda, ldw, ldo, 0, rows_per_batch, Hin, Win, Cin, Hout, Wout);
+        const GemmRoute r = gemm_route(g);
+        // TRIPLE = three launches of the single-pass problem (launch_routed): the route each of them takes
+        GemmRoute rp = r;
+        if (r.kind == GemmRoute::TRIPLE) { GemmArgs b = g; b.A_lo = nullptr; b.W_lo = nullptr; rp = gemm_route(b); }
+        int v = -1;
+        const int k = op_route_kind(r, &v), pk = op_route_kind(rp, &v);
+        if (kind) *kind = k;
+        if (variant_or_cfg) *variant_or_cfg = v;
+        if (slices) *slices = rp.slices;
+        if (pass_kind) *pass_kind = pk;
+        if (pair_ok) *pair_ok = gemm_pair_output_ok(g) ? 1 : 0;
+        return RT_OK;
+    } catch (...) { return RT_E_INVALID; }
+}
+int rt_op_split_bf16(const float* x, void* hi_bf16, void* lo_bf16, long long n, void* stream) {
+    OP_TRY({ RT_REQUIRE(x && hi_bf16 && lo_bf16 && n > 0, "rt_op_split_bf16: null argument or empty"); launch_cast_f32_bf16(x, (bf16_t*)hi_bf16, (size_t)n, (hipStream_t)stream, (bf16_t*)lo_bf16); })
 }
 int rt_op_pack_upconv(const void* w, int dtype, int Cout, int Cin, void* out_bf16, void* stream) {
     OP_TRY({ launch_pack_up2(w, dtype, (bf16_t*)out_bf16, Cout, Cin, (hipStream_t)stream); })
@@ -1828,6 +1887,74 @@ int rt_op_groupnorm_form(int in_type, int C1, int C2, int G, int B, int HW) {
     if (in_type < 0 || in_type > 2 || C1 <= 0 || C2 < 0 || G < 1 || (C1 + C2) % G || B < 1 || HW < 1) return RT_E_INVALID;
     GroupNormArgs a{}; a.in_bf16 = in_type; a.C1 = C1; a.C2 = C2; a.G = G; a.B = B; a.HW = HW;
     return groupnorm_form(a);
+}
+// ---- the VAE's kernels beyond the contractions (vae_kernels.hip; GroupNorm forward with the low planes: norm.hip), one call each, with the
+// launch arguments of vae.h
+int rt_op_vae_groupnorm_nchunk(int HW) { return HW < 1 ? RT_E_INVALID : vae_gn_nchunk(HW); }
+int rt_op_vae_groupnorm(const void* x, int x_bf16, int C, int G, int B, int HW, const float* gamma, const float* beta, float eps, int silu, void* out,
+                        void* out_lo, void* raw, void* raw_lo, float* stats, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(x && out && stats && gamma && beta && (x_bf16 == 0 || x_bf16 == 1) && C > 0 && B >= 1 && HW >= 1, "rt_op_vae_groupnorm: bad argument");
+        RT_REQUIRE(!raw_lo || raw, "rt_op_vae_groupnorm: raw_lo without raw");
+        launch_groupnorm(vae_gn_fwd_args(x, x_bf16 != 0, C, G, B, HW, gamma, beta, eps, silu != 0, (bf16_t*)out, (bf16_t*)out_lo, (bf16_t*)raw, (bf16_t*)raw_lo, stats),
+                         (hipStream_t)stream);
+    })
+}
+int rt_op_vae_groupnorm_bwd(const void* x, int x_bf16, const void* dA, const void* dA_lo, const float* stats, const float* gamma, const float* beta, float eps,
+                            int silu, int C, int G, int B, int HW, const float* add, float* out, void* out_bf16, void* out_bf16_lo, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(x && dA && stats && gamma && beta && (x_bf16 == 0 || x_bf16 == 1) && C > 0 && G >= 1 && B >= 1 && HW >= 1, "rt_op_vae_groupnorm_bwd: bad argument");
+        RT_REQUIRE(!out_bf16_lo || out_bf16, "rt_op_vae_groupnorm_bwd: out_bf16_lo without out_bf16");
+        float* bp = nullptr;
+        HIP_CHECK(hipMalloc((void**)&bp, (size_t)B * vae_gn_nchunk(HW) * G * 2 * 4));
+        try {
+            launch_groupnorm_bwd(vae_gn_bwd_args(x, x_bf16 != 0, (const bf16_t*)dA, (const bf16_t*)dA_lo, stats, bp, C, G, B, HW, gamma, beta, eps, silu != 0, add, out,
+                                                 (bf16_t*)out_bf16, (bf16_t*)out_bf16_lo), (hipStream_t)stream);
+            HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+        } catch (...) { (void)hipFree(bp); throw; }
+        HIP_CHECK(hipFree(bp));
+    })
+}
+int rt_op_softmax_rows(const float* s, void* p, void* p_lo, int rows, int cols, float scale, void* stream) {
+    OP_TRY({ RT_REQUIRE(s && p && rows >= 1 && cols >= 1, "rt_op_softmax_rows: bad argument"); launch_softmax_rows(s, (bf16_t*)p, rows, cols, scale, (hipStream_t)stream, (bf16_t*)p_lo); })
+}
+int rt_op_softmax_bwd(const void* p, const void* p_lo, const float* dp, void* ds, void* ds_lo, int rows, int cols, float scale, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(p && dp && ds && rows >= 1 && cols >= 1, "rt_op_softmax_bwd: bad argument");
+        launch_softmax_bwd((const bf16_t*)p, dp, (bf16_t*)ds, rows, cols, scale, (hipStream_t)stream, (const bf16_t*)p_lo, (bf16_t*)ds_lo);
+    })
+}
+int rt_op_transpose_bf16(const void* in, void* out, int R, int C, void* stream) {
+    OP_TRY({ RT_REQUIRE(in && out && R >= 1 && C >= 1, "rt_op_transpose_bf16: bad argument"); launch_transpose_bf16((const bf16_t*)in, (bf16_t*)out, R, C, (hipStream_t)stream); })
+}
+int rt_op_sumpool2x2(const float* in, float* out, int B, int H, int W, int C, void* stream) {
+    OP_TRY({ RT_REQUIRE(in && out && B >= 1 && H >= 1 && W >= 1 && C >= 4, "rt_op_sumpool2x2: bad argument"); launch_sumpool2x2(in, out, B, H, W, C, (hipStream_t)stream); })
+}
+int rt_op_pq_conv_fwd(const float* lat, const float* eps, float c_lat, float c_eps, const float* W, const float* b, void* out, void* out_lo, int HW, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(lat && W && b && out && HW >= 1, "rt_op_pq_conv_fwd: bad argument");
+        launch_pq_conv_fwd(lat, eps, c_lat, c_eps, W, b, (bf16_t*)out, HW, (hipStream_t)stream, (bf16_t*)out_lo);
+    })
+}
+int rt_op_pq_conv_bwd_update(const float* dz, int ldz, const float* W, float gscale, float weight, const float* mask_all, float* lat, float* grad_out, int HW,
+                             void* stream) {
+    OP_TRY({
+        RT_REQUIRE(dz && W && mask_all && lat && ldz >= 4 && HW >= 1, "rt_op_pq_conv_bwd_update: bad argument");
+        launch_pq_conv_bwd_update(dz, ldz, W, gscale, weight, mask_all, lat, grad_out, HW, (hipStream_t)stream);
+    })
+}
+int rt_op_color_loss_grad(const float* img, int ldi, const float* masks, const float* target_dev, int n, int HWi, void* dimg, void* dimg_lo, float* loss_dev,
+                          void* stream) {
+    OP_TRY({
+        RT_REQUIRE(img && masks && target_dev && dimg && ldi >= 3 && HWi >= 1 && n >= 1 && n <= RT_MAXB, "rt_op_color_loss_grad: bad argument");
+        float* part = nullptr;
+        HIP_CHECK(hipMalloc((void**)&part, vae_color_partial_floats(n) * 4));
+        try {
+            launch_color_loss_grad(vae_color_args(img, ldi, masks, target_dev, n, HWi, part, (bf16_t*)dimg, (bf16_t*)dimg_lo, loss_dev), (hipStream_t)stream);
+            HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+        } catch (...) { (void)hipFree(part); throw; }
+        HIP_CHECK(hipFree(part));
+    })
 }
 int rt_op_layernorm(const float* x, const float* gamma, const float* beta, void* out, int rows, int C, float eps, void* stream) {
     OP_TRY({ launch_layernorm(x, 0, gamma, beta, (bf16_t*)out, rows, C, eps, (hipStream_t)stream); })

@@ -232,30 +232,16 @@ struct rt_vae {
     void require_bound() { for (auto& s : slots) if (!s.bound) throw rt_error(RT_E_MISSING_WEIGHT, "vae weight not bound: " + s.name); }
 
     // ---------------------------------------------------------------- launch helpers
+    // (the launch arguments themselves: vae.h, shared with the rt_op_* entries of the same kernels)
     void gemm1(const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, int M, int N, int K, void* out, int ldo, int epi,
                const float* res, int ldres, const bf16_t* A_lo = nullptr, const bf16_t* W_lo = nullptr) {
-        GemmArgs g{}; g.A = A; g.W = W; g.bias = bias; g.out = out; g.res = res; g.zero = zero; g.mode = A_DENSE; g.epi = epi;
-        g.A_lo = A_lo; g.W_lo = W_lo;
-        g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.ldres = ldres;
-        launch_gemm(g, stream);
+        launch_gemm(vae_gemm_args(A, lda, W, ldw, bias, M, N, K, out, ldo, epi, res, ldres, A_lo, W_lo, zero), stream);
     }
     // pair_lo != null: try to get the fp32 result as the bf16 (hi, lo) pair straight from the kernel (out = hi plane); returns false -
     // nothing launched - when the route launch_gemm takes for this problem cannot (the caller then asks for fp32 and splits)
     bool conv1(const bf16_t* in, int mode, const bf16_t* W, const float* bias, int N, int K, int H, int Wd, int CinP, void* out, int epi, const float* res,
                const bf16_t* in_lo = nullptr, const bf16_t* W_lo = nullptr, bf16_t* pair_lo = nullptr) {
-        int Ho = H, Wo = Wd;
-        if (mode == A_CONV3_UP2) { Ho = 2 * H; Wo = 2 * Wd; }
-        if (mode == A_CONV3_S2P0) { Ho = H / 2; Wo = Wd / 2; }
-        GemmArgs g{}; g.A = in; g.W = W; g.bias = bias; g.out = out; g.res = res; g.zero = zero; g.mode = mode; g.epi = epi;
-        g.A_lo = in_lo; g.W_lo = W_lo; g.pair_lo = pair_lo;
-        g.M = Ho * Wo; g.N = N; g.K = K; g.ldw = K; g.ldo = N; g.ldres = N; g.rows_per_batch = Ho * Wo; g.Hin = H; g.Win = Wd; g.Cin = CinP;
-        g.Hout = Ho; g.Wout = Wo;
-        RT_REQUIRE(K == 9 * CinP, "vae conv: weight/input channel mismatch");
-        // one image: the 224 x 256 tiles of the GEMM-loop convolution fill the chip only from 256^2 x 256 channels upwards (SD 64^2
-        // latent: 13.1 ms per guidance call with every layer on it, 11.3 ms on the patch kernel; SDXL 128^2: 39.7 vs 41.0 the other way)
-        // ... and every hi / lo (precise) contraction: as ONE launch of three passes the patch kernel runs the 128-channel layers at 1.6 PF
-        // where the GEMM-loop form of the 256-channel layers reaches 0.86 (profiles/r4_vae_precise_kernel_stats.csv)
-        g.prefer_patch_conv = in_lo != nullptr || (long)g.M * N < 192L * 224 * 256;
+        const GemmArgs g = vae_conv_args(in, mode, W, K, bias, N, K, H, Wd, CinP, out, N, epi, res, N, in_lo, W_lo, pair_lo, zero);
         if (pair_lo && !gemm_pair_output_ok(g)) return false;
         launch_gemm(g, stream);
         return true;
@@ -310,24 +296,16 @@ struct rt_vae {
         return o;
     }
     float* gn_fwd(const void* x, bool x_bf16, int C, int HW, const NormW& n, bool silu, BT out, BT raw) {
-        const int rpc = groupnorm_bwd_rows_per_chunk(HW), nchunk = (HW + rpc - 1) / rpc;      // the VAE's own chunk rule (norm.hip)
-        float* part = f32((size_t)nchunk * G * 2);
+        float* part = f32((size_t)vae_gn_nchunk(HW) * G * 2);                                  // the VAE's own chunk rule (norm.hip)
         if (dry) return part;
-        GroupNormArgs a{}; a.x1 = x; a.in_bf16 = x_bf16; a.C1 = C; a.C2 = 0; a.G = G; a.B = 1; a.HW = HW; a.gamma = n.g; a.beta = n.b; a.eps = 1e-6f;
-        a.silu = silu; a.out = out.hi; a.out_lo = out.lo; a.raw_out = raw.hi; a.raw_lo = raw.lo; a.partial = part; a.nchunk = nchunk;
-        a.rows_per_chunk = rpc;
-        launch_groupnorm(a, stream);
+        launch_groupnorm(vae_gn_fwd_args(x, x_bf16, C, G, 1, HW, n.g, n.b, 1e-6f, silu, out.hi, out.lo, raw.hi, raw.lo, part), stream);
         return part;
     }
     void gn_bwd(const void* x, bool x_bf16, BT dA, const float* fwd_part, int C, int HW, const NormW& n, bool silu, const float* add,
                 float* out, BT out_b) {
-        const int rpc = groupnorm_bwd_rows_per_chunk(HW), nchunk = (HW + rpc - 1) / rpc;      // (B = 1: the forward's statistics are at fwd_part[2 g] whatever its chunking)
-        float* bp = f32((size_t)nchunk * G * 2);
+        float* bp = f32((size_t)vae_gn_nchunk(HW) * G * 2);
         if (dry) return;
-        GroupNormBwdArgs a{}; a.x = x; a.x_bf16 = x_bf16; a.dA = dA.hi; a.dA_lo = dA.lo; a.fwd_partial = fwd_part; a.bwd_partial = bp; a.gamma = n.g; a.beta = n.b;
-        a.eps = 1e-6f; a.silu = silu; a.C = C; a.G = G; a.B = 1; a.HW = HW; a.nchunk = nchunk; a.rows_per_chunk = rpc; a.add = add;
-        a.out = out; a.out_bf16 = out_b.hi; a.out_bf16_lo = out_b.lo;
-        launch_groupnorm_bwd(a, stream);
+        launch_groupnorm_bwd(vae_gn_bwd_args(x, x_bf16, dA.hi, dA.lo, fwd_part, bp, C, G, 1, HW, n.g, n.b, 1e-6f, silu, add, out, out_b.hi, out_b.lo), stream);
     }
     BT transp(BT in, int R, int C) {
         BT o = bt((size_t)R * C);
@@ -629,9 +607,9 @@ int rt_vae_color_guidance(rt_vae* v, float* latents, const float* noise_pred, fl
         const int HWi = tp.Hi * tp.Wi;
         float* tgt = v->f32((size_t)n_regions * 3 + 4);
         HIP_CHECK(hipMemcpyAsync(tgt, target_rgb_host, (size_t)n_regions * 12, hipMemcpyHostToDevice, v->stream));
-        ColorLossArgs c{}; c.img = img; c.ldi = v->conv_out.f.N; c.masks = masks_img; c.target = tgt; c.n = n_regions; c.HWi = HWi;
         BT dimg = v->bt((size_t)HWi * 8);
-        c.nblk = 1024; c.partial = v->f32((size_t)c.nblk * n_regions * 4); c.dimg = dimg.hi; c.dimg_lo = dimg.lo; c.loss_out = v->f32(4);
+        float* cpart = v->f32(vae_color_partial_floats(n_regions));
+        const ColorLossArgs c = vae_color_args(img, v->conv_out.f.N, masks_img, tgt, n_regions, HWi, cpart, dimg.hi, dimg.lo, v->f32(4));
         launch_color_loss_grad(c, v->stream);
         float* dz = v->backward(tp, dimg, h, w);
         launch_pq_conv_bwd_update(dz, 4, v->pq_w, 1.f / (sa * sc), weight, mask_all, latents, grad_out, h * w, v->stream);

@@ -240,18 +240,6 @@ void launch_sumpool2x2(const float* in, float* out, int B, int H, int W, int C, 
     hipLaunchKernelGGL(sumpool2x2_kernel, dim3(grid), dim3(256), 0, st, in, out, B, H, W, C / 4);
     HIP_CHECK(hipGetLastError());
 }
-__global__ void add_f32_kernel(const float* a, const float* b, float* out, size_t n4) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float4 x = ((const float4*)a)[i], y = ((const float4*)b)[i];
-        ((float4*)out)[i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
-    }
-}
-void launch_add_f32(const float* a, const float* b, float* out, size_t n, hipStream_t st) {
-    RT_REQUIRE(n % 4 == 0, "add: n % 4");
-    int grid = (int)((n / 4 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(add_f32_kernel, dim3(grid), dim3(256), 0, st, a, b, out, n / 4);
-    HIP_CHECK(hipGetLastError());
-}
 
 // ---------------------------------------------------------------- post_quant_conv (1x1, 4 -> 4) fused with predict_x0 / scaling
 // z0 = (c_lat * lat + c_eps * eps)  [= predict_x0(lat, eps) / scaling_factor];  out = W z0 + b

@@ -1,5 +1,6 @@
 """The GEMM / convolution case table of the memory-contract tests, shared by tests/test_gemm_route.py (CPU: every case takes the route it
-is listed under, asked through rt_op_gemm_route) and tests/test_memory_contract_gpu.py (GPU: runs them).  Plain data, no torch.
+is listed under, asked through rt_op_gemm_route) and tests/test_memory_contract_gpu.py (GPU: runs them); further down HILO_CASES, the
+VAE's hi / lo contraction behind rt_op_gemm_hilo (route query: rt_op_gemm_hilo_route; GPU: tests/test_vae_ops_gpu.py).  Plain data, no torch.
 
 A case is one rt_op_gemm call: `mode` 0 dense [M, N, K] | 1 / 2 / 3 a 3x3 convolution (stride 1 / stride 2 / nearest-2x up-sample folded
 in) of a [B, H, W, Cin] image to Cout channels; `epi` as rt_op_gemm; `cfg` = rt_op_gemm_force_config, `debug` = rt_op_gemm_debug word
@@ -16,9 +17,9 @@ NO_CHUNK_SPLIT = 1 << 28          # rt_op_gemm_debug bit 28: under-filled 3x3 co
 GEGLU_CFGS = (0, 1, 3, 5, 7)      # tile configurations with a GEGLU epilogue (kCfg[].geglu_ok); a forced other one falls back to 0
 
 # (route kind, epilogue) pairs that exist behind rt_op_gemm / rt_op_upconv - from launch_routed / launch_with_cfg / launch_conv3p /
-# splitk_reduce_kernel / gemm16_supported.  TRIPLE (the precise VAE's hi / lo contraction) needs GemmArgs.A_lo, which only rt_vae_* sets:
-# not reachable through the operator ABI, left out.  G16_UP2 needs the phase pack, which only rt_op_upconv passes (it reports the route
-# itself as *phase_route; UPCONV_CASES below).
+# splitk_reduce_kernel / gemm16_supported.  TRIPLE (the precise VAE's hi / lo contraction) needs GemmArgs.A_lo, which rt_op_gemm does not
+# take: it and the one-launch hi / lo forms are reached through rt_op_gemm_hilo (HILO_CASES / HILO_FORMS below).  G16_UP2 needs the phase
+# pack, which only rt_op_upconv passes (it reports the route itself as *phase_route; UPCONV_CASES below).
 IMPLEMENTED = {
     TILE: {0, 1, 2, 3, 4},
     G16: {0, 1, 2, 3, 4},          # 2: the convolution form (time embedding); 3: dense GEGLU
@@ -96,6 +97,69 @@ GEMM_CASES += [conv(PATCH_SPLIT, 1, 4, 3, 16, 16, 1280, 1280, slices=7), conv(PA
 GEMM_CASES += [conv(KSPLIT, 1, 4, 3, 16, 16, 1280, 1280, debug=NO_CHUNK_SPLIT), conv(KSPLIT, 1, 2, 1, 16, 16, 512, 64, debug=NO_CHUNK_SPLIT),
                conv(KSPLIT, 1, 0, 1, 16, 32, 64, 96), conv(KSPLIT, 1, 1, 1, 8, 24, 64, 72), conv(KSPLIT, 2, 1, 2, 12, 20, 64, 64),
                conv(KSPLIT, 3, 4, 1, 8, 8, 64, 96), conv(KSPLIT, 1, 4, 3, 20, 24, 128, 160), conv(KSPLIT, 1, 2, 3, 20, 24, 128, 160)]
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# rt_op_gemm_hilo: the VAE's contraction A W + A_lo W + A W_lo (fp32 output, ONE image, prefer_patch_conv by the VAE's own rule).  `kind`
+# is what rt_op_gemm_hilo_route reports for the hi / lo call - the route of the ONE launch that runs the three passes (G16 dense, PATCH
+# convolutions), or TRIPLE - and `pass_kind` the route of each of TRIPLE's three launches (= kind for the fused forms).  mode 0 dense |
+# 1 stride-1 conv | 3 up-2 conv | 4 stride-2 conv with bottom / right padding.  res: None | "res" | "inplace" (out == res, attn_bwd's
+# accumulation); pair: the bf16 pair output (patch kernel only); wact: W is an activation pair (attention products: no bias).
+# Where a candidate shape of the issue landed elsewhere it is listed where it landed (see the notes next to it).
+TRIPLE_ALL, TRIPLE_PATCH, TRIPLE_DENSE = 1 << 7, 1 << 9, 1 << 15          # rt_op_gemm_debug bits 7 / 9 / 15: the fused forms as three launches
+
+
+def hdense(kind, pass_kind, M, N, K, debug=0, bias=True, res=None, wact=False):
+    return dict(kind=kind, pass_kind=pass_kind, mode=0, M=M, N=N, K=K, debug=debug, bias=bias and not wact, res=res, pair=False, wact=wact)
+
+
+def hconv(kind, pass_kind, mode, H, W, Cin, Cout, debug=0, bias=True, res=None, pair=False):
+    return dict(kind=kind, pass_kind=pass_kind, mode=mode, H=H, W=W, Cin=Cin, Cout=Cout, debug=debug, bias=bias, res=res, pair=pair, wact=False)
+
+
+def hilo_out_hw(c):
+    return {1: (c["H"], c["W"]), 3: (2 * c["H"], 2 * c["W"]), 4: (c["H"] // 2, c["W"] // 2)}[c["mode"]]
+
+
+def hilo_id(c):
+    tail = (f"-dbg{c['debug']:x}" if c["debug"] else "") + ("" if c["bias"] else "-nobias") + (f"-{c['res']}" if c["res"] else "") + ("-pair" if c["pair"] else "")
+    head = KIND_NAMES[c["kind"]] + ("" if c["pass_kind"] == c["kind"] else "/" + KIND_NAMES[c["pass_kind"]])
+    if c["mode"] == 0:
+        return f"{head}-dense-{c['M']}x{c['N']}x{c['K']}{tail}"
+    return f"{head}-conv{c['mode']}-{c['H']}x{c['W']}x{c['Cin']}to{c['Cout']}{tail}"
+
+
+def hilo_route_args(c, pad=0, hilo=True):
+    """(hilo, pair, mode, M, N, K, lda, ldw, ldo, rows_per_batch, Hin, Win, Cin, Hout, Wout) of rt_op_gemm_hilo_route."""
+    if c["mode"] == 0:
+        return (int(hilo), 0, 0, c["M"], c["N"], c["K"], c["K"] + pad, c["K"] + pad, c["N"] + pad, 0, 0, 0, 0, 0, 0)
+    Ho, Wo = hilo_out_hw(c)
+    K = 9 * c["Cin"]
+    return (int(hilo), int(c["pair"]), c["mode"], Ho * Wo, c["Cout"], K, 0, K + pad, c["Cout"] + pad, Ho * Wo, c["H"], c["W"], c["Cin"], Ho, Wo)
+
+
+HILO_CASES = []
+# ---- fused dense on the 16x16x32 family, with a residual, accumulating in place, and without bias
+HILO_CASES += [hdense(G16, G16, 300, 256, 256), hdense(G16, G16, 300, 256, 256, res="res"), hdense(G16, G16, 300, 256, 256, res="inplace", bias=False)]
+# ---- three launches of a gemm.hip tile configuration: K tail through the zero page in both planes (200 = 3 x 64 + 8); the attention
+#      products with activation pairs on both sides; Cin = 8; the encoder's stride-2 convolution (Cin = 48: K = 432 < 512 is not sliced - the
+#      issue's 1 x 12 x 20 x 64 -> 64 has K = 576 and 1 tile: two K slices, listed under KSPLIT below)
+HILO_CASES += [hdense(TRIPLE, TILE, 300, 200, 200), hdense(TRIPLE, TILE, 300, 200, 200, res="inplace", bias=False),
+               hdense(TRIPLE, TILE, 240, 240, 64, wact=True), hdense(TRIPLE, TILE, 240, 64, 240, wact=True),
+               hconv(TRIPLE, TILE, 1, 8, 24, 8, 72), hconv(TRIPLE, TILE, 4, 12, 20, 48, 64)]
+# ---- three launches of the split-K form (the K rule slices each pass): dense, a small 64-channel convolution, conv_out's N = 4
+HILO_CASES += [hdense(TRIPLE, KSPLIT, 72, 512, 512), hdense(TRIPLE, KSPLIT, 72, 512, 512, res="res"),
+               hconv(TRIPLE, KSPLIT, 1, 16, 16, 64, 96), hconv(TRIPLE, KSPLIT, 1, 16, 16, 64, 4), hconv(TRIPLE, KSPLIT, 4, 12, 20, 64, 64)]
+# ---- the patch kernel's one-launch form: with / without residual, with / without the pair output; behind the 2x up-sample
+HILO_CASES += [hconv(PATCH, PATCH, 1, 64, 112, 64, 136), hconv(PATCH, PATCH, 1, 64, 112, 64, 136, res="res"),
+               hconv(PATCH, PATCH, 1, 64, 112, 64, 136, pair=True), hconv(PATCH, PATCH, 1, 64, 112, 64, 136, bias=False, pair=True),
+               hconv(PATCH, PATCH, 3, 32, 56, 64, 136), hconv(PATCH, PATCH, 3, 32, 56, 64, 136, res="res")]
+# ---- every fused form again as three launches (debug bits 7, 9, 15); the pair output survives on the patch kernel's single passes
+HILO_CASES += [hdense(TRIPLE, G16, 300, 256, 256, debug=TRIPLE_DENSE), hdense(TRIPLE, G16, 300, 256, 256, debug=TRIPLE_ALL, res="res"),
+               hdense(TRIPLE, G16, 300, 256, 256, debug=TRIPLE_DENSE, res="inplace", bias=False),
+               hconv(TRIPLE, PATCH, 1, 64, 112, 64, 136, debug=TRIPLE_PATCH, res="res"), hconv(TRIPLE, PATCH, 1, 64, 112, 64, 136, debug=TRIPLE_ALL),
+               hconv(TRIPLE, PATCH, 3, 32, 56, 64, 136, debug=TRIPLE_PATCH), hconv(TRIPLE, PATCH, 3, 32, 56, 64, 136, debug=TRIPLE_ALL, res="res")]
+# the forms of the hi / lo contraction that exist: each needs a case (tests/test_gemm_route.py)
+HILO_FORMS = {(G16, G16), (PATCH, PATCH), (TRIPLE, TILE), (TRIPLE, KSPLIT), (TRIPLE, G16), (TRIPLE, PATCH)}
 
 # rt_op_gemm16_variant (no routing: the caller names the tile): (variant, N, weights_on_rows, epilogues), M = 300 / K = 256 everywhere.
 # One class A variant per tile height (3: 256 rows, 2: 224, 8: 128, 11: 64), the class B variants 0, 1, 9, the V^T variants 6, 7, 12.

@@ -1,13 +1,14 @@
 """Host-only route queries (no GPU): rt_op_gemm_route answers for exactly the GemmArgs rt_op_gemm builds, rt_op_groupnorm_form from the
 GroupNorm launcher's own predicate.  The case table of the memory-contract tests (tests/memcases.py) is evaluated through them: every case
 takes the route it is listed under - with contiguous and with padded leading dimensions alike - and every (route, epilogue) pair that
-exists behind the operator ABI has at least one case."""
+exists behind the operator ABI has at least one case.  The VAE's hi / lo contraction (rt_op_gemm_hilo, HILO_CASES) likewise, through
+rt_op_gemm_hilo_route: three launches over every single-pass route, and every one-launch form."""
 import ctypes as C
 
 import pytest
 
-from memcases import (G16, G16_UP2, GEMM_CASES, IMPLEMENTED, KIND_NAMES, KSPLIT, PATCH, PATCH_SPLIT, TILE, TRIPLE, UPCONV_CASES, case_id,
-                      route_args)
+from memcases import (G16, G16_UP2, GEMM_CASES, HILO_CASES, HILO_FORMS, IMPLEMENTED, KIND_NAMES, KSPLIT, PATCH, PATCH_SPLIT, TILE, TRIPLE,
+                      TRIPLE_ALL, TRIPLE_DENSE, TRIPLE_PATCH, UPCONV_CASES, case_id, hilo_id, hilo_route_args, route_args)
 from rich_text_to_image_amd.engine import load_library
 
 
@@ -58,13 +59,60 @@ def test_every_route_and_epilogue_has_a_case():
     have = {(c["kind"], c["epi"]) for c in GEMM_CASES}
     have |= {(G16_UP2, 4) for u in UPCONV_CASES if u[6] == 1}
     want = {(k, e) for k, epis in IMPLEMENTED.items() for e in epis}
-    assert TRIPLE not in IMPLEMENTED                                  # needs the hi / lo operands of rt_vae_*: not behind the operator ABI
+    # the hi / lo contraction (rt_op_gemm_hilo): TRIPLE over every single-pass route the VAE's shapes take, and every one-launch form
+    have_hilo = {(c["kind"], c["pass_kind"]) for c in HILO_CASES}
+    assert have_hilo == HILO_FORMS, sorted(HILO_FORMS ^ have_hilo)
+    assert {p for k, p in HILO_FORMS if k == TRIPLE} == {TILE, KSPLIT, G16, PATCH} and {k for k, _ in HILO_FORMS if k != TRIPLE} == {G16, PATCH}
+    for form in HILO_FORMS:                                           # each form with and without a residual; in place on both dense forms
+        assert {bool(c["res"]) for c in HILO_CASES if (c["kind"], c["pass_kind"]) == form} == {False, True}, form
+    assert {c["kind"] for c in HILO_CASES if c["res"] == "inplace"} == {G16, TRIPLE}
+    assert any(c["pair"] for c in HILO_CASES) and any(not c["bias"] and not c["wact"] for c in HILO_CASES)
+    assert {c["debug"] for c in HILO_CASES} == {0, TRIPLE_ALL, TRIPLE_PATCH, TRIPLE_DENSE}
     missing = sorted(want - have)
     assert not missing, [f"{KIND_NAMES[k]} epi {e}" for k, e in missing]
     assert {k for k, _ in have} == {TILE, G16, G16_UP2, PATCH, PATCH_SPLIT, KSPLIT}
     # all nine tile configurations, every reduction epilogue of both split forms
     assert {c["cfg"] for c in GEMM_CASES if c["kind"] == TILE and c["mode"] == 0} >= set(range(9))
     assert {c["epi"] for c in GEMM_CASES if c["kind"] == KSPLIT and c["mode"] == 0} == {0, 1, 2, 3, 4}
+
+
+def hilo_route(lib, args):
+    o = [C.c_int(-9) for _ in range(5)]
+    assert lib.rt_op_gemm_hilo_route(*args, *[C.byref(x) for x in o]) == 0, args
+    return tuple(x.value for x in o)                                   # kind, variant_or_cfg, slices, pass_kind, pair_ok
+
+
+@pytest.mark.parametrize("case", HILO_CASES, ids=hilo_id)
+def test_hilo_case_takes_the_route_it_is_listed_under(case):
+    lib = load_library()
+    with switches(lib, -1, case["debug"]):
+        plain, padded = hilo_route(lib, hilo_route_args(case)), hilo_route(lib, hilo_route_args(case, pad=8))
+        single = hilo_route(lib, hilo_route_args(case, hilo=False))
+    assert plain == padded, "a leading dimension changed the route"
+    kind, _, slices, pass_kind, pair_ok = plain
+    assert (kind, pass_kind) == (case["kind"], case["pass_kind"]), f"{hilo_id(case)} takes {KIND_NAMES[kind]} over {KIND_NAMES[pass_kind]}, slices {slices}"
+    assert (slices > 1) == (pass_kind == KSPLIT)
+    # the pair output exists on the patch kernel's ONE launch only; the single-pass call (A_lo == NULL) takes the route of one TRIPLE pass
+    assert pair_ok == int(kind == PATCH) and (not case["pair"] or pair_ok)
+    assert single[0] == single[3] == pass_kind and single[2] == slices
+
+
+def test_hilo_route_query_refuses_nonsense():
+    lib = load_library()
+    conv = (1, 0, 1, 7168, 136, 576, 0, 576, 136, 7168, 64, 112, 64, 64, 112)
+    assert hilo_route(lib, conv)[0] == PATCH
+    outs = [None] * 5
+    assert lib.rt_op_gemm_hilo_route(*conv, *outs) == 0               # every output is optional
+    k = C.c_int(-7)
+    for bad in [(1, 0, 2) + conv[3:],                                  # stride 2 with symmetric padding: not a VAE mode
+                (1, 0, 1, 7168 * 2) + conv[4:],                        # two images
+                (1, 0, 1, 7168, 136, 584) + conv[6:],                  # K != 9 Cin
+                (1, 1, 0, 300, 256, 256, 256, 256, 256, 0, 0, 0, 0, 0, 0),      # a dense pair output
+                (1, 0, 0, 0, 256, 256, 256, 256, 256, 0, 0, 0, 0, 0, 0)]:
+        assert lib.rt_op_gemm_hilo_route(*bad, C.byref(k), None, None, None, None) != 0 and k.value == -7, bad
+    assert lib.rt_op_vae_groupnorm_nchunk(0) < 0
+    # the VAE's chunk rule: HW / 128 rows clamped to [16, 128]
+    assert [lib.rt_op_vae_groupnorm_nchunk(hw) for hw in (48, 50, 144, 200, 400, 2304, 16384, 1 << 20)] == [3, 4, 9, 13, 25, 128, 128, 8192]
 
 
 def test_route_query_follows_the_switches_and_refuses_nonsense():

@@ -16,8 +16,8 @@ Memory INSIDE an operand's declared extent that the contract calls "anything fin
 holds alternating-sign junk of magnitude 1e3, not NaN; NaN goes only where a kernel must not look.
 
 Shapes are the smallest that reach the route (tests/memcases.py, checked on the CPU by tests/test_gemm_route.py) with a ragged last row
-tile and, where the kernel allows, a ragged last column chunk and K tail.  Not covered: the precise VAE's hi / lo routes (TRIPLE and the
-three-pass kernels), which only rt_vae_* reaches.
+tile and, where the kernel allows, a ragged last column chunk and K tail.  The precise VAE's hi / lo routes (TRIPLE and the three-pass
+kernels) and the VAE's other kernels get the same contract in tests/test_vae_ops_gpu.py, through rt_op_gemm_hilo and its siblings.
 """
 import ctypes as C
 import math
