@@ -441,6 +441,24 @@ int rt_op_attention_store_handover(const void* Q, int ldq, const void* K, int ld
                                    const int* qk_src_host, const int* prompt_host, const int* key_counts_host, const float* wabs,
                                    const float* wsgn, int B, int H, int N, int NK, int d, int DP, int cross, int store_stream,
                                    float* map_out, int accumulate, int* handover, void* stream);
+/* Host-only query (no device needed; tests/test_cross_route.py): the route of an attn2 launch as the UNet forward decides it - cross_route
+ * of csrc/engine.hip, the one function the forward and every entry that launches cross-attention ask - under the current switches
+ * (rt_op_gemm_debug bits 4, 16, 17, 19).  The layer: C channels, `heads` heads of dim d padded to DP, `tokens` queries per stream; the
+ * prompts: prompt_rows (96, 192 or 288) cached rows each, stream b with key_counts_host[b] = 77, 154 or 231 valid keys; folded: the
+ * LayerNorm is folded into to_q; recorded: the layer's token map is enabled in this forward.
+ * *kind: RT_CROSS_* below; *handover: 1 when the launch may leave the recorded stream's softmax statistics for the store (what
+ * rt_op_attention_store_handover reports for the same arguments; the forward does so from the layer's eleventh recorded call on);
+ * stream_kernel (may be NULL) [B]: the kernel that computes stream b - 0 attn_kernel, 1 cross77_kernel, 2 crossmw_kernel, -1 one of the
+ * two one-launch forms.  An entry that has no d passes DP (every kernel but attn_kernel needs d = DP = 64).
+ * RT_E_INVALID for what rt_op_attention_keys refuses: B outside [1, 16], another prompt_rows, a key count that is not 77 c or exceeds
+ * the 77 / 96 of prompt_rows. */
+enum { RT_CROSS_GENERIC = 0     /* attn_kernel */,
+       RT_CROSS_CROSS77 = 1     /* d = 64, tokens % 64 == 0, every stream 77 keys: cross77_kernel */,
+       RT_CROSS_RUNS = 2        /* that shape with different key counts: maximal runs of 77-key streams on cross77_kernel, of longer ones on crossmw_kernel */,
+       RT_CROSS_XATTN_FUSED = 3 /* to_q + attention as one launch (PROBES=1 builds) */,
+       RT_CROSS_XBLOCK = 4      /* to_q, attention and to_out + residual as one launch (PROBES=1 builds, rt_op_gemm_debug bit 16) */ };
+int rt_op_cross_route(int C, int heads, int d, int DP, int tokens, int prompt_rows, const int* key_counts_host, int B, int folded,
+                      int recorded, int* kind, int* handover, int* stream_kernel);
 const char* rt_op_last_error(void);
 /* GEMM tile choice: -1 (default) = a pure function of the problem shape (csrc/gemm16.hip: 16x16x32-MFMA family, 224-row tiles;
  * csrc/gemm.hip: 32x32x16 family for everything else) - no timing, no per-process state; 0..8 = force one tile configuration of

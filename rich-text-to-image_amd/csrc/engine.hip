@@ -132,19 +132,11 @@ struct FwdIn {
 };
 
 extern int g_store_own_stats;
-static inline bool g_store_own_stats_flag() { return g_store_own_stats != 0; }
-// The statistics hand-over of a recorded layer (attn_store.hip, stats_ready), shared by the UNet forward and rt_op_attention_store_handover:
-// self-attention - the launch leaves (m, 1 / (H l)) of the recorded stream when the store would run its statistics + apply pair for the map
-// and the stream attends with its own Q / K (an injected stream's scores are another stream's);
+// The statistics hand-over of a recorded self-attention layer (attn_store.hip, stats_ready; cross-attention: cross_route): the launch leaves (m, 1 / (H l))
+// of the recorded stream when the store would run its statistics + apply pair and the stream attends with its own Q / K, not an injected stream's.
 static inline bool store_handover_self(int tokens, int DP, const int* qk_src, int stream) {
     return attn_store_takes_stats(tokens, tokens, DP) && qk_src[stream] == stream;
 }
-// cross-attention - the launch runs on cross77_kernel (head dim 64, every stream of the launch with 77 keys) ...
-static inline bool cross77_route(int heads, int DP, int d, int tokens, int prompt_rows, bool all77) {
-    return all77 && gemm_cross77_enabled() && cross77_supported(heads, DP, tokens, prompt_rows, 77) && d == 64;
-}
-// ... and debug bit 17 is clear.
-static inline bool store_handover_cross(bool on_cross77) { return on_cross77 && !g_store_own_stats_flag(); }
 // step epilogue (defined in step.hip)
 struct StepArgs;
 struct SolverArgs;
@@ -168,16 +160,52 @@ void launch_source_blend(float* lat, const float* x0, const float* noise, const 
 #include "guided.h"
 #include "vae.h"
 
-// Cross-attention of a launch whose streams have DIFFERENT key counts (prompts of one to three 77-token windows), where the shape has
-// cross77_kernel: the kernel of a stream is a function of its OWN key count - maximal runs of 77-key streams go to cross77_kernel, the
-// runs of longer ones to crossmw_kernel (cross77.hip: all 154 / 231 keys of the head in LDS) - so a one-window stream computes the
-// bits it computes alone or in a launch of one-window streams, whatever its neighbours are.  A run is the same launch on offset Q / O pointers (cross launches read Q of their
-// own batch entry).  No statistics hand-over on this route (the cross-map store then computes its own).
-static void launch_cross_runs(const AttnArgs& a, hipStream_t st) {
-    for (int b0 = 0; b0 < a.B;) {
-        const bool one = a.nkeys[b0] == 77;
-        int b1 = b0;
-        while (b1 < a.B && (a.nkeys[b1] == 77) == one) ++b1;
+// ------------------------------------------------------------------------------------------------
+// The route of an attn2 (cross-attention) launch: the ONE place that decides which kernel runs it and whether the launch may leave its
+// softmax statistics for the token-map store - asked by the UNet forward, every rt_op_* entry that launches cross-attention and the host-only
+// rt_op_cross_route.  A function of the layer's shape and the streams' key counts (77 per chunk), never of the capacity: prompt_rows (96 per
+// chunk the caches hold) is only the stride between prompts, so a launch of 77-key streams takes the kernels - and gives the bits - of an
+// engine built for one chunk.  (Except the one-launch forms: their kernels hold the 96-row stride.)
+struct CrossRoute {
+    enum Kind {
+        GENERIC,        // attn_kernel
+        CROSS77,        // head dim 64, every stream with 77 keys: cross77_kernel behind the plain to_q GEMM (debug bit 19 clear)
+        RUNS,           // that shape with DIFFERENT key counts: every run of streams on the kernel of its own count (cross_run)
+        XATTN_FUSED,    // RT_PROBES builds: to_q + attention as one launch (gemm16.hip, EPI_XATTN: the Q tile stays in LDS; debug bit 4 clear)
+        XBLOCK,         // RT_PROBES builds: to_q, attention AND to_out + residual as one launch (xblock.hip; debug bit 16 set)
+    } kind;
+    bool handover;      // the launch may leave the recorded stream's statistics (cross77_kernel only; debug bit 17 clear)
+};
+// d: the head dim (a caller that only knows the padded DP passes that: every kernel but attn_kernel needs DP = 64).  The two-launch forms
+// stay with a LayerNorm folded into to_q, a recorded token map (the store reads Q from HBM) and an entry that is handed Q (with_to_q = false).
+static CrossRoute cross_route(int C, int heads, int d, int DP, int tokens, int prompt_rows, const int* nkeys, int B, bool folded, bool recorded,
+                              bool with_to_q = true) {
+    const bool all77 = std::all_of(nkeys, nkeys + B, [](int c) { return c == 77; });
+    const bool c77ok = gemm_cross77_enabled() && cross77_supported(heads, DP, tokens, prompt_rows, 77) && d == 64;
+    const bool one_launch = with_to_q && all77 && prompt_rows == 96 && !folded && !recorded;
+    CrossRoute r{CrossRoute::GENERIC, false};
+    if (one_launch && gemm_xblock_enabled() && xblock_supported(C, heads, DP, tokens) && d == 64) r.kind = CrossRoute::XBLOCK;
+    else if (one_launch && !c77ok && gemm_xattn_enabled() && xattn_fused_supported(C, heads, DP, tokens)) r.kind = CrossRoute::XATTN_FUSED;
+    else if (c77ok) r.kind = all77 ? CrossRoute::CROSS77 : CrossRoute::RUNS;
+    r.handover = recorded && r.kind == CrossRoute::CROSS77 && !g_store_own_stats;
+    return r;
+}
+// RUNS (prompts of one to three 77-token windows in one launch): the kernel of a stream is a function of its OWN key count - maximal runs
+// of 77-key streams go to cross77_kernel (*kernel = 1), the runs of longer ones to crossmw_kernel (2; cross77.hip: all 154 / 231 keys of the
+// head in LDS; 0 = attn_kernel) - so a one-window stream computes the bits it computes alone, whatever its neighbours are.  Returns the run's end.
+static int cross_run(const int* nkeys, int B, int b0, int heads, int DP, int tokens, int prompt_rows, int* kernel) {
+    const bool one = nkeys[b0] == 77;
+    *kernel = one ? 1 : crossmw_supported(heads, DP, tokens, prompt_rows) ? 2 : 0;
+    while (b0 < B && (nkeys[b0] == 77) == one) ++b0;
+    return b0;
+}
+// The attention launch of the two-launch routes.  A run is the same launch on offset Q / O pointers; no statistics hand-over on RUNS.
+static void launch_cross(const AttnArgs& a, const CrossRoute& route, hipStream_t st) {
+    if (route.kind == CrossRoute::CROSS77) return launch_cross77(a, st);
+    if (route.kind == CrossRoute::GENERIC) return launch_attention(a, st);
+    RT_REQUIRE(route.kind == CrossRoute::RUNS, "launch_cross: the one-launch forms include to_q and are launched by their callers");
+    for (int b0 = 0, b1, kernel; b0 < a.B; b0 = b1) {
+        b1 = cross_run(a.nkeys, a.B, b0, a.H, a.DP, a.N, a.NK, &kernel);
         AttnArgs r = a;
         r.B = b1 - b0; r.stats = nullptr;
         r.Q = a.Q + (size_t)b0 * a.N * a.ldq; r.O = a.O + (size_t)b0 * a.N * a.ldo;
@@ -185,9 +213,107 @@ static void launch_cross_runs(const AttnArgs& a, hipStream_t st) {
             const int b = b0 + i < a.B ? b0 + i : b0;
             r.q_src[i] = i; r.k_src[i] = a.k_src[b]; r.v_src[i] = a.v_src[b]; r.wset[i] = a.wset[b]; r.nkeys[i] = i < r.B ? a.nkeys[b] : 0;
         }
-        if (one) launch_cross77(r, st); else if (crossmw_supported(r.H, r.DP, r.N, r.NK)) launch_crossmw(r, st); else launch_attention(r, st);
-        b0 = b1;
+        if (kernel == 1) launch_cross77(r, st); else if (kernel == 2) launch_crossmw(r, st); else launch_attention(r, st);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launch arguments of the UNet's kernels, built HERE for rt_engine and for the stateless rt_op_* entries alike (as vae.h does for rt_vae), so
+// that an entry launches what the forward launches.  zero: the caller's zero page.  hw: the tokens ONE stream contributes (0: not known): the
+// split-K rule and the tile classes are keyed on it, so that results are batch invariant.  (temb_ld is only read with temb set.)
+static GemmArgs unet_dense_args(const bf16_t* zero, int hw, const bf16_t* A, int lda, const MatW& W, int M, void* out, int ldo, int epi,
+                                const void* res = nullptr, int ldres = 0, const float* temb = nullptr, int rows_per_batch = 0) {
+    GemmArgs g{}; g.A = A; g.W = W.w; g.bias = W.b; g.out = out; g.res = res; g.temb = temb; g.zero = zero;
+    g.mode = A_DENSE; g.epi = epi; g.M = M; g.N = W.N; g.K = W.K; g.lda = lda; g.ldw = W.K; g.ldo = ldo; g.ldres = ldres; g.temb_ld = W.N;
+    g.rows_per_batch = rows_per_batch;
+    if (hw > 0) { g.split_tiles = cdiv(hw, 128) * cdiv(W.N, 128); g.rows_per_stream = hw; }
+    return g;
+}
+// V^T = Wv [HD, K] x X[M, K]^T -> [HD, M]
+static GemmArgs unet_vt_args(const bf16_t* zero, int hw, const MatW& Wv, const bf16_t* X, int ldx, int M, bf16_t* out, int ldo) {
+    GemmArgs g{}; g.A = Wv.w; g.W = X; g.bias = Wv.b; g.out = out; g.zero = zero;
+    g.mode = A_DENSE; g.epi = EPI_BF16; g.M = Wv.N; g.N = M; g.K = Wv.K; g.lda = Wv.K; g.ldw = ldx; g.ldo = ldo; g.weights_on_rows = 1;
+    if (hw > 0) { g.split_tiles = cdiv(Wv.N, 128) * cdiv(hw, 128); g.rows_per_stream = hw; }
+    return g;
+}
+// 3x3 convolution (A_CONV3 / A_CONV3_S2: k3 s2 p1 / A_CONV3_UP2) of B maps [Hin, Win, CinP] to W.N channels
+static GemmArgs unet_conv3_args(const bf16_t* zero, const bf16_t* in, int mode, const MatW& W, int B, int Hin, int Win, int CinP, void* out, int epi,
+                                const void* res = nullptr, const float* temb = nullptr) {
+    const int Hout = mode == A_CONV3_S2 ? (Hin + 1) / 2 : mode == A_CONV3_UP2 ? Hin * 2 : Hin;
+    const int Wout = mode == A_CONV3_S2 ? (Win + 1) / 2 : mode == A_CONV3_UP2 ? Win * 2 : Win;
+    GemmArgs g{}; g.A = in; g.W = W.w; g.W_up2 = mode == A_CONV3_UP2 ? W.w_up2 : nullptr; g.bias = W.b; g.out = out; g.res = res; g.temb = temb; g.zero = zero;
+    g.mode = mode; g.epi = epi; g.M = B * Hout * Wout; g.N = W.N; g.K = W.K; g.lda = 0; g.ldw = W.K; g.ldo = W.N; g.ldres = W.N; g.temb_ld = W.N;
+    g.rows_per_batch = Hout * Wout; g.Hin = Hin; g.Win = Win; g.Cin = CinP; g.Hout = Hout; g.Wout = Wout; g.split_tiles = cdiv(Hout * Wout, 128) * cdiv(W.N, 128);
+    return g;
+}
+// LayerNorm fold of a launch (gemm16.hip, "LNF"): `part` set = consumer (A / X is xb, the un-normalised trunk as bf16; W the folded
+// copy, `s` its (row sum, c) pairs); `emit` set = producer: leaves xb in `copy` and the partials of its output rows in `emit`
+struct LnFold { const float* part = nullptr; int npair = 0; int ld = 0; const float* s = nullptr; float* emit = nullptr; bf16_t* copy = nullptr; };
+static void ln_apply(GemmArgs& g, const LnFold* ln, int C) {
+    if (!ln) return;
+    g.ln_part = ln->part; g.ln_npair = ln->npair; g.ln_ld = ln->ld; g.ln_s = ln->s; g.ln_emit = ln->emit; g.ln_copy = ln->copy;
+    g.ln_inv_c = 1.f / (float)C; g.ln_eps = 1e-5f;
+}
+// GroupNorm of the UNet: its chunk rule, the per-chunk partials [B, nchunk, G, 2] reduced by the apply kernel's own blocks
+static GroupNormArgs unet_gn_args(const void* x1, const void* x2, int in_type /* 0 fp32, 1 bf16, 2 fp16 */, int C1, int C2, int G, int B, int HW,
+                                  const float* gamma, const float* beta, float eps, int silu, bf16_t* out, bf16_t* raw, float* partial) {
+    GroupNormArgs a{}; a.x1 = x1; a.x2 = x2; a.in_bf16 = in_type; a.C1 = C1; a.C2 = C2; a.G = G; a.B = B; a.HW = HW;
+    a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu; a.out = out; a.raw_out = raw; a.partial = partial;
+    a.nchunk = groupnorm_nchunk(HW); a.rows_per_chunk = groupnorm_rows_per_chunk(HW); a.fuse_finalize = 1;
+    return a;
+}
+// Attention: Q, K, V^T and O of a launch as AttnArgs lays them out
+struct AttnIO { const bf16_t* Q; int ldq; const bf16_t* K; int ldk; const bf16_t* VT; int ldvt; bf16_t* O; int ldo; };
+static AttnArgs attn_io_args(const AttnIO& io, int B, int H, int N, int NK, int nk_valid, int DP, int cross, float* stats, int stats_b) {
+    AttnArgs a{}; a.Q = io.Q; a.ldq = io.ldq; a.K = io.K; a.ldk = io.ldk; a.VT = io.VT; a.ldvt = io.ldvt; a.O = io.O; a.ldo = io.ldo;
+    a.B = B; a.H = H; a.N = N; a.NK = NK; a.nk_valid = nk_valid; a.DP = DP; a.cross = cross;
+    if (stats) { a.stats = stats; a.stats_b = stats_b; }
+    return a;
+}
+// attn1: stream b attends with Q / K of stream qk_src[b] and its own V.  stats non-null: the launch leaves the softmax statistics of
+// stream stats_b there (store_handover_self).  (wabs / wsgn stay null: attn_kernel reads them for cross launches only.)
+static AttnArgs unet_self_attn_args(const AttnIO& io, const int* qk_src, int B, int H, int N, int DP, float* stats, int stats_b) {
+    AttnArgs a = attn_io_args(io, B, H, N, N, N, DP, 0, stats, stats_b);
+    for (int b = 0; b < B; ++b) { a.q_src[b] = a.k_src[b] = qk_src[b]; a.v_src[b] = b; a.wset[b] = 0; }
+    return a;
+}
+// attn2 behind the to_q GEMM: stream b reads K / V^T of prompt[b] (prompt_rows cached rows each, nkeys[b] = 77 c of them valid) with multiplier
+// set wset[b] (-1: plain softmax, no tables).  (cross77_kernel masks by nk_valid and does not read nkeys, attn_kernel takes 0 as nk_valid.)
+static AttnArgs unet_cross_attn_args(const AttnIO& io, const int* prompt, const int* wset, const int* nkeys, const float* wabs, const float* wsgn, int B,
+                                     int H, int N, int prompt_rows, int DP, float* stats = nullptr /* CrossRoute.handover */, int stats_b = 0) {
+    AttnArgs a = attn_io_args(io, B, H, N, prompt_rows, 77, DP, 1, stats, stats_b);
+    a.wabs = wabs; a.wsgn = wsgn;
+    for (int b = 0; b < B; ++b) { a.q_src[b] = b; a.k_src[b] = a.v_src[b] = prompt[b]; a.wset[b] = wset[b]; a.nkeys[b] = nkeys[b]; }
+    return a;
+}
+// The token-map store of stream `stream` behind the launch `a`: its Q rows against its own K rows (attn1: [N, N]; NKpad is the caller's - the
+// forward passes N, which launch_attn_store refuses unless N % 32 == 0, rt_op_attention_store_handover N padded to the store's 32-key step)
+// or against the recorded prompt's own keys (attn2: [N, 77 c] out of its 96 c cached rows).  a.stats set: the launch left the statistics, the
+// store runs its apply kernel only; attn1 passes its scratch either way.
+static AttnStoreArgs unet_store_args(const AttnArgs& a, int stream, float* out, bool overwrite, float* self_scratch = nullptr, int self_NKpad = 0) {
+    const int rows = a.cross ? 96 * (a.nkeys[stream] / 77) : a.N;
+    AttnStoreArgs sa{}; sa.Q = a.Q; sa.ldq = a.ldq; sa.q_row0 = (long)stream * a.N; sa.K = a.K; sa.ldk = a.ldk;
+    sa.k_row0 = a.cross ? (long)a.k_src[stream] * a.NK : (long)stream * a.N;
+    sa.out = out; sa.H = a.H; sa.N = a.N; sa.NK = a.cross ? a.nkeys[stream] : a.N; sa.NKpad = a.cross ? rows : self_NKpad; sa.NKrows = rows; sa.DP = a.DP;
+    sa.overwrite = overwrite; sa.stats = a.cross ? a.stats : self_scratch; sa.stats_ready = a.stats ? 1 : 0;
+    return sa;
+}
+// The one-launch forms of attn2 (head dim 64, 77 of 96 cached keys; CrossRoute::XBLOCK / XATTN_FUSED): x = the LayerNorm'd tokens
+static XBlockArgs unet_xblock_args(const bf16_t* x, const bf16_t* wq, const bf16_t* wo, const float* bo, const bf16_t* kc, const bf16_t* vt, int ldvt,
+                                   const f16_t* res, f16_t* out, const float* wabs, const float* wsgn, const int* prompt, const int* wset, int B,
+                                   int tokens, int C, int H) {
+    XBlockArgs xa{}; xa.x = x; xa.wq = wq; xa.wo = wo; xa.bo = bo; xa.kc = kc; xa.vt = vt; xa.res = res; xa.out = out; xa.wabs = wabs; xa.wsgn = wsgn;
+    xa.ldk = H * 64; xa.ldvt = ldvt; xa.ldres = C; xa.ldo = C; xa.M = B * tokens; xa.tokens = tokens; xa.nk_valid = 77; xa.C = C; xa.H = H;
+    for (int b = 0; b < B; ++b) { xa.prompt[b] = prompt[b]; xa.wset[b] = wset[b]; }
+    return xa;
+}
+static GemmArgs unet_xattn_args(const bf16_t* zero, const bf16_t* x, const bf16_t* wq, bf16_t* o, const bf16_t* kc, const bf16_t* vt, int ldvt,
+                                const float* wabs, const float* wsgn, const int* prompt, const int* wset, int B, int tokens, int C, int H) {
+    GemmArgs g{}; g.A = x; g.W = wq; g.out = o; g.zero = zero; g.mode = A_DENSE; g.epi = EPI_XATTN;
+    g.M = B * tokens; g.N = H * 64; g.K = C; g.lda = C; g.ldw = C; g.ldo = H * 64; g.rows_per_stream = tokens;
+    g.xa_k = kc; g.xa_vt = vt; g.xa_ldk = H * 64; g.xa_ldvt = ldvt; g.xa_tokens = tokens; g.xa_nk_valid = 77; g.xa_wabs = wabs; g.xa_wsgn = wsgn;
+    for (int b = 0; b < B; ++b) { g.xa_prompt[b] = prompt[b]; g.xa_wset[b] = wset[b]; }
+    return g;
 }
 
 // multistep state of the running schedule
@@ -504,45 +630,24 @@ struct rt_engine {
         g.splitk_ws = splitk_buf; g.splitk_ws_floats = splitk_floats;
         return true;
     }
-    // LayerNorm fold of a launch (gemm16.hip, "LNF"): `part` set = consumer (A / X is xb, the un-normalised trunk as bf16; W the folded
-    // copy, `s` its (row sum, c) pairs); `emit` set = producer: leaves xb in `copy` and the partials of its output rows in `emit`
-    struct LnFold { const float* part = nullptr; int npair = 0; int ld = 0; const float* s = nullptr; float* emit = nullptr; bf16_t* copy = nullptr; };
-    void ln_apply(GemmArgs& g, const LnFold* ln, int C) const {
-        if (!ln) return;
-        g.ln_part = ln->part; g.ln_npair = ln->npair; g.ln_ld = ln->ld; g.ln_s = ln->s; g.ln_emit = ln->emit; g.ln_copy = ln->copy;
-        g.ln_inv_c = 1.f / (float)C; g.ln_eps = 1e-5f;
+    GemmArgs dense_args(const bf16_t* A, int lda, const MatW& W, int M, void* out, int ldo, int epi, const void* res = nullptr, int ldres = 0) const {
+        return unet_dense_args(zero, cur_hw, A, lda, W, M, out, ldo, epi, res, ldres);
     }
-    GemmArgs dense_args(const bf16_t* A, int lda, const MatW& W, int M, void* out, int ldo, int epi, const void* res = nullptr,
-                        int ldres = 0, const float* temb = nullptr, int rows_per_batch = 0) const {
-        GemmArgs g{}; g.A = A; g.W = W.w; g.bias = W.b; g.out = out; g.res = res; g.temb = temb; g.zero = zero;
-        g.mode = A_DENSE; g.epi = epi; g.M = M; g.N = W.N; g.K = W.K; g.lda = lda; g.ldw = W.K; g.ldo = ldo;
-        g.ldres = ldres; g.temb_ld = W.N; g.rows_per_batch = rows_per_batch;
-        if (cur_hw > 0) { g.split_tiles = cdiv(cur_hw, 128) * cdiv(W.N, 128); g.rows_per_stream = cur_hw; }
-        return g;
-    }
-    GemmArgs vt_args(const MatW& Wv, const bf16_t* X, int ldx, int M, bf16_t* out, int ldo) const {
-        GemmArgs g{}; g.A = Wv.w; g.W = X; g.bias = Wv.b; g.out = out; g.zero = zero;
-        g.mode = A_DENSE; g.epi = EPI_BF16; g.M = Wv.N; g.N = M; g.K = Wv.K; g.lda = Wv.K; g.ldw = ldx; g.ldo = ldo;
-        g.weights_on_rows = 1;
-        if (cur_hw > 0) { g.split_tiles = cdiv(Wv.N, 128) * cdiv(cur_hw, 128); g.rows_per_stream = cur_hw; }
-        return g;
-    }
-    void gemm(const bf16_t* A, int lda, const MatW& W, int M, void* out, int ldo, int epi, const void* res = nullptr,
-              int ldres = 0, const float* temb = nullptr, int rows_per_batch = 0, const LnFold* ln = nullptr) {
-        GemmArgs g = dense_args(A, lda, W, M, out, ldo, epi, res, ldres, temb, rows_per_batch);
-        ln_apply(g, ln, ln && ln->part ? W.K : W.N);
+    GemmArgs vt_args(const MatW& Wv, const bf16_t* X, int ldx, int M, bf16_t* out, int ldo) const { return unet_vt_args(zero, cur_hw, Wv, X, ldx, M, out, ldo); }
+    void run(GemmArgs& g, int prof_class, double flops) {      // one launch_gemm, with the engine's split-K scratch and its profiling record
         if (!run_gemm(g)) return;
-        prof_begin(RT_PROF_GEMM_DENSE, 2.0 * M * W.N * W.K);
+        prof_begin(prof_class, flops);
         launch_gemm(g, stream);
         prof_end();
     }
-    // V^T = Wv [HD, K] x X[M, K]^T -> [HD, M]
+    void gemm(const bf16_t* A, int lda, const MatW& W, int M, void* out, int ldo, int epi, const void* res = nullptr, int ldres = 0, const LnFold* ln = nullptr) {
+        GemmArgs g = dense_args(A, lda, W, M, out, ldo, epi, res, ldres);
+        ln_apply(g, ln, ln && ln->part ? W.K : W.N);
+        run(g, RT_PROF_GEMM_DENSE, 2.0 * M * W.N * W.K);
+    }
     void gemm_vt(const MatW& Wv, const bf16_t* X, int ldx, int M, bf16_t* out, int ldo) {
         GemmArgs g = vt_args(Wv, X, ldx, M, out, ldo);
-        if (!run_gemm(g)) return;
-        prof_begin(RT_PROF_GEMM_DENSE, 2.0 * M * Wv.N * Wv.K);
-        launch_gemm(g, stream);
-        prof_end();
+        run(g, RT_PROF_GEMM_DENSE, 2.0 * M * Wv.N * Wv.K);
     }
     // attn1: the stacked Q|K projection of the first Mqk rows and V^T of all M rows read the same LayerNorm output: ONE grouped launch
     // where gemm16.hip has the pair of tiles (launch_gemm_pair), otherwise one launch each - the same tile bodies either way
@@ -559,34 +664,18 @@ struct rt_engine {
     }
     void conv3(const bf16_t* in, int mode, const MatW& W, int B, int Hin, int Win, int CinP, void* out, int epi,
                const void* res = nullptr, const float* temb = nullptr) {
-        int Hout = Hin, Wout = Win;
-        if (mode == A_CONV3_S2) { Hout = (Hin + 1) / 2; Wout = (Win + 1) / 2; }   // k3 s2 p1
-        if (mode == A_CONV3_UP2) { Hout = Hin * 2; Wout = Win * 2; }
-        GemmArgs g{}; g.A = in; g.W = W.w; g.bias = W.b; g.out = out; g.res = res; g.temb = temb; g.zero = zero;
-        if (mode == A_CONV3_UP2) g.W_up2 = W.w_up2;
-        g.mode = mode; g.epi = epi; g.M = B * Hout * Wout; g.N = W.N; g.K = W.K; g.lda = 0; g.ldw = W.K; g.ldo = W.N;
-        g.ldres = W.N; g.temb_ld = W.N; g.rows_per_batch = Hout * Wout;
-        g.Hin = Hin; g.Win = Win; g.Cin = CinP; g.Hout = Hout; g.Wout = Wout;
-        g.split_tiles = cdiv(Hout * Wout, 128) * cdiv(W.N, 128);
+        GemmArgs g = unet_conv3_args(zero, in, mode, W, B, Hin, Win, CinP, out, epi, res, temb);
         RT_REQUIRE(W.K == 9 * CinP, "conv: weight/input channel mismatch");
-        if (!run_gemm(g)) return;
         // executed FLOPs: the phase form of an up-sampler convolution multiplies 4 taps per output pixel, not 9
-        const bool phase = profiling && gemm_route(g).kind == GemmRoute::G16_UP2;
-        prof_begin(RT_PROF_GEMM_CONV, 2.0 * g.M * W.N * (phase ? 4 * CinP : W.K));
-        launch_gemm(g, stream);
-        prof_end();
+        const bool phase = profiling && !dry() && gemm_route(g).kind == GemmRoute::G16_UP2;
+        run(g, RT_PROF_GEMM_CONV, 2.0 * g.M * W.N * (phase ? 4 * CinP : W.K));
     }
     void groupnorm(const void* x1, const void* x2, int in_type /* 0 fp32, 1 bf16, 2 fp16 */, int C1, int C2, int B, int HW, const NormW& n, float eps_,
                    bool silu, bf16_t* out, bf16_t* raw) {
         Scope sc(ws);
-        const int nchunk = groupnorm_nchunk(HW);
-        float* partial = ws.f32((size_t)B * nchunk * cfg.norm_groups * 2);
+        float* partial = ws.f32((size_t)B * groupnorm_nchunk(HW) * cfg.norm_groups * 2);
         if (dry()) return;
-        GroupNormArgs a{}; a.x1 = x1; a.x2 = x2; a.in_bf16 = in_type; a.C1 = C1; a.C2 = C2; a.G = cfg.norm_groups; a.B = B;
-        a.HW = HW; a.gamma = n.g; a.beta = n.b; a.eps = eps_; a.silu = silu; a.out = out; a.raw_out = raw;
-        a.partial = partial; a.nchunk = nchunk; a.rows_per_chunk = groupnorm_rows_per_chunk(HW);
-        a.fuse_finalize = 1;
-        launch_groupnorm(a, stream);
+        launch_groupnorm(unet_gn_args(x1, x2, in_type, C1, C2, cfg.norm_groups, B, HW, n.g, n.b, eps_, silu, out, raw, partial), stream);
     }
     void layernorm(const f16_t* x, const NormW& n, bf16_t* out, int rows) {
         if (dry()) return;
@@ -683,7 +772,7 @@ struct rt_engine {
                 Scope s2(ws);
                 bf16_t* g = ws.b16((size_t)M * C);
                 groupnorm(x.p, nullptr, 2, C, 0, B, HW, t.gn, 1e-6f, false, g, nullptr);
-                gemm(g, C, t.pin, M, hcur, C, EPI_F16, nullptr, 0, nullptr, 0, fold1 && emit_pin ? &em : nullptr);
+                gemm(g, C, t.pin, M, hcur, C, EPI_F16, nullptr, 0, fold1 && emit_pin ? &em : nullptr);
                 if (fold1) partials_after(emit_pin);
             }
             for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
@@ -707,122 +796,77 @@ struct rt_engine {
                     gemm_qk_vt(xb, C, k.qk1f, nqk * HW, qk, 2 * HD, k.v1f, M, vt, M, &lq, &lv);
                 } else gemm_qk_vt(n, C, k.qk1, nqk * HW, qk, 2 * HD, k.v1, M, vt, M);
                 if (!dry()) {
-                    AttnArgs a{}; a.Q = qk; a.ldq = 2 * HD; a.K = qk + HD; a.ldk = 2 * HD; a.VT = vt; a.ldvt = M; a.O = o; a.ldo = HD;
-                    for (int b = 0; b < B; ++b) { a.q_src[b] = in.qk_src[b]; a.k_src[b] = in.qk_src[b]; a.v_src[b] = b; a.wset[b] = 0; }
-                    a.B = B; a.H = t.heads; a.N = HW; a.NK = HW; a.nk_valid = HW; a.DP = t.DP; a.cross = 0;
                     // a layer whose map is recorded in this call: the attention launch leaves the softmax statistics of the recorded stream,
                     // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
                     const bool will_store = in.store_stream >= 0 && k.store_mode[0] && k.store_calls[0] + 1 > 10;      // n_maps[name] > 10 (rd.py:422, xl.py:988)
                     const bool stats_from_attn = will_store && store_handover_self(HW, t.DP, in.qk_src, in.store_stream);
-                    if (stats_from_attn) { a.stats = store_stats; a.stats_b = in.store_stream; }
+                    const AttnArgs a = unet_self_attn_args(AttnIO{qk, 2 * HD, qk + HD, 2 * HD, vt, M, o, HD}, in.qk_src, B, t.heads, HW, t.DP,
+                                                           stats_from_attn ? store_stats : nullptr, in.store_stream);
                     prof_begin(RT_PROF_ATTN_SELF, 4.0 * B * t.heads * (double)HW * HW * t.d);
                     launch_attention(a, stream);
                     prof_end();
                     if (in.store_stream >= 0 && k.store_mode[0] && ++k.store_calls[0] > 10) {
                         RT_REQUIRE((size_t)HW * HW <= k.store_cap[0], "attention store: map larger than the enabled buffer");
-                        AttnStoreArgs sa{}; sa.Q = qk; sa.ldq = 2 * HD; sa.q_row0 = (long)in.store_stream * HW;
-                        sa.K = qk + HD; sa.ldk = 2 * HD; sa.k_row0 = (long)in.store_stream * HW;
-                        sa.out = k.store[0]; sa.H = t.heads; sa.N = HW; sa.NK = HW; sa.NKpad = HW; sa.NKrows = HW; sa.DP = t.DP;
-                        sa.overwrite = k.store_mode[0] == 2; sa.stats = store_stats; sa.stats_ready = stats_from_attn ? 1 : 0;
                         prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * HW * t.d, 8.0 * HW * HW + 2.0 * 2.0 * HW * HD);
-                        launch_attn_store(sa, stream);
+                        launch_attn_store(unet_store_args(a, in.store_stream, k.store[0], k.store_mode[0] == 2, store_stats, HW), stream);
                         prof_end();
                         k.store_rows[0] = HW; k.store_cols[0] = HW;
                     }
                 }
-                gemm(o, HD, k.out1, M, hcur, C, EPI_F16, hcur, C, nullptr, 0, fold2 && emit_out ? &em : nullptr);
+                gemm(o, HD, k.out1, M, hcur, C, EPI_F16, hcur, C, fold2 && emit_out ? &em : nullptr);
                 if (fold2) partials_after(emit_out);
                 // --- attn2 (cross, K/V from the per-prompt cache; font-size softmax on flagged streams)
                 if (!fold2) layernorm(hcur, k.ln2, n, M);
-                // to_q and the 77-key attention as ONE launch (gemm16.hip, EPI_XATTN: the Q tile stays in LDS) wherever the tiling
-                // allows it - a pure function of the layer's shape; the token-map capture of the plain pass reads Q from HBM and
-                // keeps the two-launch form for the layers it records
+                // the route (cross_route): a layer with its map enabled counts as recorded whether or not this call is past the tenth
                 const bool capture2 = in.store_stream >= 0 && k.store_mode[1];
-                // key counts of the streams' prompts (77 per chunk).  Every route below is a function of THESE and of the layer's shape,
-                // never of the capacity (KP only enters as the stride between prompts): a launch whose streams all have 77 keys takes
-                // the kernels - and gives the bits - of an engine built for one chunk.  The one exception are the two probe-only forms
-                // below (fused2 / block2, RT_PROBES builds with their debug switches on): their kernels hold the 96-row stride in their
-                // code, so an engine with a wider one leaves them out and runs the default route instead.
-                const int KPr = KP();
-                int nkeys[RT_MAXB]; bool all77 = true;
-                for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; all77 = all77 && nkeys[b] == 77; }
-                // round 5: the 77-key attention on its own kernel (cross77_kernel, xblock.hip: 64 queries x 2 heads per workgroup, K / V^T in
-                // LDS) behind the plain to_q GEMM is faster than the fused launch of round 4 and serves the capturing layers too (Q is in HBM)
-                const bool c77ok = cross77_route(t.heads, t.DP, t.d, HW, KPr, true);
-                const bool c77 = cross77_route(t.heads, t.DP, t.d, HW, KPr, all77);
-                const bool fused2 = all77 && KPr == 96 && !c77 && !fold2 && gemm_xattn_enabled() && xattn_fused_supported(C, t.heads, t.DP, HW) && !capture2;
-                // the 640-channel level: to_q, attention AND to_out + residual as one launch with Q / P / O in registers (xblock.hip)
-                const bool block2 = all77 && KPr == 96 && !fold2 && gemm_xblock_enabled() && xblock_supported(C, t.heads, t.DP, HW) && t.d == 64 && !capture2;
-                if (block2) {
+                const int KPr = KP(), ldvt2 = cfg.max_prompts * KPr;
+                int nkeys[RT_MAXB], wset2[RT_MAXB];
+                for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; wset2[b] = in.fontsize[b] ? 1 : -1; }      // -1: plain softmax, no multiplier tables
+                const CrossRoute route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2);
+                if (route.kind == CrossRoute::XBLOCK) {
                     if (!dry()) {
-                        XBlockArgs xa{}; xa.x = n; xa.wq = k.q2.w; xa.wo = k.out2.w; xa.bo = k.out2.b; xa.kc = k.kcache; xa.vt = k.vtcache;
-                        xa.res = hcur; xa.out = hcur; xa.wabs = wabs; xa.wsgn = wsgn; xa.ldk = HD; xa.ldvt = cfg.max_prompts * 96; xa.ldres = C; xa.ldo = C;
-                        xa.M = M; xa.tokens = HW; xa.nk_valid = 77; xa.C = C; xa.H = t.heads;
-                        for (int b = 0; b < B; ++b) { xa.prompt[b] = in.prompt[b]; xa.wset[b] = in.fontsize[b] ? 1 : -1; }
                         RT_REQUIRE(k.q2.K == C && k.out2.K == HD && HD == C, "xblock: packed projection widths");
                         prof_begin(RT_PROF_XBLOCK, 4.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
-                        launch_xblock(xa, stream);
+                        launch_xblock(unet_xblock_args(n, k.q2.w, k.out2.w, k.out2.b, k.kcache, k.vtcache, ldvt2, hcur, hcur, wabs, wsgn, in.prompt, wset2, B, HW, C, t.heads), stream);
                         prof_end();
                     }
-                    if (fold3) partials_after(false);
-                } else {
-                if (fused2) {
+                } else if (route.kind == CrossRoute::XATTN_FUSED) {
                     if (!dry()) {
-                        GemmArgs g{}; g.A = n; g.W = k.q2.w; g.out = o; g.zero = zero; g.mode = A_DENSE; g.epi = EPI_XATTN;
-                        g.M = M; g.N = HD; g.K = C; g.lda = C; g.ldw = k.q2.K; g.ldo = HD; g.rows_per_stream = HW;
-                        g.xa_k = k.kcache; g.xa_vt = k.vtcache; g.xa_ldk = HD; g.xa_ldvt = cfg.max_prompts * 96; g.xa_tokens = HW; g.xa_nk_valid = 77;
-                        g.xa_wabs = wabs; g.xa_wsgn = wsgn;
-                        for (int b = 0; b < B; ++b) { g.xa_prompt[b] = in.prompt[b]; g.xa_wset[b] = in.fontsize[b] ? 1 : -1; }
                         prof_begin(RT_PROF_XATTN_FUSED, 2.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
-                        launch_xattn_fused(g, stream);
+                        launch_xattn_fused(unet_xattn_args(zero, n, k.q2.w, o, k.kcache, k.vtcache, ldvt2, wabs, wsgn, in.prompt, wset2, B, HW, C, t.heads), stream);
                         prof_end();
                     }
                 } else {
                 if (fold2) {
                     LnFold l2; l2.part = part; l2.npair = npair; l2.ld = M; l2.s = k.q2s;
-                    gemm(xb, C, k.q2f, M, qk, HD, EPI_BF16, nullptr, 0, nullptr, 0, &l2);
+                    gemm(xb, C, k.q2f, M, qk, HD, EPI_BF16, nullptr, 0, &l2);
                 } else gemm(n, C, k.q2, M, qk, HD, EPI_BF16);
                 if (!dry()) {
-                    AttnArgs a{}; a.Q = qk; a.ldq = HD; a.K = k.kcache; a.ldk = HD; a.VT = k.vtcache; a.ldvt = cfg.max_prompts * KPr;
-                    a.O = o; a.ldo = HD;
-                    for (int b = 0; b < B; ++b) a.nkeys[b] = nkeys[b];
-                    for (int b = 0; b < B; ++b) { a.q_src[b] = b; a.k_src[b] = in.prompt[b]; a.v_src[b] = in.prompt[b]; a.wset[b] = in.fontsize[b] ? 1 : -1; }      // -1: plain softmax, no multiplier tables
-                    a.wabs = wabs; a.wsgn = wsgn;
-                    a.B = B; a.H = t.heads; a.N = HW; a.NK = KPr; a.nk_valid = 77; a.DP = t.DP; a.cross = 1;
-                    // a recorded layer on cross77_kernel: the launch leaves the softmax statistics of the recorded stream (as the self-attention
-                    // launch does for attn1), the store runs its apply kernel only
-                    const bool stats2 = capture2 && k.store_calls[1] + 1 > 10 && store_handover_cross(c77);
-                    if (stats2) { a.stats = store_stats; a.stats_b = in.store_stream; }
+                    // (a recorded layer on cross77_kernel hands its statistics over as attn1 does, from the eleventh recorded call on)
+                    const AttnArgs a = unet_cross_attn_args(AttnIO{qk, HD, k.kcache, HD, k.vtcache, ldvt2, o, HD}, in.prompt, wset2, nkeys, wabs, wsgn, B, t.heads, HW,
+                                                            KPr, t.DP, route.handover && k.store_calls[1] + 1 > 10 ? store_stats : nullptr, in.store_stream);
                     double keysum = 0; for (int b = 0; b < B; ++b) keysum += nkeys[b];
                     prof_begin(RT_PROF_ATTN_CROSS, 4.0 * t.heads * (double)HW * keysum * t.d);
-                    if (c77) launch_cross77(a, stream);
-                    else if (c77ok) launch_cross_runs(a, stream);           // mixed key counts: every stream on the kernel of its own count
-                    else launch_attention(a, stream);
+                    launch_cross(a, route, stream);
                     prof_end();
-                    if (in.store_stream >= 0 && k.store_mode[1] && ++k.store_calls[1] > 10) {
-                        // the recorded prompt's own keys: [HW, 77 c] out of its 96 c cached rows
+                    if (capture2 && ++k.store_calls[1] > 10) {
                         const int snk = nkeys[in.store_stream], srows = 96 * (snk / 77);
                         RT_REQUIRE((size_t)HW * snk <= k.store_cap[1], "attention store: map larger than the enabled buffer");
-                        AttnStoreArgs sa{}; sa.Q = qk; sa.ldq = HD; sa.q_row0 = (long)in.store_stream * HW;
-                        sa.K = k.kcache; sa.ldk = HD; sa.k_row0 = (long)in.prompt[in.store_stream] * KPr;
-                        sa.out = k.store[1]; sa.H = t.heads; sa.N = HW; sa.NK = snk; sa.NKpad = srows; sa.NKrows = srows; sa.DP = t.DP;
-                        sa.overwrite = k.store_mode[1] == 2;
-                        if (stats2) { sa.stats = store_stats; sa.stats_ready = 1; }
                         prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * snk * t.d, 8.0 * HW * snk + 2.0 * (HW + (double)srows) * HD);
-                        launch_attn_store(sa, stream);
+                        launch_attn_store(unet_store_args(a, in.store_stream, k.store[1], k.store_mode[1] == 2), stream);
                         prof_end();
                         k.store_rows[1] = HW; k.store_cols[1] = snk;
                     }
                 }
                 }
-                gemm(o, HD, k.out2, M, hcur, C, EPI_F16, hcur, C, nullptr, 0, fold3 && emit_out ? &em : nullptr);
-                if (fold3) partials_after(emit_out);
-                }
+                const bool out2_done = route.kind == CrossRoute::XBLOCK;      // to_out + residual were part of that launch
+                if (!out2_done) gemm(o, HD, k.out2, M, hcur, C, EPI_F16, hcur, C, fold3 && emit_out ? &em : nullptr);
+                if (fold3) partials_after(!out2_done && emit_out);
                 // --- GEGLU feed-forward (attention.py:209-304)
                 bf16_t* gg = ws.b16((size_t)M * 4 * C);
                 if (fold3) {
                     LnFold l3; l3.part = part; l3.npair = npair; l3.ld = M; l3.s = k.ff1s;
-                    gemm(xb, C, k.ff1f, M, gg, 4 * C, EPI_GEGLU, nullptr, 0, nullptr, 0, &l3);
+                    gemm(xb, C, k.ff1f, M, gg, 4 * C, EPI_GEGLU, nullptr, 0, &l3);
                 } else {
                     layernorm(hcur, k.ln3, n, M);
                     gemm(n, C, k.ff1, M, gg, 4 * C, EPI_GEGLU);
@@ -830,7 +874,7 @@ struct rt_engine {
                 // the next block's norm1 reads what ff.net.2 leaves; behind the LAST block proj_out reads the trunk as bf16 - which is
                 // exactly the xb an emitting ff.net.2 writes (the cast launch below is then not needed)
                 const bool need1 = fold1 && !last, copy_last = last && fold1 && emit_ff2;
-                gemm(gg, 4 * C, k.ff2, M, hcur, C, EPI_F16, hcur, C, nullptr, 0, (need1 || copy_last) && emit_ff2 ? &em : nullptr);
+                gemm(gg, 4 * C, k.ff2, M, hcur, C, EPI_F16, hcur, C, (need1 || copy_last) && emit_ff2 ? &em : nullptr);
                 if (need1) partials_after(emit_ff2);
             }
             const bool have_xb = fold1 && emit_ff2 && !t.blocks.empty();
@@ -1474,6 +1518,9 @@ static bf16_t* op_zero_page() {       // one page per DEVICE (a thread that driv
     if (!z) { HIP_CHECK(hipMalloc((void**)&z, 256)); HIP_CHECK(hipMemset(z, 0, 256)); }
     return z;
 }
+// a caller's packed [N, K] weight (+ bias) as the plan's MatW, for the builders above (read only)
+static MatW op_mat(const void* w, const float* b, int N, int K) { MatW m; m.w = (bf16_t*)w; m.b = (float*)b; m.N = N; m.K = K; return m; }
+static bool op_key_count_ok(int c, int NK) { return c >= 77 && c % 77 == 0 && c / 77 * 96 <= NK; }
 // statistics scratch of rt_op_attention_probs_avg: one buffer per (device, stream), grown on demand (never under capture: null then,
 // which selects the one-pass kernel)
 static float* op_store_stats(size_t floats, hipStream_t st) {
@@ -1646,9 +1693,9 @@ int rt_op_pack_upconv(const void* w, int dtype, int Cout, int Cin, void* out_bf1
 int rt_op_upconv(const void* x, const void* w9, const void* w_phase, const float* bias, void* out_f16, int B, int Hin, int Win, int Cin, int N,
                  int* phase_route, void* stream) {
     OP_TRY({
-        GemmArgs g{}; g.A = (const bf16_t*)x; g.W = (const bf16_t*)w9; g.W_up2 = (const bf16_t*)w_phase; g.bias = bias; g.out = out_f16; g.zero = op_zero_page();
-        g.mode = A_CONV3_UP2; g.epi = EPI_F16; g.M = B * 4 * Hin * Win; g.N = N; g.K = 9 * Cin; g.ldw = g.K; g.ldo = N; g.ldres = N; g.temb_ld = N;
-        g.rows_per_batch = 4 * Hin * Win; g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.Hout = 2 * Hin; g.Wout = 2 * Win;
+        MatW W = op_mat(w9, bias, N, 9 * Cin); W.w_up2 = (bf16_t*)w_phase;
+        GemmArgs g = unet_conv3_args(op_zero_page(), (const bf16_t*)x, A_CONV3_UP2, W, B, Hin, Win, Cin, out_f16, EPI_F16);
+        g.split_tiles = 0;      // this entry has never passed one stream's tile count: the split rule sees the B images' actual tiles
         if (phase_route) *phase_route = gemm_route(g).kind == GemmRoute::G16_UP2 ? 1 : 0;
         launch_gemm(g, (hipStream_t)stream);
     })
@@ -1659,9 +1706,7 @@ int rt_op_ln_partials(const void* x_f16, void* xb_bf16, float* partials, int row
 int rt_op_gemm_emit_partials(const void* A, const void* W, const float* bias, void* out_f16, const void* res_f16, int M, int N, int K,
                              int rows_per_stream, void* xb_bf16, float* partials, int* tile_cols, void* stream) {
     OP_TRY({
-        GemmArgs g{}; g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.out = out_f16; g.res = res_f16; g.zero = op_zero_page();
-        g.mode = A_DENSE; g.epi = EPI_F16; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldo = N; g.ldres = N;
-        g.rows_per_stream = rows_per_stream; if (rows_per_stream > 0) g.split_tiles = cdiv(rows_per_stream, 128) * cdiv(N, 128);
+        GemmArgs g = unet_dense_args(op_zero_page(), rows_per_stream, (const bf16_t*)A, K, op_mat(W, bias, N, K), M, out_f16, N, EPI_F16, res_f16, N);
         const int bn = gemm_ln_emit_bn(g);
         if (!bn) throw rt_error(RT_E_UNSUPPORTED, "rt_op_gemm_emit_partials: this shape's route has no partial-emitting epilogue");
         if (tile_cols) *tile_cols = bn;
@@ -1676,12 +1721,11 @@ int rt_op_ln_gemm(const void* x_f16, const float* gamma, const float* beta, cons
         RT_REQUIRE((xb_bf16 != nullptr) == (partials != nullptr) && (xb_bf16 || x_f16), "rt_op_ln_gemm: a producer's (xb, partials) pair, or the fp16 trunk");
         RT_REQUIRE((tile_cols == 160 || tile_cols == 320) && C % (2 * tile_cols) == 0, "rt_op_ln_gemm: column tiles of 160 / 320, an even number per row");
         hipStream_t st = (hipStream_t)stream;
-        GemmArgs g{}; g.zero = op_zero_page(); g.mode = A_DENSE; g.epi = epi; g.K = C; g.out = out;
-        if (weights_on_rows) { g.M = N; g.N = tokens; g.lda = C; g.ldw = C; g.ldo = tokens; g.weights_on_rows = 1; }
-        else { g.M = tokens; g.N = N; g.lda = C; g.ldw = C; g.ldo = epi == EPI_GEGLU ? N / 2 : N; }
-        g.rows_per_stream = rows_per_stream;
-        if (rows_per_stream > 0) g.split_tiles = weights_on_rows ? cdiv(N, 128) * cdiv(rows_per_stream, 128) : cdiv(rows_per_stream, 128) * cdiv(N, 128);
-        g.ln_npair = C / tile_cols / 2; g.ln_ld = tokens; g.ln_inv_c = 1.f / (float)C; g.ln_eps = 1e-5f;
+        const MatW Wn = op_mat(nullptr, nullptr, N, C);
+        GemmArgs g = weights_on_rows ? unet_vt_args(op_zero_page(), rows_per_stream, Wn, nullptr, C, tokens, (bf16_t*)out, tokens)
+                                     : unet_dense_args(op_zero_page(), rows_per_stream, nullptr, C, Wn, tokens, out, epi == EPI_GEGLU ? N / 2 : N, epi);
+        LnFold ln; ln.npair = C / tile_cols / 2; ln.ld = tokens;
+        ln_apply(g, &ln, C);
         if (!gemm_ln_fold_ok(g)) throw rt_error(RT_E_UNSUPPORTED, "rt_op_ln_gemm: this shape's route has no folded instantiation");
         // scratch of the op (the engine keeps these in its own arenas): W', (s, c), xb, partials
         bf16_t* Wf = nullptr; float* sc = nullptr; float* part = nullptr; bf16_t* xb = nullptr;
@@ -1712,10 +1756,12 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
         a.O = (bf16_t*)O; a.ldo = ldo; a.wabs = wabs; a.wsgn = wsgn;
         for (int b = 0; b < B; ++b) { a.q_src[b] = q_src ? q_src[b] : b; a.k_src[b] = k_src ? k_src[b] : b; a.v_src[b] = v_src ? v_src[b] : b; a.wset[b] = wset ? wset[b] : 0; }
         a.B = B; a.H = H; a.N = N; a.NK = NK; a.nk_valid = nk_valid; a.DP = DP; a.cross = cross;
-        bool same_kv = true;
-        for (int b = 0; b < B; ++b) same_kv = same_kv && a.k_src[b] == a.v_src[b];
-        if (cross && same_kv && gemm_cross77_enabled() && cross77_supported(H, DP, N, NK, nk_valid)) launch_cross77(a, (hipStream_t)stream);     // the engine's kernel for these shapes
-        else launch_attention(a, (hipStream_t)stream);
+        // the engine's route where the launch is one of its 77-key ones (K and V of one prompt, at most the 80 keys cross77_kernel reads; this
+        // entry is handed Q and knows DP only), attn_kernel for everything else
+        bool as77 = cross && nk_valid >= 1 && nk_valid <= 80;
+        int k77[RT_MAXB];
+        for (int b = 0; b < B; ++b) { as77 = as77 && a.k_src[b] == a.v_src[b]; k77[b] = 77; }
+        launch_cross(a, as77 ? cross_route(H * DP, H, DP, DP, N, NK, k77, B, false, false, false) : CrossRoute{CrossRoute::GENERIC, false}, (hipStream_t)stream);
     })
 }
 int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo, const int* q_src,
@@ -1724,40 +1770,33 @@ int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const v
     OP_TRY({
         RT_REQUIRE(B >= 1 && B <= RT_MAXB && key_counts, "rt_op_attention_keys: batch / key counts");
         RT_REQUIRE(NK == 96 || NK == 192 || NK == 288, "rt_op_attention_keys: NK must be 96, 192 or 288 rows per prompt");
-        AttnArgs a{}; a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.VT = (const bf16_t*)VT; a.ldvt = ldvt;
-        a.O = (bf16_t*)O; a.ldo = ldo; a.wabs = wabs; a.wsgn = wsgn;
-        bool all77 = true;
+        int p[RT_MAXB], ws[RT_MAXB];
         for (int b = 0; b < B; ++b) {
-            RT_REQUIRE(key_counts[b] >= 77 && key_counts[b] % 77 == 0 && key_counts[b] / 77 * 96 <= NK, "rt_op_attention_keys: a key count must be 77 per 96-row chunk of NK");
-            a.q_src[b] = q_src ? q_src[b] : b; a.k_src[b] = a.v_src[b] = prompt ? prompt[b] : b; a.wset[b] = wset ? wset[b] : -1;
-            a.nkeys[b] = key_counts[b]; all77 = all77 && key_counts[b] == 77;
+            RT_REQUIRE(op_key_count_ok(key_counts[b], NK), "rt_op_attention_keys: a key count must be 77 per 96-row chunk of NK");
+            p[b] = prompt ? prompt[b] : b; ws[b] = wset ? wset[b] : -1;
         }
-        a.B = B; a.H = H; a.N = N; a.NK = NK; a.nk_valid = 77; a.DP = DP; a.cross = 1;
-        // the engine's route: a stream's kernel follows its own key count - cross77_kernel for the 77-key streams where the shape has it,
-        // the tile loop of attn_kernel for the longer ones (and for everything behind debug bit 19)
         RT_REQUIRE(!q_src, "rt_op_attention_keys: cross launches read Q of their own batch entry (q_src must be NULL)");
-        const bool c77ok = gemm_cross77_enabled() && cross77_supported(H, DP, N, NK, 77);
-        if (all77 && c77ok) launch_cross77(a, (hipStream_t)stream);
-        else if (c77ok) launch_cross_runs(a, (hipStream_t)stream);
-        else launch_attention(a, (hipStream_t)stream);
+        // the engine's launch and route (this entry is handed Q and knows DP only)
+        launch_cross(unet_cross_attn_args(AttnIO{(const bf16_t*)Q, ldq, (const bf16_t*)K, ldk, (const bf16_t*)VT, ldvt, (bf16_t*)O, ldo}, p, ws, key_counts, wabs, wsgn,
+                                          B, H, N, NK, DP),
+                     cross_route(H * DP, H, DP, DP, N, NK, key_counts, B, false, false, false), (hipStream_t)stream);
     })
 }
 // The arguments of a host-only shape query as the engine launches them: `streams` streams / images of rows_per_stream rows each
-// (3x3 convolution modes: a square map of rows_per_stream OUTPUT pixels, K_or_Cin input channels); N = the weight rows.  false: not a square map.
+// (3x3 convolution modes: a square map of rows_per_stream OUTPUT pixels - of even side for the 2x up-sampler - and K_or_Cin input channels,
+// else false); N = the weight rows.  No pointer is set: no routing rule reads a pointer's value.
 static bool query_args(GemmArgs& g, int mode, int epi, int streams, int rows_per_stream, int N, int K_or_Cin, int weights_on_rows) {
-    g = GemmArgs{};
-    g.mode = mode; g.epi = epi; g.M = streams * rows_per_stream; g.N = N; g.weights_on_rows = weights_on_rows;
+    const int M = streams * rows_per_stream;
     if (mode != A_DENSE) {
         int side = 1; while (side * side < rows_per_stream) ++side;
-        if (side * side != rows_per_stream) return false;
-        g.Cin = K_or_Cin; g.K = 9 * K_or_Cin; g.ldw = g.K;
-        g.Hout = g.Wout = side; g.Hin = g.Win = mode == A_CONV3_UP2 ? side / 2 : side; g.rows_per_batch = rows_per_stream;
-    } else {
-        g.K = K_or_Cin; g.lda = g.K; g.ldw = g.K; g.rows_per_stream = rows_per_stream;
-        if (weights_on_rows) { g.M = N; g.N = streams * rows_per_stream; }
-    }
-    g.ldo = g.N;
-    g.split_tiles = cdiv(rows_per_stream, 128) * cdiv(N, 128);                  // what the engine passes (engine.hip: conv3 / gemm)
+        if (side * side != rows_per_stream || (mode == A_CONV3_UP2 && side % 2)) return false;
+        const int in = mode == A_CONV3_UP2 ? side / 2 : side;
+        g = unet_conv3_args(nullptr, nullptr, mode, op_mat(nullptr, nullptr, N, 9 * K_or_Cin), streams, in, in, K_or_Cin, nullptr, epi);
+        g.weights_on_rows = weights_on_rows;
+    } else if (weights_on_rows) {
+        g = unet_vt_args(nullptr, rows_per_stream, op_mat(nullptr, nullptr, N, K_or_Cin), nullptr, K_or_Cin, M, nullptr, M);
+        g.epi = epi;
+    } else g = unet_dense_args(nullptr, rows_per_stream, nullptr, K_or_Cin, op_mat(nullptr, nullptr, N, K_or_Cin), M, nullptr, N, epi);
     return true;
 }
 // The route launch_gemm takes for problems that cannot fill the chip (gemm_route) as a host-only query (no device needed).
@@ -1788,8 +1827,8 @@ int rt_op_gemm16_pick(int conv3x3, int epi, int streams, int rows_per_stream, in
 int rt_op_gemm16_variant(const void* A, const void* W, const float* bias, void* out, const void* res, int epi, int M, int N, int K, int lda,
                          int ldw, int ldo, int ldres, int weights_on_rows, int variant, int wstat, void* stream) {
     OP_TRY({
-        GemmArgs g{}; g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = bias; g.out = out; g.res = res; g.zero = op_zero_page();
-        g.mode = A_DENSE; g.epi = epi; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.ldres = ldres; g.weights_on_rows = weights_on_rows;
+        GemmArgs g = unet_dense_args(op_zero_page(), 0, (const bf16_t*)A, lda, op_mat(W, bias, N, K), M, out, ldo, epi, res, ldres);
+        g.ldw = ldw; g.weights_on_rows = weights_on_rows;       // the caller's operands as they are (V^T form: A = the weight rows)
         if (variant < 0) { int ws = 0; variant = gemm16_pick(g, weights_on_rows, &ws); wstat = ws; RT_REQUIRE(variant >= 0, "rt_op_gemm16_variant: the family has no tile for this shape"); }
         launch_gemm16_variant(g, variant, wstat, (hipStream_t)stream);
     })
@@ -1810,14 +1849,8 @@ int rt_op_gemm_pair_pick(int streams_qk, int streams, int rows_per_stream, int N
 int rt_op_gemm_qk_vt(const void* X, int ldx, int K, int rows_per_stream, const void* Wqk, const float* bqk, int Mqk, int Nqk, void* qk, int ldqk,
                      const void* Wv, int Nv, int M, void* vt, int ldvt, int* grouped, void* stream) {
     OP_TRY({
-        GemmArgs a{}; a.A = (const bf16_t*)X; a.W = (const bf16_t*)Wqk; a.bias = bqk; a.out = qk; a.zero = op_zero_page();
-        a.mode = A_DENSE; a.epi = EPI_BF16; a.M = Mqk; a.N = Nqk; a.K = K; a.lda = ldx; a.ldw = K; a.ldo = ldqk; a.temb_ld = Nqk;
-        GemmArgs b{}; b.A = (const bf16_t*)Wv; b.W = (const bf16_t*)X; b.out = vt; b.zero = a.zero;
-        b.mode = A_DENSE; b.epi = EPI_BF16; b.M = Nv; b.N = M; b.K = K; b.lda = K; b.ldw = ldx; b.ldo = ldvt; b.weights_on_rows = 1;
-        if (rows_per_stream > 0) {
-            a.rows_per_stream = b.rows_per_stream = rows_per_stream;
-            a.split_tiles = cdiv(rows_per_stream, 128) * cdiv(Nqk, 128); b.split_tiles = cdiv(Nv, 128) * cdiv(rows_per_stream, 128);
-        }
+        const GemmArgs a = unet_dense_args(op_zero_page(), rows_per_stream, (const bf16_t*)X, ldx, op_mat(Wqk, bqk, Nqk, K), Mqk, qk, ldqk, EPI_BF16);
+        const GemmArgs b = unet_vt_args(a.zero, rows_per_stream, op_mat(Wv, nullptr, Nv, K), (const bf16_t*)X, ldx, M, (bf16_t*)vt, ldvt);     // (no V bias in this entry)
         if (grouped) *grouped = gemm_pair_grouped(a, b) >= 0 ? 1 : 0;
         launch_gemm_pair(a, b, (hipStream_t)stream);
     })
@@ -1834,50 +1867,31 @@ int rt_op_cross_attn_block(const void* x, const void* wq, const void* wo, const 
         RT_REQUIRE(B >= 1 && B <= RT_MAXB && N > 0 && C % 8 == 0 && H > 0 && DP % 32 == 0, "rt_op_cross_attn_block: shape");
         hipStream_t st = (hipStream_t)stream;
         const int M = B * N, HD = H * DP;
-        if (gemm_xblock_enabled() && xblock_supported(C, H, DP, N)) {
-            // the engine's path for the 640-channel level: the whole block in one launch (neither scratch buffer is written)
-            XBlockArgs xa{}; xa.x = (const bf16_t*)x; xa.wq = (const bf16_t*)wq; xa.wo = (const bf16_t*)wo; xa.bo = bo; xa.kc = (const bf16_t*)kcache;
-            xa.vt = (const bf16_t*)vtcache; xa.res = (const f16_t*)trunk_in; xa.out = (f16_t*)trunk_out; xa.wabs = wabs; xa.wsgn = wsgn;
-            xa.ldk = HD; xa.ldvt = ldvt; xa.ldres = C; xa.ldo = C; xa.M = M; xa.tokens = N; xa.nk_valid = 77; xa.C = C; xa.H = H;
-            for (int b = 0; b < B; ++b) { xa.prompt[b] = prompt_host ? prompt_host[b] : 0; xa.wset[b] = wset_host ? wset_host[b] : 0; }
-            launch_xblock(xa, st);
-            return RT_OK;
-        }
-        const bool c77 = gemm_cross77_enabled() && cross77_supported(H, DP, N, 96, 77);
-        if (!c77 && gemm_xattn_enabled() && xattn_fused_supported(C, H, DP, N)) {
-            // round 4's path for these shapes: to_q + attention in one launch (Q stays in LDS; q_scratch is not written)
-            GemmArgs g{}; g.A = (const bf16_t*)x; g.W = (const bf16_t*)wq; g.out = o_scratch; g.zero = op_zero_page(); g.mode = A_DENSE; g.epi = EPI_XATTN;
-            g.M = M; g.N = HD; g.K = C; g.lda = C; g.ldw = C; g.ldo = HD; g.rows_per_stream = N;
-            g.xa_k = (const bf16_t*)kcache; g.xa_vt = (const bf16_t*)vtcache; g.xa_ldk = HD; g.xa_ldvt = ldvt; g.xa_tokens = N; g.xa_nk_valid = 77;
-            g.xa_wabs = wabs; g.xa_wsgn = wsgn;
-            for (int b = 0; b < B; ++b) { g.xa_prompt[b] = prompt_host ? prompt_host[b] : 0; g.xa_wset[b] = wset_host ? wset_host[b] : 0; }
-            launch_xattn_fused(g, st);
+        const bf16_t* zero = op_zero_page();
+        int prompt[RT_MAXB], wset[RT_MAXB], k77[RT_MAXB];
+        for (int b = 0; b < B; ++b) { prompt[b] = prompt_host ? prompt_host[b] : 0; wset[b] = wset_host ? wset_host[b] : 0; k77[b] = 77; }
+        // the engine's route for a layer of this shape with 77-key prompts in a 96-row cache, LayerNorm not folded, map not recorded
+        const CrossRoute route = cross_route(C, H, DP, DP, N, 96, k77, B, false, false);
+        if (route.kind == CrossRoute::XBLOCK) {                // the whole block in one launch (neither scratch buffer is written)
+            launch_xblock(unet_xblock_args((const bf16_t*)x, (const bf16_t*)wq, (const bf16_t*)wo, bo, (const bf16_t*)kcache, (const bf16_t*)vtcache, ldvt,
+                                           (const f16_t*)trunk_in, (f16_t*)trunk_out, wabs, wsgn, prompt, wset, B, N, C, H), st);
+        } else if (route.kind == CrossRoute::XATTN_FUSED) {    // to_q + attention in one launch (Q stays in LDS; q_scratch is not written)
+            launch_xattn_fused(unet_xattn_args(zero, (const bf16_t*)x, (const bf16_t*)wq, (bf16_t*)o_scratch, (const bf16_t*)kcache, (const bf16_t*)vtcache, ldvt,
+                                               wabs, wsgn, prompt, wset, B, N, C, H), st);
         } else {
-        GemmArgs g{}; g.A = (const bf16_t*)x; g.W = (const bf16_t*)wq; g.out = q_scratch; g.zero = op_zero_page(); g.mode = A_DENSE; g.epi = EPI_BF16;
-        g.M = M; g.N = HD; g.K = C; g.lda = C; g.ldw = C; g.ldo = HD; g.rows_per_stream = N; g.split_tiles = cdiv(N, 128) * cdiv(HD, 128);
-        launch_gemm(g, st);
-        AttnArgs a{}; a.Q = (const bf16_t*)q_scratch; a.ldq = HD; a.K = (const bf16_t*)kcache; a.ldk = HD; a.VT = (const bf16_t*)vtcache; a.ldvt = ldvt;
-        a.O = (bf16_t*)o_scratch; a.ldo = HD; a.wabs = wabs; a.wsgn = wsgn;
-        for (int b = 0; b < B; ++b) { a.q_src[b] = b; a.k_src[b] = prompt_host ? prompt_host[b] : 0; a.v_src[b] = a.k_src[b]; a.wset[b] = wset_host ? wset_host[b] : 0; }
-        a.B = B; a.H = H; a.N = N; a.NK = 96; a.nk_valid = 77; a.DP = DP; a.cross = 1;
-        if (c77) launch_cross77(a, st); else launch_attention(a, st);
+            launch_gemm(unet_dense_args(zero, N, (const bf16_t*)x, C, op_mat(wq, nullptr, HD, C), M, q_scratch, HD, EPI_BF16), st);
+            launch_cross(unet_cross_attn_args(AttnIO{(const bf16_t*)q_scratch, HD, (const bf16_t*)kcache, HD, (const bf16_t*)vtcache, ldvt, (bf16_t*)o_scratch, HD},
+                                              prompt, wset, k77, wabs, wsgn, B, H, N, 96, DP), route, st);
         }
-        GemmArgs o{}; o.A = (const bf16_t*)o_scratch; o.W = (const bf16_t*)wo; o.bias = bo; o.out = trunk_out; o.res = trunk_in; o.zero = op_zero_page();
-        o.mode = A_DENSE; o.epi = EPI_F16; o.M = M; o.N = C; o.K = HD; o.lda = HD; o.ldw = HD; o.ldo = C; o.ldres = C; o.rows_per_stream = N;
-        o.split_tiles = cdiv(N, 128) * cdiv(C, 128);
-        launch_gemm(o, st);
+        if (route.kind != CrossRoute::XBLOCK) launch_gemm(unet_dense_args(zero, N, (const bf16_t*)o_scratch, HD, op_mat(wo, bo, C, HD), M, trunk_out, C, EPI_F16, trunk_in, C), st);
     })
 }
 int rt_op_groupnorm(const void* x1, const void* x2, int in_bf16, int C1, int C2, int G, int B, int HW, const float* gamma,
                     const float* beta, float eps, int silu, void* out, void* raw, void* stream) {
     OP_TRY({
-        GroupNormArgs a{}; a.x1 = x1; a.x2 = x2; a.in_bf16 = in_bf16; a.C1 = C1; a.C2 = C2; a.G = G; a.B = B; a.HW = HW;
-        a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu; a.out = (bf16_t*)out; a.raw_out = (bf16_t*)raw;
-        a.nchunk = groupnorm_nchunk(HW); a.rows_per_chunk = groupnorm_rows_per_chunk(HW);
         float* partial = nullptr;
-        HIP_CHECK(hipMalloc((void**)&partial, (size_t)B * a.nchunk * G * 2 * 4));
-        a.partial = partial; a.fuse_finalize = 1;               // the path the UNet forward takes
-        launch_groupnorm(a, (hipStream_t)stream);
+        HIP_CHECK(hipMalloc((void**)&partial, (size_t)B * groupnorm_nchunk(HW) * G * 2 * 4));
+        launch_groupnorm(unet_gn_args(x1, x2, in_bf16, C1, C2, G, B, HW, gamma, beta, eps, silu, (bf16_t*)out, (bf16_t*)raw, partial), (hipStream_t)stream);
         HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
         HIP_CHECK(hipFree(partial));
     })
@@ -1885,8 +1899,7 @@ int rt_op_groupnorm(const void* x1, const void* x2, int in_bf16, int C1, int C2,
 // Host-only: the form launch_groupnorm takes for that call (the predicate of the launcher itself; rt_op_gemm_debug bit 23 counts).
 int rt_op_groupnorm_form(int in_type, int C1, int C2, int G, int B, int HW) {
     if (in_type < 0 || in_type > 2 || C1 <= 0 || C2 < 0 || G < 1 || (C1 + C2) % G || B < 1 || HW < 1) return RT_E_INVALID;
-    GroupNormArgs a{}; a.in_bf16 = in_type; a.C1 = C1; a.C2 = C2; a.G = G; a.B = B; a.HW = HW;
-    return groupnorm_form(a);
+    return groupnorm_form(unet_gn_args(nullptr, nullptr, in_type, C1, C2, G, B, HW, nullptr, nullptr, 0.f, 0, nullptr, nullptr, nullptr));
 }
 // ---- the VAE's kernels beyond the contractions (vae_kernels.hip; GroupNorm forward with the low planes: norm.hip), one call each, with the
 // launch arguments of vae.h
@@ -2029,49 +2042,53 @@ int rt_op_attention_store_handover(const void* Q, int ldq, const void* K, int ld
         hipStream_t st = (hipStream_t)stream;
         RT_REQUIRE(B >= 1 && B <= RT_MAXB && store_stream >= 0 && store_stream < B && map_out && handover, "rt_op_attention_store_handover: batch / recorded stream / outputs");
         RT_REQUIRE(H >= 1 && H <= 32 && N >= 1, "rt_op_attention_store_handover: at most 32 heads");
-        AttnArgs a{}; a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.VT = (const bf16_t*)VT; a.ldvt = ldvt;
-        a.O = (bf16_t*)O; a.ldo = ldo; a.wabs = wabs; a.wsgn = wsgn; a.B = B; a.H = H; a.N = N; a.DP = DP; a.cross = cross;
-        AttnStoreArgs sa{}; sa.Q = a.Q; sa.ldq = ldq; sa.q_row0 = (long)store_stream * N; sa.K = a.K; sa.ldk = ldk;
-        sa.out = map_out; sa.H = H; sa.N = N; sa.DP = DP; sa.overwrite = accumulate ? 0 : 1;
+        const AttnIO io{(const bf16_t*)Q, ldq, (const bf16_t*)K, ldk, (const bf16_t*)VT, ldvt, (bf16_t*)O, ldo};
         float* scratch = op_store_stats((size_t)H * N * 2, st);
         bool taken = false;
         if (!cross) {
             RT_REQUIRE(NK == N, "rt_op_attention_store_handover: self-attention has as many keys as queries");
             int src[RT_MAXB];
-            for (int b = 0; b < B; ++b) {
-                src[b] = qk_src_host ? qk_src_host[b] : b;
-                RT_REQUIRE(src[b] >= 0 && src[b] < B, "rt_op_attention_store_handover: Q / K source");
-                a.q_src[b] = a.k_src[b] = src[b]; a.v_src[b] = b; a.wset[b] = 0;
-            }
-            a.NK = N; a.nk_valid = N;
+            for (int b = 0; b < B; ++b) src[b] = qk_src_host ? qk_src_host[b] : b;
+            for (int b = 0; b < B; ++b) RT_REQUIRE(src[b] >= 0 && src[b] < B, "rt_op_attention_store_handover: Q / K source");
             taken = scratch && store_handover_self(N, DP, src, store_stream);
-            if (taken) { a.stats = scratch; a.stats_b = store_stream; }
+            const AttnArgs a = unet_self_attn_args(io, src, B, H, N, DP, taken ? scratch : nullptr, store_stream);
             launch_attention(a, st);
             // the key COUNT is padded to the store's 32-key step, the key rows are not (a map of N % 32 == 0 tokens: NKpad = N as in the forward)
-            sa.k_row0 = (long)store_stream * N; sa.NK = N; sa.NKpad = (N + 31) / 32 * 32; sa.NKrows = N;
-            sa.stats = scratch; sa.stats_ready = taken ? 1 : 0;
+            launch_attn_store(unet_store_args(a, store_stream, map_out, !accumulate, scratch, (N + 31) / 32 * 32), st);
         } else {
             RT_REQUIRE(prompt_host && key_counts_host && (NK == 96 || NK == 192 || NK == 288), "rt_op_attention_store_handover: prompts of 96, 192 or 288 rows");
-            bool all77 = true;
-            for (int b = 0; b < B; ++b) {
-                const int c = key_counts_host[b];
-                RT_REQUIRE(c >= 77 && c % 77 == 0 && c / 77 * 96 <= NK && prompt_host[b] >= 0, "rt_op_attention_store_handover: a key count must be 77 per 96-row chunk of NK");
-                a.q_src[b] = b; a.k_src[b] = a.v_src[b] = prompt_host[b]; a.wset[b] = -1; a.nkeys[b] = c; all77 = all77 && c == 77;
-            }
-            a.NK = NK; a.nk_valid = 77;
-            const bool c77 = cross77_route(H, DP, d, N, NK, all77);
-            taken = scratch && store_handover_cross(c77);
-            if (taken) { a.stats = scratch; a.stats_b = store_stream; }
-            if (c77) launch_cross77(a, st);
-            else if (cross77_route(H, DP, d, N, NK, true)) launch_cross_runs(a, st);      // mixed key counts; no hand-over
-            else launch_attention(a, st);                                                // the generic launch: no hand-over
-            const int snk = key_counts_host[store_stream], srows = 96 * (snk / 77);
-            sa.k_row0 = (long)prompt_host[store_stream] * NK; sa.NK = snk; sa.NKpad = srows; sa.NKrows = srows;
-            if (taken) { sa.stats = scratch; sa.stats_ready = 1; }
+            int wset[RT_MAXB];
+            std::fill_n(wset, RT_MAXB, -1);
+            for (int b = 0; b < B; ++b)
+                RT_REQUIRE(op_key_count_ok(key_counts_host[b], NK) && prompt_host[b] >= 0, "rt_op_attention_store_handover: a key count must be 77 per 96-row chunk of NK");
+            // a recorded layer whose Q is in HBM: the two-launch routes; the statistics where the route hands them over
+            const CrossRoute route = cross_route(H * DP, H, d, DP, N, NK, key_counts_host, B, false, true, false);
+            taken = scratch && route.handover;
+            const AttnArgs a = unet_cross_attn_args(io, prompt_host, wset, key_counts_host, wabs, wsgn, B, H, N, NK, DP, taken ? scratch : nullptr, store_stream);
+            launch_cross(a, route, st);
+            launch_attn_store(unet_store_args(a, store_stream, map_out, !accumulate), st);
         }
-        launch_attn_store(sa, st);
         *handover = taken ? 1 : 0;
     })
+}
+// The forward's route of an attn2 launch as a host-only query (no device needed): cross_route and cross_run, under the same switches.
+int rt_op_cross_route(int C, int heads, int d, int DP, int tokens, int prompt_rows, const int* key_counts_host, int B, int folded, int recorded,
+                      int* kind, int* handover, int* stream_kernel) {
+    static_assert(CrossRoute::GENERIC == RT_CROSS_GENERIC && CrossRoute::CROSS77 == RT_CROSS_CROSS77 && CrossRoute::RUNS == RT_CROSS_RUNS &&
+                  CrossRoute::XATTN_FUSED == RT_CROSS_XATTN_FUSED && CrossRoute::XBLOCK == RT_CROSS_XBLOCK, "RT_CROSS_* mirror CrossRoute::Kind");
+    if (!key_counts_host || B < 1 || B > RT_MAXB || !(prompt_rows == 96 || prompt_rows == 192 || prompt_rows == 288)) return RT_E_INVALID;
+    for (int b = 0; b < B; ++b) if (!op_key_count_ok(key_counts_host[b], prompt_rows)) return RT_E_INVALID;
+    const CrossRoute r = cross_route(C, heads, d, DP, tokens, prompt_rows, key_counts_host, B, folded != 0, recorded != 0);
+    if (kind) *kind = r.kind;
+    if (handover) *handover = r.handover ? 1 : 0;
+    if (stream_kernel) {
+        for (int b = 0; b < B; ++b) stream_kernel[b] = r.kind == CrossRoute::GENERIC ? 0 : r.kind == CrossRoute::CROSS77 ? 1 : -1;
+        for (int b0 = 0, b1, kernel; r.kind == CrossRoute::RUNS && b0 < B; b0 = b1) {
+            b1 = cross_run(key_counts_host, B, b0, heads, DP, tokens, prompt_rows, &kernel);
+            std::fill(stream_kernel + b0, stream_kernel + b1, kernel);
+        }
+    }
+    return RT_OK;
 }
 
 }  // extern "C"

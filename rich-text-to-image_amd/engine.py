@@ -83,7 +83,7 @@ _SYMBOLS = [
     "rt_set_noise_seed", "rt_op_step_noise",
     "rt_set_prediction", "rt_op_guided_prediction",
     "rt_op_attention_store_handover",
-    "rt_op_gemm_route", "rt_op_groupnorm_form",
+    "rt_op_gemm_route", "rt_op_groupnorm_form", "rt_op_cross_route",
     "rt_set_freeu", "rt_op_freeu",
     "rt_op_gemm_hilo", "rt_op_gemm_hilo_route", "rt_op_split_bf16", "rt_op_vae_groupnorm_nchunk", "rt_op_vae_groupnorm", "rt_op_vae_groupnorm_bwd",
     "rt_op_softmax_rows", "rt_op_softmax_bwd", "rt_op_transpose_bf16", "rt_op_sumpool2x2", "rt_op_pq_conv_fwd", "rt_op_pq_conv_bwd_update",

@@ -134,6 +134,15 @@ def probs_avg_rc(Q, K, out, H, N, NK, NKpad, NKrows, DP, accumulate=0, q_row0=0,
     return rc
 
 
+def cross_route(C_, heads, d, DP, tokens, prompt_rows, key_counts, folded=False, recorded=False, lib=None):
+    """rt_op_cross_route (host only, under the current switches): (kind, hand-over, [kernel of every stream]) of the forward's attn2 launch."""
+    B = len(key_counts)
+    kind, hand, kern = C.c_int(-9), C.c_int(-9), (C.c_int * B)(*([-9] * B))
+    chk((lib or load_library()).rt_op_cross_route(C_, heads, d, DP, tokens, prompt_rows, (C.c_int * B)(*key_counts), B, int(folded), int(recorded),
+                                                  C.byref(kind), C.byref(hand), kern))
+    return kind.value, hand.value, list(kern)
+
+
 def store_handover(Q, K, VT, O, out, B, H, N, NK, d, DP, store_stream, cross=False, qk_src=None, prompt=None, key_counts=None, accumulate=0):
     """rt_op_attention_store_handover: the attention launch (writes O) + the store of `store_stream` (writes out); True when the
     attention launch handed its softmax statistics to the store."""

@@ -10,7 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attn_store_ref as R  # noqa: E402
-from hiputil import DEV, probs_avg_rc, store_handover  # noqa: E402
+from hiputil import DEV, cross_route, probs_avg_rc, store_handover  # noqa: E402
 from rich_text_to_image_amd.engine import load_library  # noqa: E402
 
 GUARD = 4096                 # floats on either side of the output buffer
@@ -196,7 +196,9 @@ def test_cross77_statistics_handover(H, N, stream, family):
             taken.append(store_handover(Q, K, VT, O, out, B, H, N, KP, d, DP, stream, cross=True, prompt=prompt, key_counts=[77] * B, accumulate=acc))
         with _debug(bits):
             got = _semantics(tag, run, N, 77)
+            asked = cross_route(H * d, H, d, DP, N, KP, [77] * B, recorded=True)
         assert all(t == (bits != R.B17) for t in taken), (tag, taken)
+        assert all(t == bool(asked[1]) for t in taken), (tag, taken, asked)      # the host-only query answers what the launch did
         _parity(tag + (" [taken]" if taken[0] else " [not taken]"), got, ref, Rbar, Rc)
         res[name] = O
     assert torch.isfinite(res["hand-over"].float()).all()
