@@ -63,6 +63,11 @@ typedef struct rt_config {
     int max_keys;                       /* keys of the longest prompt: 77, 154 or 231 = one, two or three 77-token CLIP windows (0 = 77).  Sizes the
                                          * K / V^T caches (96 rows per window and prompt), the font-size tables and the cross-map store; what a step
                                          * launches depends on the prompts' own key counts only (rt_set_prompts_keys), never on this capacity */
+    int ip_tokens;                      /* image tokens per prompt slot (IP-Adapter, rt_set_image_prompts): 0 = no image prompts - what a zero-initialised
+                                         * struct gets: nothing new is registered, allocated or launched and the weight table is the reference's
+                                         * state_dict layout - or 1 .. 16: every attn2 registers <module>.to_k_ip.weight / .to_v_ip.weight
+                                         * [heads d, cross_attention_dim] (packed like to_k / to_v, in the same arena) and keeps two more caches of
+                                         * 16 rows per prompt slot */
 } rt_config;
 
 typedef struct rt_engine rt_engine;
@@ -93,6 +98,18 @@ int rt_set_prompts(rt_engine* e, const float* prompt_embeds, const float* pooled
  * above max_keys is RT_E_INVALID, nothing is computed and the engine stays usable.  rt_set_prompts == L = 77, every count 77. */
 int rt_set_prompts_keys(rt_engine* e, const float* prompt_embeds, const int* key_counts_host, int L, const float* pooled,
                         const float* time_ids_host, int n_prompts, int pooled_dim);
+/* Image prompts by decoupled cross-attention (IP-Adapter; no counterpart in the reference).  Engines with rt_config.ip_tokens > 0 only.
+ * Slot p is the text prompt slot p of rt_set_prompts: a stream uses the image of the prompt it runs, in every stream mode and in the
+ * split steps alike.  tokens [n_prompts, ip_tokens, D] f32 on the device = the PROJECTED image tokens in cross-attention space (may be
+ * NULL when every scale is 0); counts_host[p] in 1 .. ip_tokens = the valid tokens of slot p (NULL: all); scales_host[p] finite, 0 = prompt
+ * p has no image.  Every attn2 then computes
+ *   O = attn(Q, K_text, V_text) + scale[p] attn(Q, to_k_ip(tokens[p]), to_v_ip(tokens[p]))        two separate softmaxes
+ * with the image term added into the attention output in place by one more launch (csrc/ipattn.hip) in front of to_out; it runs only for
+ * the streams whose prompt has scale != 0 - every other stream, and every launch without one, keeps the bits it has without this call.
+ * The token-map store records the text probabilities only.  Slots n_prompts .. are switched off.  rt_set_prompts / rt_set_prompts_keys
+ * reset every scale to 0 (the slots change meaning); every other call leaves the state alone.  n_prompts above the prompts set, a count
+ * out of range, a non-finite scale or an engine with ip_tokens == 0: RT_E_INVALID, the state is unchanged and the engine stays usable. */
+int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts_host, const float* scales_host, int n_prompts);
 /* region masks (model.masks, rd.py:97,119-128 / xl.py:775,810-821): [R,4,h,w] f32 */
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
 /* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables.
@@ -206,7 +223,9 @@ enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_
        RT_PROF_ATTN_STORE = 4 /* head-averaged map accumulation of the plain pass (attn_store_kernel, HBM-side accumulators); the
                                   * elementwise class, priced in bytes: the FreeU launches of rt_set_freeu are counted here too */,
        RT_PROF_XATTN_FUSED = 5 /* to_q + 77-key cross-attention as one launch (gemm16 EPI_XATTN): FLOPs = 2*M*HD*C + 4*B*H*N*77*d */,
-       RT_PROF_XBLOCK = 6 /* the whole cross-attention block as one launch (xblock.hip): FLOPs = 4*M*HD*C + 4*B*H*N*77*d */ };
+       RT_PROF_XBLOCK = 6 /* the whole cross-attention block as one launch (xblock.hip): FLOPs = 4*M*HD*C + 4*B*H*N*77*d */,
+       RT_PROF_IP_ATTN = 7 /* the image-prompt term of attn2 (ipattn.hip; rt_set_image_prompts): FLOPs = 4*H*N*d*(image tokens of the launch's
+                            * streams), bytes = Q read once + O read and written once for the streams that carry an image */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
 int rt_profile_read(rt_engine* e, int kernel_class, int* count, double* total_ms, double* total_flops);
 /* as rt_profile_read, plus the ALGORITHMIC HBM bytes of the launches (attention store: the fp32 accumulator read + written once and the
@@ -242,6 +261,16 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
 int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo,
                          const int* q_src_host, const int* prompt_host, const int* wset_host, const float* wabs, const float* wsgn,
                          const int* key_counts_host, int B, int H, int N, int NK, int DP, void* stream);
+/* The image-prompt term of rt_set_image_prompts alone (csrc/ipattn.hip), in place on the attention output: for batch entry b with slot
+ * s = slot_host[b], T = count_host[b] in 1 .. 16 keys and sigma = scale_host[b] (finite), every query n and head h:
+ *   p_j = softmax_j(Q[b, n, h, :] . Kip[s, j, h, :]),  j < T        (Q pre-scaled by d^-1/2 log2 e: base-2 exponent; keys T .. 15 masked)
+ *   O[b, n, h, :] <- bf16(fp32(O[b, n, h, :]) + sigma sum_j p_j Vip[s, j, h, :])                  one rounding of the sum
+ * Q [B N, ldq] and O [B N, ldo] bf16, head h at column h DP; Kip [*, ldk] bf16, row 16 s + j; VTip [H DP, ldvt] bf16, row h DP + d, column
+ * 16 s + j.  DP in {32, 64, 96, 128, 160}, N % 8 == 0, leading dimensions % 8 == 0, B <= 16.  slot < 0 or scale == 0: entry b is not
+ * launched and keeps its bytes.  Columns whose image term is exactly 0 (the pad columns d .. DP behind zero V^T rows) keep their bits.
+ * Each entry is a function of itself alone: deterministic and batch invariant. */
+int rt_op_ip_attention(const void* Q, int ldq, const void* Kip, int ldk, const void* VTip, int ldvt, void* O, int ldo,
+                       const int* slot_host, const int* count_host, const float* scale_host, int B, int H, int N, int DP, void* stream);
 /* Host-only (no GPU): the partition of a self-attention launch into shared-probability units (round 6; csrc/attention.hip).  Streams that
  * attend with the same (q_src, k_src) - text_ref and the region streams that take its probabilities, attention_processor.py:522-524 - are dealt
  * G at a time into units that compute softmax(QK^T) once; mode 0 = the shape rule (tokens >= 2048: units of four in their own launch, else

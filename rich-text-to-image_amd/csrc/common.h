@@ -301,6 +301,10 @@ bool cross77_supported(int H, int DP, int tokens, int NK, int nk_valid);
 void launch_cross77(const AttnArgs& a, hipStream_t st);
 bool crossmw_supported(int H, int DP, int tokens, int NK);    // crossmw_kernel (cross77.hip): streams of 154 / 231 keys, head dim 64
 void launch_crossmw(const AttnArgs& a, hipStream_t st);
+// ipattn.hip: the image-prompt term of decoupled cross-attention, O += scale[b] softmax(Q Kip[slot[b]]^T) Vip[slot[b]] in place over count[b] <= 16
+// keys (Kip [*, ldk] 16 rows per slot, VTip [H*DP, ldvt] 16 columns per slot); host arrays; slot < 0 or scale == 0: the stream is not launched
+void launch_ip_attention(const bf16_t* Q, int ldq, const bf16_t* Kip, int ldk, const bf16_t* VTip, int ldvt, bf16_t* O, int ldo, const int* slot,
+                         const int* count, const float* scale, int B, int H, int N, int DP, hipStream_t st);
 bool gemm_cross77_enabled();      // debug bit 19 clear
 int attention_units_plan_host(const int* q_src, const int* k_src, int B, int N, int DP, int mode, int* launch_of, int* unit_of, int* members_of);   // host-only: the partition launch_attention would take
 void gemm16_set_tall(int on);        // (A/B) rt_op_gemm_debug bit 27

@@ -85,6 +85,10 @@ struct TBlockP {
     float* qk1s = nullptr; float* v1s = nullptr; float* q2s = nullptr; float* ff1s = nullptr;
     bf16_t* kcache = nullptr;    // [maxP*KP, H*DP]   KP = 96 rows per 77-key chunk of rt_config.max_keys; a prompt's valid keys come first
     bf16_t* vtcache = nullptr;   // [H*DP, maxP*KP]
+    // image prompts (rt_config.ip_tokens > 0; ipattn.hip): to_k_ip / to_v_ip packed like k2 / v2, and their caches, 16 rows per prompt slot
+    MatW kip, vip;
+    bf16_t* kipcache = nullptr;  // [maxP*16, H*DP]   a slot's valid image tokens come first, the rest of its 16 rows are zero
+    bf16_t* vtipcache = nullptr; // [H*DP, maxP*16]
     // token-map attention store: index 0 = attn1, 1 = attn2
     std::string mod_name[2];
     float* store[2] = {nullptr, nullptr};
@@ -364,6 +368,10 @@ struct rt_engine {
     // per-image state
     int n_prompts = 0;
     std::vector<int> prompt_keys;    // [max_prompts] valid keys of every resident prompt (77 per chunk); rt_create fills 77
+    // rt_set_image_prompts: per prompt slot the valid image tokens and the scale of the image term (0 = the prompt has no image); rt_create
+    // sizes both to max_prompts, rt_set_prompts zeroes the scales
+    std::vector<int> ip_count;
+    std::vector<float> ip_scale;
     int KP() const { return 96 * (cfg.max_keys / 77); }      // rows per prompt in the K / V^T caches and the multiplier tables
     float* aug_emb = nullptr;        // [maxP, temb_dim] (zeros when no addition embedding)
     float* wabs = nullptr;           // [2, KP]
@@ -530,6 +538,12 @@ struct rt_engine {
             k.k2 = mk_headproj(b + ".attn2.to_k", D, heads, t.d, t.DP, 1.f, k2, D);
             bf16_t* v2 = (bf16_t*)arena.alloc((size_t)HD * D * 2);
             k.v2 = mk_headproj(b + ".attn2.to_v", D, heads, t.d, t.DP, 1.f, v2, D);
+            if (cfg.ip_tokens > 0) {
+                bf16_t* kip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
+                k.kip = mk_headproj(b + ".attn2.to_k_ip", D, heads, t.d, t.DP, 1.f, kip, D);
+                bf16_t* vip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
+                k.vip = mk_headproj(b + ".attn2.to_v_ip", D, heads, t.d, t.DP, 1.f, vip, D);
+            }
             k.out2 = mk_outproj(b + ".attn2.to_out.0", C, heads, t.d, t.DP);
             k.ln3 = mk_norm(b + ".norm3", C);
             // GEGLU: nn.Linear(C, 8C); rows interleaved per 64-block [32 value | 32 gate]
@@ -542,6 +556,10 @@ struct rt_engine {
             k.ff2 = mk_linear(b + ".ff.net.2", 4 * C, C, true);
             k.kcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
             k.vtcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
+            if (cfg.ip_tokens > 0) {
+                k.kipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
+                k.vtipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
+            }
             if (ln_fold_width(C)) {
                 auto mkf = [&](const MatW& w, MatW& f, float*& sv) {
                     f.N = w.N; f.K = w.K;
@@ -822,7 +840,22 @@ struct rt_engine {
                 const int KPr = KP(), ldvt2 = cfg.max_prompts * KPr;
                 int nkeys[RT_MAXB], wset2[RT_MAXB];
                 for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; wset2[b] = in.fontsize[b] ? 1 : -1; }      // -1: plain softmax, no multiplier tables
-                const CrossRoute route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2);
+                CrossRoute route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2);
+                // image prompts (rt_set_image_prompts): the image term is added into o behind the text attention, which the one-launch forms
+                // never write - a launch with an image takes the two-launch route of the same shape
+                int ip_slot[RT_MAXB], ip_cnt[RT_MAXB]; float ip_sc[RT_MAXB];
+                bool any_ip = false;
+                double ip_keys = 0;
+                for (int b = 0; b < B; ++b) {
+                    const bool on = cfg.ip_tokens > 0 && ip_scale[in.prompt[b]] != 0.f;
+                    ip_slot[b] = on ? in.prompt[b] : -1; ip_cnt[b] = on ? ip_count[in.prompt[b]] : 0; ip_sc[b] = on ? ip_scale[in.prompt[b]] : 0.f;
+                    if (on) { any_ip = true; ip_keys += ip_cnt[b]; }
+                }
+                // (Only RT_PROBES builds with their debug switches on ever reach the one-launch kinds.  The dry planning forward of an
+                // engine that can hold images takes the two-launch route as well, so that the to_q GEMM a launch with an image runs
+                // has been planned: its split-K scratch is recorded like every other GEMM's.)
+                if ((any_ip || (dry() && cfg.ip_tokens > 0)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
+                    route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2, false);
                 if (route.kind == CrossRoute::XBLOCK) {
                     if (!dry()) {
                         RT_REQUIRE(k.q2.K == C && k.out2.K == HD && HD == C, "xblock: packed projection widths");
@@ -856,6 +889,12 @@ struct rt_engine {
                         launch_attn_store(unet_store_args(a, in.store_stream, k.store[1], k.store_mode[1] == 2), stream);
                         prof_end();
                         k.store_rows[1] = HW; k.store_cols[1] = snk;
+                    }
+                    if (any_ip) {                                     // (the token-map store above recorded the text probabilities only)
+                        double nip = 0; for (int b = 0; b < B; ++b) nip += ip_slot[b] >= 0;
+                        prof_begin(RT_PROF_IP_ATTN, 4.0 * t.heads * (double)HW * ip_keys * t.d, 3.0 * 2.0 * nip * HW * HD);
+                        launch_ip_attention(qk, HD, k.kipcache, HD, k.vtipcache, cfg.max_prompts * 16, o, HD, ip_slot, ip_cnt, ip_sc, B, t.heads, HW, t.DP, stream);
+                        prof_end();
                     }
                 }
                 }
@@ -1047,7 +1086,43 @@ struct rt_engine {
         }
         n_prompts = P;
         for (int p_ = 0; p_ < P; ++p_) prompt_keys[p_] = counts ? counts[p_] : L;
+        std::fill(ip_scale.begin(), ip_scale.end(), 0.f);              // the slots change meaning: no prompt has an image until rt_set_image_prompts
         HIP_CHECK(hipStreamSynchronize(stream));   // host buffers (time_ids) may go away
+    }
+
+    // tokens [P, ip_tokens, D] fp32 (device): slot p's first counts[p] rows are its image tokens.  Validates everything before it touches the state.
+    void set_image_prompts(const float* tokens, const int* counts, const float* scales, int P) {
+        RT_REQUIRE(cfg.ip_tokens > 0, "set_image_prompts: the engine was built without image prompts (rt_config.ip_tokens == 0)");
+        RT_REQUIRE(scales, "set_image_prompts: scales");
+        RT_REQUIRE(P >= 1 && P <= n_prompts, "set_image_prompts: more slots than prompts set (rt_set_prompts first)");
+        bool any = false;
+        for (int p_ = 0; p_ < P; ++p_) {
+            RT_REQUIRE(std::isfinite(scales[p_]), "set_image_prompts: a scale must be finite");
+            RT_REQUIRE(!counts || (counts[p_] >= 1 && counts[p_] <= cfg.ip_tokens), "set_image_prompts: a count must be in 1 .. ip_tokens");
+            any = any || scales[p_] != 0.f;
+        }
+        RT_REQUIRE(tokens || !any, "set_image_prompts: tokens may be NULL only when every scale is 0");
+        require_bound();
+        if (tokens) {
+            const int D = cfg.cross_attention_dim, T = cfg.ip_tokens;
+            Scope sc(ws);
+            bf16_t* ctx = ws.b16((size_t)cfg.max_prompts * 16 * D);
+            for (int p_ = 0; p_ < P; ++p_)                            // rows past a slot's count are zeros, in the caches too
+                launch_pad_ctx(tokens + (size_t)p_ * T * D, ctx + (size_t)p_ * 16 * D, counts ? counts[p_] : T, 16, D, stream);
+            // one slot = one "stream" of 16 rows (set_prompts: a slot's cached bits do not depend on how many other slots are set)
+            cur_hw = 16;
+            for_each_tblock([&](TransformerP& t, TBlockP& k) {
+                const int HD = t.heads * t.DP;
+                gemm(ctx, D, k.kip, P * 16, k.kipcache, HD, EPI_BF16);
+                gemm_vt(k.vip, ctx, D, P * 16, k.vtipcache, cfg.max_prompts * 16);
+            });
+            cur_hw = 0;
+        }
+        for (int p_ = 0; p_ < cfg.max_prompts; ++p_) {
+            ip_scale[p_] = p_ < P ? scales[p_] : 0.f;
+            if (p_ < P) ip_count[p_] = counts ? counts[p_] : cfg.ip_tokens;
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));   // the launches read the caller's tokens
     }
 
     void set_fontsize(const int64_t* word_pos, const float* font_size, int n) {
@@ -1154,8 +1229,10 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         RT_REQUIRE(cfg->in_channels == 4 && cfg->out_channels == 4, "rt_create: latent channels must be 4");
         RT_REQUIRE(cfg->cross_attention_dim % 8 == 0, "rt_create: cross_attention_dim % 8");
         RT_REQUIRE(cfg->max_keys == 0 || cfg->max_keys == 77 || cfg->max_keys == 154 || cfg->max_keys == 231, "rt_create: max_keys must be 77, 154 or 231 (0 = 77)");
+        RT_REQUIRE(cfg->ip_tokens >= 0 && cfg->ip_tokens <= 16, "rt_create: ip_tokens must be 0 (no image prompts) or 1 .. 16");
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
+        e->ip_count.assign((size_t)std::max(1, cfg->max_prompts), 0); e->ip_scale.assign((size_t)std::max(1, cfg->max_prompts), 0.f);
         if (e->cfg.max_keys == 0) e->cfg.max_keys = 77;
         e->prompt_keys.assign((size_t)std::max(1, e->cfg.max_prompts), 77);
         // pass 1: measure the arena (no device needed: lets CPU-only hosts enumerate the weight table)
@@ -1195,6 +1272,12 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
                 e->for_each_tblock([&](TransformerP& t, TBlockP& k) {
                     e->gemm(nullptr, D, k.k2, P96, nullptr, t.heads * t.DP, EPI_BF16);
                     e->gemm_vt(k.v2, nullptr, D, P96, nullptr, P96);
+                    if (cfg->ip_tokens > 0) {      // ... and those of rt_set_image_prompts (one slot = one 16-row stream)
+                        e->cur_hw = 16;
+                        e->gemm(nullptr, D, k.kip, cfg->max_prompts * 16, nullptr, t.heads * t.DP, EPI_BF16);
+                        e->gemm_vt(k.vip, nullptr, D, cfg->max_prompts * 16, nullptr, cfg->max_prompts * 16);
+                        e->cur_hw = 96;
+                    }
                 });
                 e->cur_hw = 0;
             }
@@ -1297,6 +1380,9 @@ int rt_set_prompts(rt_engine* e, const float* pe, const float* pooled, const flo
 }
 int rt_set_prompts_keys(rt_engine* e, const float* pe, const int* key_counts, int L, const float* pooled, const float* tids, int P, int pooled_dim) {
     RT_TRY(e, { need_device(e); RT_REQUIRE(key_counts, "rt_set_prompts_keys: key counts"); e->ensure_fold(); e->set_prompts(pe, key_counts, L, pooled, tids, P, pooled_dim); })
+}
+int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts, const float* scales, int P) {
+    RT_TRY(e, { need_device(e); e->set_image_prompts(tokens, counts, scales, P); })
 }
 int rt_set_masks(rt_engine* e, const float* m, int R, int h, int w) {
     RT_TRY(e, {
@@ -1762,6 +1848,14 @@ int rt_op_attention(const void* Q, int ldq, const void* K, int ldk, const void* 
         int k77[RT_MAXB];
         for (int b = 0; b < B; ++b) { as77 = as77 && a.k_src[b] == a.v_src[b]; k77[b] = 77; }
         launch_cross(a, as77 ? cross_route(H * DP, H, DP, DP, N, NK, k77, B, false, false, false) : CrossRoute{CrossRoute::GENERIC, false}, (hipStream_t)stream);
+    })
+}
+int rt_op_ip_attention(const void* Q, int ldq, const void* Kip, int ldk, const void* VTip, int ldvt, void* O, int ldo, const int* slot_host,
+                       const int* count_host, const float* scale_host, int B, int H, int N, int DP, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(Q && Kip && VTip && O && slot_host && count_host && scale_host, "rt_op_ip_attention: null argument");
+        launch_ip_attention((const bf16_t*)Q, ldq, (const bf16_t*)Kip, ldk, (const bf16_t*)VTip, ldvt, (bf16_t*)O, ldo, slot_host, count_host, scale_host,
+                            B, H, N, DP, (hipStream_t)stream);
     })
 }
 int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const void* VT, int ldvt, void* O, int ldo, const int* q_src,

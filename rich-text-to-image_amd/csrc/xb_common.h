@@ -22,8 +22,9 @@ static __device__ __forceinline__ bf16x8 xb_pack8(const f32x4& a0, const f32x4& 
 }
 
 // Row reductions over the four 16-lane groups by gfx950's v_permlane16_swap / v_permlane32_swap (VALU) instead of two ds_bpermute
-// round trips.  The maxima are plain fmaxf: this file is compiled with -fno-honor-nans (scores are finite or -inf), which drops the
-// canonicalising self-max fmaxf's NaN semantics drag in.  (An inline-asm v_max3_f32 is NOT an option: hipcc's hazard recogniser does not
+// round trips.  The maxima are plain fmaxf: cross77.hip and xblock.hip are compiled with -fno-honor-nans (scores are finite or -inf), which
+// drops the canonicalising self-max fmaxf's NaN semantics drag in; ipattn.hip includes this header under the generic flags and pays that
+// one extra v_max per operand (five maxima per 16-query tile of a launch bound by bytes).  (An inline-asm v_max3_f32 is NOT an option: hipcc's hazard recogniser does not
 // see the registers an asm statement reads, so the wait states between an MFMA and a VALU read of its result were missing and the
 // maxima were taken over stale registers - harmless for the mathematics, any reference works, but the last bits differed from run to
 // run, which the determinism tests caught.)

@@ -54,6 +54,7 @@ class RtConfig(C.Structure):
         ("latent_h", C.c_int), ("latent_w", C.c_int),
         ("max_streams", C.c_int), ("max_prompts", C.c_int),
         ("max_keys", C.c_int),
+        ("ip_tokens", C.c_int),
     ]
 
 
@@ -88,6 +89,7 @@ _SYMBOLS = [
     "rt_op_gemm_hilo", "rt_op_gemm_hilo_route", "rt_op_split_bf16", "rt_op_vae_groupnorm_nchunk", "rt_op_vae_groupnorm", "rt_op_vae_groupnorm_bwd",
     "rt_op_softmax_rows", "rt_op_softmax_bwd", "rt_op_transpose_bf16", "rt_op_sumpool2x2", "rt_op_pq_conv_fwd", "rt_op_pq_conv_bwd_update",
     "rt_op_color_loss_grad",
+    "rt_set_image_prompts", "rt_op_ip_attention",
 ]
 
 
@@ -128,8 +130,9 @@ def _tup(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
 
-def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77):
-    """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window)."""
+def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0):
+    """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window).
+    ip_tokens: image tokens per prompt slot of an IP-Adapter (1 .. 16); 0 = none: the weight table is the reference's state_dict layout."""
     c = RtConfig()
     boc = tuple(cfg["block_out_channels"])
     n = len(boc)
@@ -156,6 +159,7 @@ def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_
     c.latent_h, c.latent_w = latent_h, latent_w
     c.max_streams, c.max_prompts = max_streams, max_prompts
     c.max_keys = max_keys
+    c.ip_tokens = int(ip_tokens)
     return c
 
 
@@ -166,11 +170,12 @@ def _ptr(t):
 class Engine:
     """One engine = one GPU.  Mirrors the C ABI one to one; see include/rtdiff.h for semantics."""
 
-    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77):
+    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0):
         self.lib = load_library()
         self.cfg_dict = dict(cfg_dict)
-        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys)
+        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens)
         self.max_keys = max_keys
+        self.ip_tokens = int(ip_tokens)
         self.h = C.c_void_p()
         self.device = device
         rc = self.lib.rt_create(C.byref(self.cfg), C.c_int(device), C.byref(self.h))
@@ -278,6 +283,24 @@ class Engine:
         assert len(kc) == pe.shape[0], (len(kc), pe.shape[0])
         self._chk(self.lib.rt_set_prompts_keys(self.h, _ptr(pe), (C.c_int * len(kc))(*kc), pe.shape[1], _ptr(pl), tid, pe.shape[0],
                                                pl.shape[1] if pl is not None else 0))
+
+    def set_image_prompts(self, tokens, scales, counts=None):
+        """Image prompts of the prompt slots of the last set_prompts (include/rtdiff.h: rt_set_image_prompts; engines built with
+        ip_tokens > 0).  tokens [P, ip_tokens, D]: the projected image tokens of slot p (None when every scale is 0); scales [P], 0 = that
+        prompt has no image; counts [P] in 1 .. ip_tokens (default: all).  set_prompts switches every image off again."""
+        sc = [float(v) for v in scales]
+        P = len(sc)
+        tk = None
+        if tokens is not None:
+            tk = tokens.contiguous().float()
+            if tk.dim() != 3 or tuple(tk.shape[:2]) != (P, self.ip_tokens) or tk.shape[2] != self.cfg.cross_attention_dim:
+                raise ValueError(f"set_image_prompts: tokens must be [{P}, {self.ip_tokens}, {self.cfg.cross_attention_dim}], got {tuple(tk.shape)}")
+        cn = None
+        if counts is not None:
+            cn = [int(v) for v in counts]
+            if len(cn) != P:
+                raise ValueError(f"set_image_prompts: {len(cn)} counts for {P} scales")
+        self._chk(self.lib.rt_set_image_prompts(self.h, _ptr(tk), (C.c_int * P)(*cn) if cn is not None else None, (C.c_float * max(1, P))(*sc), P))
 
     def set_masks(self, masks):
         """masks: list of [1,4,h,w] tensors (model.masks) or one [R,4,h,w] tensor."""
@@ -396,6 +419,13 @@ class Engine:
         self._chk(self.lib.rt_profile_read2(self.h, self.PROF_STORE, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)))
         return dict(launches=n.value, total_ms=ms.value, total_flops=fl.value, total_bytes=by.value)
 
+    PROF_IP = 7             # ipattn_kernel (the image-prompt term of attn2, set_image_prompts): FLOPs and algorithmic HBM bytes
+
+    def profile_read_ip(self):
+        n, ms, fl, by = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.rt_profile_read2(self.h, self.PROF_IP, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)))
+        return dict(launches=n.value, total_ms=ms.value, total_flops=fl.value, total_bytes=by.value)
+
     def profile_enable(self, on=True):
         self._chk(self.lib.rt_profile_enable(self.h, int(on)))
 
@@ -484,6 +514,29 @@ def step_noise(seed, step, h, w, words=False, device=0):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return (out, wd.to(torch.int64) & 0xFFFFFFFF) if words else out
+
+
+def ip_attention(Q, Kip, VTip, O, slots, counts, scales, H, N, DP):
+    """The image-prompt term of decoupled cross-attention alone (rt_op_ip_attention), IN PLACE on O: bf16 2-D tensors (views with a row
+    stride are fine: the stride is the leading dimension) Q / O [B N, >= H DP], Kip [16 slots, >= H DP], VTip [H DP, >= 16 slots]; per
+    batch entry a slot (-1: skipped), its valid keys (1 .. 16) and the scale (0: skipped).  Returns O."""
+    import torch
+    lib = load_library()
+    B = len(slots)
+    for t in (Q, Kip, VTip, O):
+        assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.device == O.device, "ip_attention: bf16 [rows, ld] tensors on one device"
+    assert len(counts) == B and len(scales) == B and Q.shape[0] >= B * N and O.shape[0] >= B * N, "ip_attention: batch"
+    assert VTip.shape[0] >= H * DP and min(Q.shape[1], O.shape[1], Kip.shape[1]) >= H * DP, "ip_attention: widths"
+    assert all(s < 0 or (16 * (s + 1) <= Kip.shape[0] and 16 * (s + 1) <= VTip.shape[1]) for s in slots), "ip_attention: slot outside the caches"
+    with torch.cuda.device(O.device):
+        rc = lib.rt_op_ip_attention(_ptr(Q), int(Q.stride(0)), _ptr(Kip), int(Kip.stride(0)), _ptr(VTip), int(VTip.stride(0)), _ptr(O), int(O.stride(0)),
+                                    (C.c_int * B)(*[int(v) for v in slots]), (C.c_int * B)(*[int(v) for v in counts]),
+                                    (C.c_float * B)(*[float(v) for v in scales]), B, int(H), int(N), int(DP),
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return O
 
 
 def freeu(hidden, skip, H, W, b=1.0, s=1.0):

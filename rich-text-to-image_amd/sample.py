@@ -39,10 +39,22 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     keyword; the SDXL rich pass, whose keyword the reference refuses, takes it as the pipeline attribute, set around that one call and
     restored after it.
     `param['freeu']` (optional, four numbers s1 s2 b1 b2): FreeU in both passes of THIS request - the pipeline attribute
-    (enable_freeu) for the duration of the call, restored after it; absent / None: the pipeline as it is."""
-    fu = param.get('freeu')
+    (enable_freeu) for the duration of the call, restored after it; absent / None: the pipeline as it is.
+    `param['image_prompts']` (optional; ip_adapter.image_prompts_from_specs' result: dict(base=, regions=, negative=) of dict(file=,
+    scale=)): the image prompts of THIS request on a pipeline with an IP-Adapter loaded - set for the call, restored after it; `base`
+    holds in both passes, `regions` (by region number) in the rich pass; absent / None: the pipeline as it is."""
     args = (model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background, latents,
             init_image, strength, keep_source)
+    ip = param.get('image_prompts')
+    if ip is not None:
+        from .ip_adapter import apply_specs
+        keep_ip = getattr(model, 'image_prompts', None)
+        apply_specs(model, ip)
+        try:
+            return generate(model, {k: v for k, v in param.items() if k != 'image_prompts'}, *args)
+        finally:
+            model.image_prompts = keep_ip
+    fu = param.get('freeu')
     if fu is None:
         return _generate(model, param, *args)
     from .freeu import check_freeu
@@ -204,12 +216,51 @@ def check_requests_freeu(path):
                 check_freeu_arg(json.loads(line).get("freeu"), f"--requests line {n}: freeu")
 
 
+def check_ip_args(a):
+    """--ip_adapter / --ip_image_embeds and the "image_prompts" keys of a --requests file, checked before any rank starts: the adapter
+    and every embedding file exist, every FILE[:TARGET[:SCALE]] parses, no image prompt without an adapter.  Bad values end the run
+    (SystemExit).  Returns the flag's image prompts (ip_adapter.image_prompts_from_specs) or None."""
+    from .ip_adapter import image_prompts_from_specs
+
+    def parse(specs, who):
+        try:
+            ip = image_prompts_from_specs(specs, who)
+            for e in [ip["base"], ip["negative"], *ip["regions"].values()]:
+                if e is not None and not os.path.isfile(e["file"]):
+                    raise ValueError(f"{who}: file not found: {e['file']}")
+        except ValueError as e:
+            raise SystemExit(f"sample: {e}")
+        if not getattr(a, "ip_adapter", None):
+            raise SystemExit(f"sample: {who} needs --ip_adapter")
+        return ip
+    if getattr(a, "ip_adapter", None) and not os.path.isfile(a.ip_adapter):
+        raise SystemExit(f"sample: --ip_adapter: file not found: {a.ip_adapter}")
+    flag = parse(a.ip_image_embeds, "--ip_image_embeds") if getattr(a, "ip_image_embeds", None) else None
+    if getattr(a, "requests", None):
+        with open(a.requests) as f:
+            for n, line in enumerate(f, 1):
+                if line.strip() and json.loads(line).get("image_prompts") is not None:
+                    parse(json.loads(line)["image_prompts"], f"--requests line {n}: image_prompts")
+    return flag
+
+
+def _request_image_prompts(a, r):
+    """A --requests line's "image_prompts" (a list of FILE[:TARGET[:SCALE]] strings or {"file", "target", "scale"} objects), else the flag's."""
+    if r.get("image_prompts") is None:
+        return getattr(a, "image_prompts", None)
+    from .ip_adapter import image_prompts_from_specs
+    try:
+        return image_prompts_from_specs(r["image_prompts"], "--requests: image_prompts")
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
+
+
 def build_requests(a):
     """The (rich-text JSON, seed) list of one invocation.  One JSON + one --seed = the reference's single image.  Several JSONs and / or
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
     one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
-    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
+    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -222,13 +273,14 @@ def build_requests(a):
                 reqs.append(dict(text_input=_load_json_arg(js) if isinstance(js, str) else js, seed=int(r.get("seed", a.seed)),
                                  negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
                                  max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1)))),
-                                 freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu")))
+                                 freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu"),
+                                 image_prompts=_request_image_prompts(a, r)))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
         reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1),
-                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu")) for j, sd in pairs]
+                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None)) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -245,15 +297,22 @@ def build_model(a, rank=0, local_rank=0, world=1):
     res = 512 if a.model == 'SD' else 1024
     # the VAE plan (decode + colour guidance workspace) is sized for the requested image, like the UNet engine
     hw = ((a.height or res) // 8, (a.width or res) // 8)
+    def with_adapter(m):          # --ip_adapter: every rank reads the file itself (the small image_proj tensors; the layer weights travel in the arena)
+        if getattr(a, 'ip_adapter', None):
+            try:
+                m.load_ip_adapter(a.ip_adapter)
+            except ValueError as e:
+                raise SystemExit(f"sample: --ip_adapter: {e}")
+        return m
     if world == 1:
         if a.model == 'SD':
-            return apply_scheduler(RegionDiffusion(torch.device('cuda'), load_path=a.load_path, latent_hw=hw), a), 0.0
+            return apply_scheduler(with_adapter(RegionDiffusion(torch.device('cuda'), load_path=a.load_path, latent_hw=hw)), a), 0.0
         xl_path = a.load_path or ("stabilityai/stable-diffusion-xl-base-1.0" if a.model == 'SDXL' else "Linaqruf/animagine-xl")
         model = RegionDiffusionXL(load_path=xl_path, latent_hw=hw)
         if getattr(a, 'guidance_precision', 'fp32') == 'bf16':
             from .checkpoint import load_guidance_vae, resolve_checkpoint
             model.guidance_vae = load_guidance_vae(resolve_checkpoint(xl_path, 'SDXL'), 'SDXL', 0, hw)
-        return apply_scheduler(model, a), 0.0
+        return apply_scheduler(with_adapter(model), a), 0.0
     from . import launcher
     from .checkpoint import load_components, resolve_checkpoint
     kind = 'SD' if a.model == 'SD' else 'SDXL'
@@ -265,6 +324,7 @@ def build_model(a, rank=0, local_rank=0, world=1):
     else:
         model = RegionDiffusionXL(None, local_rank, **comp)
         encoders = list(comp["text_encoders"].encoders)
+    with_adapter(model)                                              # before the engine exists: its arena holds the adapter's projections
     eng = model.unet.engine(hw[0], hw[1])                            # the engine (and its arena) must exist on every rank before the broadcast
     seconds = launcher.broadcast_pipeline(eng, model.vae, encoders, src=0, pipeline=model)
     return apply_scheduler(model, a), seconds
@@ -375,6 +435,13 @@ def build_parser():
                    help='FreeU (diffusers enable_freeu, same order): in the first two up blocks of the UNet the four lowest frequency bins of '
                         'the skip features are scaled by S1 / S2 and half of the backbone channels by B1 / B2, in both passes; all > 0. '
                         'Usual values: SD-v1.5 0.9 0.2 1.5 1.6, SDXL 0.6 0.4 1.1 1.2.  Default: off.  Holds on every rank of --gpus N')
+    p.add_argument('--ip_adapter', type=str, default=None, metavar='PATH',
+                   help='IP-Adapter checkpoint (.safetensors / .bin, the original layout or diffusers\' names; linear image projection): image '
+                        'prompts by decoupled cross-attention, see --ip_image_embeds.  Holds on every rank of --gpus N')
+    p.add_argument('--ip_image_embeds', type=str, nargs='+', default=None, metavar='FILE[:TARGET[:SCALE]]',
+                   help='with --ip_adapter: a CLIP image embedding (.pt / .npy / .safetensors; a [t, D] matrix = ready image tokens) as the image '
+                        'prompt of TARGET = base (default: the whole picture, both passes), negative, or a region number of the rich text '
+                        '(that region alone); SCALE defaults to 1')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
                    help='what the UNet predicts; default: the checkpoint\'s scheduler/scheduler_config.json, else epsilon')
     p.add_argument('--timestep_spacing', type=str, default=None, choices=['leading', 'trailing'],
@@ -419,6 +486,7 @@ def main(argv=None):
     a.freeu = check_freeu_arg(a.freeu, "--freeu")      # ... and so do bad FreeU values, the flag's and a --requests line's
     if a.requests:
         check_requests_freeu(a.requests)
+    a.image_prompts = check_ip_args(a)                 # ... and a missing adapter / embedding file or a malformed FILE[:TARGET[:SCALE]]
     if a.init_image is None and a.keep_source != 'none':
         raise SystemExit("sample: --keep_source needs --init_image")
     if a.init_image is not None and a.keep_source != 'none' and a.split_image:
@@ -455,7 +523,7 @@ def main(argv=None):
         apply_request_scheduler(model, flag_scheduler, r, a)
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
-                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu')}
+                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu'), 'image_prompts': r.get('image_prompts')}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

@@ -5,10 +5,13 @@ import types
 import torch
 
 from .engine import Engine
+from .ip_adapter import IPAdapterMixin
 
 
-class HipUNet2DConditionModel:
-    """Holds the engine(s) for one set of weights; engines are created lazily per latent size."""
+class HipUNet2DConditionModel(IPAdapterMixin):
+    """Holds the engine(s) for one set of weights; engines are created lazily per latent size.  With an IP-Adapter installed
+    (load_ip_adapter) every engine is built with its image tokens per prompt and carries its to_k_ip / to_v_ip weights; the operator
+    seam __call__ stays text-only."""
 
     def __init__(self, config, state_dict=None, device=0, max_streams=8, max_prompts=8, max_keys=77):
         self.config_dict = dict(config)
@@ -19,6 +22,20 @@ class HipUNet2DConditionModel:
         self._state_dict = state_dict
         self._engines = {}
         self.freeu = None                          # (s1, s2, b1, b2) or None = off: on every engine of this model, present and future
+        self.ip_tokens, self._ip_weights = 0, None # install_ip_adapter: image tokens per prompt slot (0 = no adapter) and the adapter's layer weights
+
+    def install_ip_adapter(self, adapter):
+        """adapter: what ip_adapter.load_ip_adapter returns, or None = remove it.  The weight table - and with it the arena - changes, so
+        the engines are dropped and rebuilt on their next use.  A model built "empty" (ranks != 0 of a multi-GPU launch) holds its weights
+        nowhere but in the arena of its engines, which a changed layout could not take over: once it has an engine this is refused and
+        nothing changes - install the adapter before the first engine() call, as sample.build_model does."""
+        if isinstance(self._state_dict, str) and self._state_dict == "empty" and self._engines:
+            raise RuntimeError("HipUNet2DConditionModel: the weights of this model arrived by broadcast and live in its engines only; "
+                               "load / unload an IP-Adapter before the first engine is built")
+        self.ip_tokens, self._ip_weights = (adapter["T"], adapter["weights"]) if adapter is not None else (0, None)
+        for e in self._engines.values():
+            e.close()
+        self._engines = {}
 
     def enable_freeu(self, s1, s2, b1, b2):
         """diffusers' `unet.enable_freeu(s1, s2, b1, b2)` (argument order included): FreeU in the first two up blocks of every forward
@@ -71,7 +88,7 @@ class HipUNet2DConditionModel:
                 raise RuntimeError("HipUNet2DConditionModel: no weights loaded (call load_state_dict)")
             try:
                 e = Engine(self.config_dict, h, w, device=self.device_index, max_streams=self.max_streams,
-                           max_prompts=self.max_prompts, max_keys=self.max_keys)
+                           max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens)
                 try:
                     if empty:
                         if donor is not None:
@@ -85,6 +102,11 @@ class HipUNet2DConditionModel:
                         # otherwise the packed arena arrives by launcher.broadcast_weights
                     elif isinstance(self._state_dict, str) and self._state_dict.startswith("random"):
                         e.init_random_weights(seed=int(self._state_dict[6:] or 0))      # "random<seed>": benchmarks without checkpoints
+                        for name, t in (self._ip_weights or {}).items():
+                            e.bind_weight(name, t.to(f"cuda:{self.device_index}"))
+                        e.synchronize()
+                    elif self._ip_weights:
+                        e.load_state_dict({**self._state_dict, **self._ip_weights})
                     else:
                         e.load_state_dict(self._state_dict)
                     if self.freeu is not None:
