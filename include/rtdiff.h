@@ -82,6 +82,9 @@ int rt_synchronize(rt_engine* e);
 /* weights: names are the reference UNet's state_dict keys (unet.load_state_dict, rd.py:32, xl.py:115) --- */
 int rt_weight_count(rt_engine* e);
 int rt_weight_info(rt_engine* e, int idx, char* name, int name_cap, int64_t* shape4, int* ndim);
+/* A weight may be bound again at any time (LoRA, tests): everything the engine derives from it follows - packed forms at once, the
+ * LayerNorm-folded projections at the next forward.  Re-binding a weight that rt_set_prompts reads (attn2.to_k / to_v, to_k_ip / to_v_ip,
+ * add_embedding.*) - and rt_arena_mark_bound - discards the prompts: call rt_set_prompts again before the next forward or step. */
 int rt_bind_weight(rt_engine* e, const char* name, const void* dev_ptr, int dtype, const int64_t* shape, int ndim);
 int rt_weights_missing(rt_engine* e, char* buf, int cap);            /* returns count; names ';'-joined into buf */
 int rt_arena_info(rt_engine* e, void** dev_ptr, uint64_t* bytes);    /* packed arena, for one RCCL broadcast */
@@ -238,6 +241,19 @@ int rt_profile_read2(rt_engine* e, int kernel_class, int* count, double* total_m
 int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float timestep, const float* in_scale_host,
                     const int* prompt_idx_host, const int* fontsize_host, const int* qk_src_host,
                     const int* res_src_host, float* out);
+/* Trace seam (test infrastructure in the product, like the rt_op_* entries): the SAME forward - `out` equals rt_unet_forward's bit for
+ * bit - which, when the module `module_name` has finished, copies the trunk tensor that module leaves (fp16 NHWC) to trace_out_dev as
+ * fp32 NCHW [B, C, h', w'].  Traceable modules carry the reference's module names: "conv_in", every "...resnets.j", every
+ * "...attentions.j" (the whole Transformer2DModel, residual included), every "...downsamplers.0.conv" / "...upsamplers.0.conv" and
+ * "conv_out" (whose tensor is `out` itself).  rt_trace_module_info lists them in execution order with their channel count C and the
+ * power of two their grid is smaller than the latent grid by (h' = h >> downshift); it needs no device.  An unknown name or
+ * trace_cap_floats < B C h' w' is an error (rt_last_error) before anything is launched or written.  The copy is one plain kernel
+ * between the module and its successor; a traced forward is not meant for hipGraph capture. */
+int rt_unet_forward_trace(rt_engine* e, const float* x, int B, int h, int w, float timestep, const float* in_scale_host,
+                          const int* prompt_idx_host, const int* fontsize_host, const int* qk_src_host, const int* res_src_host,
+                          float* out, const char* module_name, float* trace_out_dev, long long trace_cap_floats);
+int rt_trace_module_count(rt_engine* e);
+int rt_trace_module_info(rt_engine* e, int idx, char* name, int name_cap, int* channels, int* downshift);
 
 /* epi: 0 bf16 out | 1 fp32 out (+ fp32 residual) | 2 bf16 out + per-batch-entry time embedding | 3 GEGLU (bf16 out, N/2 columns)
  *      | 4 fp16 out (+ fp16 residual): the UNet's residual trunk (fp32 arithmetic in the epilogue, fp16 in HBM like the reference's

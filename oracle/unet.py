@@ -25,7 +25,11 @@ Hook semantics (models/region_diffusion.py:313-395,465-494; region_diffusion_sdx
 are expressed through the `ctl` argument of `forward`:
   ctl = {"fontsize": {"word_pos": LongTensor, "font_size": FloatTensor} | None,   # attn2 only
          "capture": dict | None,   # filled with per-head attn1 probs + 'up_blocks.1.resnets.1' feature
-         "inject":  dict | None}   # same keys: attn1 probs replace softmax, resnet feature injected
+         "inject":  dict | None,   # same keys: attn1 probs replace softmax, resnet feature injected
+         "trace": dict | None,     # filled with the trunk tensor [B, C, h', w'] every traceable module leaves, under the module's name:
+                                   # conv_in, every ...resnets.j, ...attentions.j (residual included), ...downsamplers.0.conv,
+                                   # ...upsamplers.0.conv and conv_out (= the forward's result), in execution order
+         "trace_stop": str | None} # the forward ends behind that module and returns ITS tensor (saves the rest of the CPU time)
 """
 import math
 
@@ -221,6 +225,15 @@ class OracleUNet:
             return x + inj[name]                                             # :639-641
         return x + h
 
+    @staticmethod
+    def _trace(ctl, name, x):
+        """Records x under `name` in ctl["trace"]; True when the forward is to end here (ctl["trace_stop"])."""
+        if not ctl:
+            return False
+        if ctl.get("trace") is not None:
+            ctl["trace"][name] = x.detach()
+        return ctl.get("trace_stop") == name
+
     # ---- forward (unet_2d_condition.py:703-983) -----------------------------------------------
     def forward(self, sample, timestep, ctx, added=None, ctl=None, store=None):
         """sample [B,4,h,w]; timestep scalar; ctx [B,77,D]; added = {"text_embeds","time_ids"}.
@@ -238,23 +251,37 @@ class OracleUNet:
             aug = self._lin(F.silu(self._lin(add, "add_embedding.linear_1")), "add_embedding.linear_2")
             emb = emb + aug
         x = self._conv(sample.float(), "conv_in")
+        if self._trace(ctl, "conv_in", x):
+            return x
         skips = [x]
         nlev = len(boc)
         for i, bt in enumerate(c["down_block_types"]):
             heads = c["attention_head_dim"][i]
             for j in range(c["layers_per_block"][i]):
                 x = self._resnet(f"down_blocks.{i}.resnets.{j}", x, emb, ctl)
+                if self._trace(ctl, f"down_blocks.{i}.resnets.{j}", x):
+                    return x
                 if bt == "CrossAttnDownBlock2D":
                     x = self._transformer(f"down_blocks.{i}.attentions.{j}", x, ctx, heads,
                                           c["transformer_layers_per_block"][i], ctl, store)
+                    if self._trace(ctl, f"down_blocks.{i}.attentions.{j}", x):
+                        return x
                 skips.append(x)
             if i != nlev - 1:
                 x = self._conv(x, f"down_blocks.{i}.downsamplers.0.conv", stride=2, padding=1)
+                if self._trace(ctl, f"down_blocks.{i}.downsamplers.0.conv", x):
+                    return x
                 skips.append(x)
         heads = c["attention_head_dim"][-1]
         x = self._resnet("mid_block.resnets.0", x, emb, ctl)
+        if self._trace(ctl, "mid_block.resnets.0", x):
+            return x
         x = self._transformer("mid_block.attentions.0", x, ctx, heads, c["transformer_layers_per_block"][-1], ctl, store)
+        if self._trace(ctl, "mid_block.attentions.0", x):
+            return x
         x = self._resnet("mid_block.resnets.1", x, emb, ctl)
+        if self._trace(ctl, "mid_block.resnets.1", x):
+            return x
         rev_heads = list(reversed(c["attention_head_dim"]))
         rev_tl = list(reversed(c["transformer_layers_per_block"]))
         rev_lpb = list(reversed(c["layers_per_block"]))
@@ -262,13 +289,21 @@ class OracleUNet:
             for j in range(rev_lpb[i] + 1):
                 x = torch.cat([x, skips.pop()], dim=1)
                 x = self._resnet(f"up_blocks.{i}.resnets.{j}", x, emb, ctl)
+                if self._trace(ctl, f"up_blocks.{i}.resnets.{j}", x):
+                    return x
                 if bt == "CrossAttnUpBlock2D":
                     x = self._transformer(f"up_blocks.{i}.attentions.{j}", x, ctx, rev_heads[i], rev_tl[i], ctl, store)
+                    if self._trace(ctl, f"up_blocks.{i}.attentions.{j}", x):
+                        return x
             if i != nlev - 1:
                 x = F.interpolate(x, scale_factor=2.0, mode="nearest")       # resnet.py:160
                 x = self._conv(x, f"up_blocks.{i}.upsamplers.0.conv")
+                if self._trace(ctl, f"up_blocks.{i}.upsamplers.0.conv", x):
+                    return x
         x = F.silu(self._gn(x, "conv_norm_out", c["norm_eps"]))
-        return self._conv(x, "conv_out")
+        x = self._conv(x, "conv_out")
+        self._trace(ctl, "conv_out", x)
+        return x
 
 
 def reference_kwargs(config):

@@ -155,6 +155,7 @@ static inline bool rt_sched_is_stoch(int kind) { return kind == RT_SCHED_EULER_A
 void launch_gather_add_rows(const float* base, const float* table, const int* /*host*/ idx, float* out, int B, int C, hipStream_t st);
 void launch_inject_add(f16_t* out, const f16_t* sc, const float* hres, const int* /*host*/ src, int B, size_t per_batch, hipStream_t st);
 void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_t st);
+void launch_trace_f16_nhwc_to_nchw(const f16_t* in, float* out, int B, int C, int HW, hipStream_t st);
 void launch_pad_ctx(const float* ctx, bf16_t* out, int rows_valid, int rows_out, int D, hipStream_t st);
 void launch_background_blend(float* lat, const float* lat_ref, const float* mask_last, int n, hipStream_t st);
 void launch_noise_latents(float* lat, float* lat_ref, const float* x0, const float* noise, float a, float b, int n, hipStream_t st);
@@ -414,6 +415,18 @@ struct rt_engine {
     }
     void prof_end() { if (profiling) HIP_CHECK(hipEventRecord(prof.back().b, stream)); }
 
+    // trace seam (rt_unet_forward_trace): the modules whose trunk tensor can be read, in execution order (build_plan), and the request of
+    // the running forward (empty name: none).  trace_point is a no-op unless the forward was asked for exactly that module.
+    struct TraceMod { std::string name; int C; int shift; };      // grid of the module's output = the latent grid >> shift
+    std::vector<TraceMod> trace_mods;
+    std::string trace_name;
+    float* trace_out = nullptr;
+    bool tracing() const { return !trace_name.empty() && !dry(); }      // (callers that have to BUILD a module's name ask first: an untraced forward allocates nothing)
+    void trace_point(const std::string& name, const Tensor& x, int B, int HW) {
+        if (!tracing() || trace_name != name) return;
+        launch_trace_f16_nhwc_to_nchw(x.p, trace_out, B, x.C, HW, stream);
+    }
+
     // ---------------------------------------------------------------------------- plan building
     void add_slot(const std::string& name, std::vector<int64_t> shape, const PackArgs& pk) {
         WeightSlot s; s.name = name; s.shape = std::move(shape); s.pack = pk;
@@ -575,12 +588,13 @@ struct rt_engine {
     }
 
     void build_plan() {
-        slots.clear(); slot_index.clear(); down.clear(); up.clear(); temb_tab.clear(); temb_total = 0;
+        slots.clear(); slot_index.clear(); down.clear(); up.clear(); temb_tab.clear(); temb_total = 0; trace_mods.clear();
         const int L = cfg.n_levels;
         const int* boc = cfg.block_out_channels;
         temb_dim = boc[0] * 4;
         zero = (bf16_t*)sarena.alloc(256);
         conv_in = mk_conv3("conv_in", cfg.in_channels, boc[0]);
+        trace_mods.push_back({"conv_in", boc[0], 0});
         t1 = mk_linear("time_embedding.linear_1", boc[0], temb_dim, true);
         t2 = mk_linear("time_embedding.linear_2", temb_dim, temb_dim, true);
         if (cfg.addition_text_time) {
@@ -594,14 +608,19 @@ struct rt_engine {
             const std::string pre = "down_blocks." + std::to_string(i);
             for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
                 d.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), j == 0 ? in_c : out_c, out_c));
-                if (d.has_attn) d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i));
+                trace_mods.push_back({d.res.back().name, out_c, i});
+                if (d.has_attn) {
+                    d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i));
+                    trace_mods.push_back({d.attn.back().name, out_c, i});
+                }
             }
-            if (d.has_down) d.down = mk_conv3(pre + ".downsamplers.0.conv", out_c, out_c);
+            if (d.has_down) { d.down = mk_conv3(pre + ".downsamplers.0.conv", out_c, out_c); trace_mods.push_back({pre + ".downsamplers.0.conv", out_c, i + 1}); }
             down.push_back(d);
         }
         mid_r0 = mk_resnet("mid_block.resnets.0", boc[L - 1], boc[L - 1]);
         mid_t = mk_transformer("mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1);
         mid_r1 = mk_resnet("mid_block.resnets.1", boc[L - 1], boc[L - 1]);
+        for (const char* m : {"mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1"}) trace_mods.push_back({m, boc[L - 1], L - 1});
         out_c = boc[L - 1];
         for (int i = 0; i < L; ++i) {
             UpP u; const int prev = out_c; out_c = boc[L - 1 - i];
@@ -613,13 +632,18 @@ struct rt_engine {
                 const int skip_c = j == nl - 1 ? in_c : out_c;
                 const int res_in = j == 0 ? prev : out_c;
                 u.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), res_in + skip_c, out_c));
-                if (u.has_attn) u.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[L - 1 - i], cfg.transformer_layers[L - 1 - i], L - 1 - i));
+                trace_mods.push_back({u.res.back().name, out_c, L - 1 - i});
+                if (u.has_attn) {
+                    u.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[L - 1 - i], cfg.transformer_layers[L - 1 - i], L - 1 - i));
+                    trace_mods.push_back({u.attn.back().name, out_c, L - 1 - i});
+                }
             }
-            if (u.has_up) u.up = mk_conv3(pre + ".upsamplers.0.conv", out_c, out_c, true);
+            if (u.has_up) { u.up = mk_conv3(pre + ".upsamplers.0.conv", out_c, out_c, true); trace_mods.push_back({pre + ".upsamplers.0.conv", out_c, L - 2 - i}); }
             up.push_back(u);
         }
         norm_out = mk_norm("conv_norm_out", boc[0]);
         conv_out = mk_conv3("conv_out", boc[0], cfg.out_channels);
+        trace_mods.push_back({"conv_out", cfg.out_channels, 0});
         // per-image sampler state
         const size_t HW = (size_t)cfg.latent_h * cfg.latent_w;
         aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
@@ -971,13 +995,15 @@ struct rt_engine {
             conv3(x8, A_CONV3, conv_in, B, Hh, Ww, 8, x0, EPI_F16);
             x = Tensor{x0, cfg.block_out_channels[0]};
         }
+        if (tracing()) trace_point("conv_in", x, B, HW0);
         skips.push_back(x);
         int ch = Hh, cw = Ww;
         for (size_t i = 0; i < down.size(); ++i) {
             DownP& d = down[i];
             for (size_t j = 0; j < d.res.size(); ++j) {
                 x = resnet(d.res[j], in, ch * cw, ch, cw, x, nullptr, emb, false);
-                if (d.has_attn) x = transformer(d.attn[j], in, ch * cw, x);
+                trace_point(d.res[j].name, x, B, ch * cw);
+                if (d.has_attn) { x = transformer(d.attn[j], in, ch * cw, x); trace_point(d.attn[j].name, x, B, ch * cw); }
                 skips.push_back(x);
             }
             if (d.has_down) {
@@ -991,12 +1017,16 @@ struct rt_engine {
                 }
                 ch = nh; cw = nw;
                 x = Tensor{y, d.C};
+                if (tracing()) trace_point("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", x, B, ch * cw);
                 skips.push_back(x);
             }
         }
         x = resnet(mid_r0, in, ch * cw, ch, cw, x, nullptr, emb, false);
+        trace_point(mid_r0.name, x, B, ch * cw);
         x = transformer(mid_t, in, ch * cw, x);
+        trace_point(mid_t.name, x, B, ch * cw);
         x = resnet(mid_r1, in, ch * cw, ch, cw, x, nullptr, emb, false);
+        trace_point(mid_r1.name, x, B, ch * cw);
         for (size_t i = 0; i < up.size(); ++i) {
             UpP& u = up[i];
             for (size_t j = 0; j < u.res.size(); ++j) {
@@ -1011,7 +1041,8 @@ struct rt_engine {
                     prof_end();
                 }
                 x = resnet(u.res[j], in, ch * cw, ch, cw, x, &sk, emb, inject_here);
-                if (u.has_attn) x = transformer(u.attn[j], in, ch * cw, x);
+                trace_point(u.res[j].name, x, B, ch * cw);
+                if (u.has_attn) { x = transformer(u.attn[j], in, ch * cw, x); trace_point(u.attn[j].name, x, B, ch * cw); }
             }
             if (u.has_up) {
                 f16_t* y = ws.f16((size_t)B * ch * cw * 4 * u.C);
@@ -1023,6 +1054,7 @@ struct rt_engine {
                 }
                 ch *= 2; cw *= 2;
                 x = Tensor{y, u.C};
+                if (tracing()) trace_point("up_blocks." + std::to_string(i) + ".upsamplers.0.conv", x, B, ch * cw);
             }
         }
         {
@@ -1363,7 +1395,13 @@ int rt_bind_weight(rt_engine* e, const char* name, const void* ptr, int dtype, c
         launch_pack(p, e->stream);
         if (s.up2) launch_pack_up2(ptr, dtype, s.up2, s.up2_cout, s.up2_cin, e->stream);
         s.bound = true;
+        // Derived data follows a re-bind: the up-sampler phase pack above, the folded projections at the next forward (fold_dirty) and the
+        // time_emb_proj table, which every forward reads from the arena.  What rt_set_prompts derived from the OLD weight - the K / V^T caches
+        // (attn2.to_k / to_v, to_k_ip / to_v_ip) and the addition embeddings (add_embedding.*) - cannot be rebuilt here (the engine does
+        // not keep the prompt embeddings): the prompts are discarded, and a forward or step before the next rt_set_prompts is an error.
         e->fold_dirty = true;
+        if (s.name.compare(0, 14, "add_embedding.") == 0 || s.name.find(".attn2.to_k") != std::string::npos || s.name.find(".attn2.to_v") != std::string::npos)
+            e->n_prompts = 0;
     })
 }
 int rt_weights_missing(rt_engine* e, char* buf, int cap) {
@@ -1373,7 +1411,7 @@ int rt_weights_missing(rt_engine* e, char* buf, int cap) {
     return n;
 }
 int rt_arena_info(rt_engine* e, void** p, uint64_t* bytes) { RT_TRY(e, { need_device(e); *p = e->arena_base; *bytes = e->arena_bytes; }) }
-int rt_arena_mark_bound(rt_engine* e) { for (auto& s : e->slots) s.bound = true; e->fold_dirty = true; return RT_OK; }
+int rt_arena_mark_bound(rt_engine* e) { for (auto& s : e->slots) s.bound = true; e->fold_dirty = true; e->n_prompts = 0; return RT_OK; }
 
 int rt_set_prompts(rt_engine* e, const float* pe, const float* pooled, const float* tids, int P, int pooled_dim) {
     RT_TRY(e, { need_device(e); e->ensure_fold(); e->set_prompts(pe, nullptr, 77, pooled, tids, P, pooled_dim); })
@@ -1507,12 +1545,31 @@ int rt_plain_step_part(rt_engine* e, int i, int part, int nparts, int* first, in
 }
 int rt_plain_step_finish(rt_engine* e, int i, float g) { RT_TRY(e, { need_device(e); e->plain_finish(i, g); }) }
 
-int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt,
-                    const int* fontsize, const int* qk_src, const int* res_src, float* out) {
-    RT_TRY(e, {
+// rt_unet_forward and rt_unet_forward_trace: one body.  module == nullptr: no trace.  The request is validated before anything is launched.
+static void unet_forward_entry(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt, const int* fontsize,
+                               const int* qk_src, const int* res_src, float* out, const char* module, float* trace_out, long long trace_cap) {
+    {
         need_device(e); e->require_bound();
         RT_REQUIRE(B >= 1 && B <= e->cfg.max_streams, "rt_unet_forward: batch");
-        RT_REQUIRE(e->n_prompts > 0, "rt_unet_forward: call rt_set_prompts first");
+        if (e->n_prompts <= 0)
+            throw rt_error(RT_E_INVALID, "rt_unet_forward: call rt_set_prompts first (rt_bind_weight of a weight that rt_set_prompts reads - attn2.to_k / to_v, add_embedding.* - "
+                                       "discards the prompts: their cached K / V and addition embeddings were derived from the old weight)");
+        bool final_out = false;
+        if (module) {
+            RT_REQUIRE(trace_out, "rt_unet_forward_trace: trace_out is NULL");
+            const rt_engine::TraceMod* tm = nullptr;
+            for (const auto& m : e->trace_mods) if (m.name == module) tm = &m;
+            if (!tm) throw rt_error(RT_E_INVALID, std::string("rt_unet_forward_trace: not a traceable module: ") + module);
+            const long long need = (long long)B * tm->C * (h >> tm->shift) * (w >> tm->shift);
+            if (trace_cap < need)
+                throw rt_error(RT_E_INVALID, "rt_unet_forward_trace: trace_cap_floats " + std::to_string(trace_cap) + " < " + std::to_string(need) + " for " + module);
+            final_out = tm->name == "conv_out";
+        }
+        struct TraceScope {      // the request lives for this forward only, also when it throws
+            rt_engine* e;
+            TraceScope(rt_engine* e_, const char* name, float* dst) : e(e_) { e->trace_name = name ? name : ""; e->trace_out = dst; }
+            ~TraceScope() { e->trace_name.clear(); e->trace_out = nullptr; }
+        } scope(e, module && !final_out ? module : nullptr, trace_out);
         FwdIn in{}; in.B = B; in.h = h; in.w = w; in.t = t; in.eps_out = e->eps;
         for (int b = 0; b < B; ++b) {
             in.x[b] = x + (size_t)b * 4 * h * w; in.scale[b] = in_scale ? in_scale[b] : 1.f;
@@ -1523,6 +1580,29 @@ int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float t, 
         }
         e->unet_forward(in);
         launch_nhwc4_to_nchw(e->eps, out, B, h * w, e->stream);
+        if (final_out) launch_nhwc4_to_nchw(e->eps, trace_out, B, h * w, e->stream);      // conv_out's tensor is `out` itself
+    }
+}
+int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt,
+                    const int* fontsize, const int* qk_src, const int* res_src, float* out) {
+    RT_TRY(e, { unet_forward_entry(e, x, B, h, w, t, in_scale, prompt, fontsize, qk_src, res_src, out, nullptr, nullptr, 0); })
+}
+int rt_unet_forward_trace(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt, const int* fontsize,
+                          const int* qk_src, const int* res_src, float* out, const char* module_name, float* trace_out_dev, long long trace_cap_floats) {
+    RT_TRY(e, {
+        RT_REQUIRE(module_name, "rt_unet_forward_trace: module_name is NULL");
+        unet_forward_entry(e, x, B, h, w, t, in_scale, prompt, fontsize, qk_src, res_src, out, module_name, trace_out_dev, trace_cap_floats);
+    })
+}
+int rt_trace_module_count(rt_engine* e) { return (int)e->trace_mods.size(); }
+int rt_trace_module_info(rt_engine* e, int idx, char* name, int cap, int* channels, int* downshift) {
+    RT_TRY(e, {
+        RT_REQUIRE(idx >= 0 && idx < (int)e->trace_mods.size(), "rt_trace_module_info: index");
+        const auto& m = e->trace_mods[idx];
+        RT_REQUIRE(name && (int)m.name.size() < cap, "rt_trace_module_info: name buffer too small");
+        std::strcpy(name, m.name.c_str());
+        if (channels) *channels = m.C;
+        if (downshift) *downshift = m.shift;
     })
 }
 

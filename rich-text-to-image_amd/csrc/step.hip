@@ -211,6 +211,20 @@ void launch_nhwc4_to_nchw(const float* in, float* out, int B, int HW, hipStream_
     HIP_CHECK(hipGetLastError());
 }
 
+// trace seam (rt_unet_forward_trace): the fp16 trunk [B, HW, C] as fp32 [B, C, HW]; one output element per thread, stores coalesced along HW
+__global__ void trace_f16_nhwc_to_nchw_kernel(const f16_t* in, float* out, size_t n, int C, int HW) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t pix = i % HW, bc = i / HW, c = bc % C, b = bc / C;
+        out[i] = (float)in[(b * HW + pix) * C + c];
+    }
+}
+void launch_trace_f16_nhwc_to_nchw(const f16_t* in, float* out, int B, int C, int HW, hipStream_t st) {
+    const size_t n = (size_t)B * C * HW;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(trace_f16_nhwc_to_nchw_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, in, out, n, C, HW);
+    HIP_CHECK(hipGetLastError());
+}
+
 // one prompt: its rows_valid embedding rows as bf16, zeros behind them up to the rows_out rows the prompt owns in the K / V^T caches
 __global__ void pad_ctx_kernel(const float* ctx, bf16_t* out, int rows_valid, int rows_out, int D) {
     const size_t n = (size_t)rows_out * D;

@@ -90,6 +90,7 @@ _SYMBOLS = [
     "rt_op_softmax_rows", "rt_op_softmax_bwd", "rt_op_transpose_bf16", "rt_op_sumpool2x2", "rt_op_pq_conv_fwd", "rt_op_pq_conv_bwd_update",
     "rt_op_color_loss_grad",
     "rt_set_image_prompts", "rt_op_ip_attention",
+    "rt_unet_forward_trace", "rt_trace_module_count", "rt_trace_module_info",
 ]
 
 
@@ -484,7 +485,21 @@ class Engine:
     def plain_step_finish(self, i, guidance_scale):
         self._chk(self.lib.rt_plain_step_finish(self.h, i, C.c_float(guidance_scale)))
 
-    def unet_forward(self, x, timestep, prompt_idx, in_scale=None, fontsize=None, qk_src=None, res_src=None):
+    def trace_modules(self):
+        """The modules whose trunk tensor unet_forward(..., trace=name) can read, in execution order: [(name, channels, downshift)]
+        (include/rtdiff.h: rt_trace_module_info; the module's grid is the latent grid >> downshift).  Needs no device."""
+        n = self.lib.rt_trace_module_count(self.h)
+        name = C.create_string_buffer(256)
+        ch, sh = C.c_int(), C.c_int()
+        out = []
+        for i in range(n):
+            self._chk(self.lib.rt_trace_module_info(self.h, i, name, 256, C.byref(ch), C.byref(sh)))
+            out.append((name.value.decode(), ch.value, sh.value))
+        return out
+
+    def unet_forward(self, x, timestep, prompt_idx, in_scale=None, fontsize=None, qk_src=None, res_src=None, trace=None):
+        """trace = a module name of trace_modules(): returns (out, the trunk tensor that module leaves as fp32 [B, C, h', w']) - the same
+        forward, `out` bit for bit (rt_unet_forward_trace: test infrastructure)."""
         import torch
         x = x.contiguous().float()
         B, _, h, w = x.shape
@@ -493,6 +508,16 @@ class Engine:
         def iarr(v):
             return (C.c_int * B)(*[int(k) for k in v]) if v is not None else None
         sc = (C.c_float * B)(*[float(k) for k in in_scale]) if in_scale is not None else None
+        if trace is not None:
+            shapes = {n: (c, s) for n, c, s in self.trace_modules()}
+            if trace not in shapes:
+                raise RtError(-1, f"unet_forward: not a traceable module: {trace}")
+            ch, sh = shapes[trace]
+            tr = torch.empty(B, ch, h >> sh, w >> sh, device=x.device)
+            self._chk(self.lib.rt_unet_forward_trace(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
+                                                     iarr(qk_src), iarr(res_src), _ptr(out), trace.encode(), _ptr(tr), C.c_longlong(tr.numel())))
+            self.synchronize()
+            return out, tr
         self._chk(self.lib.rt_unet_forward(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx),
                                            iarr(fontsize), iarr(qk_src), iarr(res_src), _ptr(out)))
         self.synchronize()
