@@ -466,6 +466,20 @@ int rt_op_activation(const void* x_bf16, void* out_bf16, long long n, int kind, 
 /* causal self-attention over N <= 128 tokens: q, k, v bf16 [B*N, ld] with head h at column h*d; out bf16 [B*N, ldo] */
 int rt_op_causal_attention(const void* q, const void* k, const void* v, int ld, void* out, int ldo, int B, int H, int N, int d, float scale,
                            void* stream);
+/* ---- CLIP vision encoder pieces (transformers' CLIPVisionModelWithProjection, the image encoder of IP-Adapter); the patch convolution,
+ * the linear layers and the LayerNorms are rt_op_gemm / rt_op_layernorm (rt_op_layernorm: C <= 2048).
+ * img_u8 [B, S, S, 3] uint8 RGB (device), S % p == 0 -> out_bf16 [B (S/p)^2, Kp]: column (c p + ky) p + kx = (u / 255 - mean[c]) / std[c] (the
+ * flatten order of the conv weight [C, 3, p, p]), columns 3 p^2 .. Kp written as zeros; Kp % 8 == 0, Kp >= 3 p^2; mean / std: 3 host floats */
+int rt_op_patchify(const void* img_u8, void* out_bf16, int B, int S, int p, int Kp, const float* mean_host, const float* std_host, void* stream);
+/* out [B N, C] fp32 = LayerNorm_{gamma, beta, eps}(e), e[b N] = cls + pos[0], e[b N + 1 + i] = patch[b (N - 1) + i] + pos[1 + i]: patch [B (N - 1),
+ * ldp] fp32, cls [C], pos [N, C], gamma / beta [C] fp32; two-pass statistics in fp32; N >= 2, C <= 2048 */
+int rt_op_vit_embed(const float* patch, int ldp, const float* cls, const float* pos, const float* gamma, const float* beta, float* out,
+                    int B, int N, int C, float eps, void* stream);
+/* unmasked self-attention over 1 <= N <= 640 tokens: q, k, v bf16 [B*N, ld] with head h at column h*d; out bf16 [B*N, ldo]; d % 8 == 0,
+ * d <= 128, ld % 8 == 0, ldo % 4 == 0, q / k / v 16-byte and out 8-byte aligned.  fp32 scores and online softmax, P rounded to bf16 for
+ * the PV product, fp32 accumulation.  Anything else is RT_E_INVALID. */
+int rt_op_bidir_attention(const void* q, const void* k, const void* v, int ld, void* out, int ldo, int B, int H, int N, int d, float scale,
+                          void* stream);
 /* Head-averaged attention probabilities of ONE batch entry (the `attention_probs_avg` the reference processor returns,
  * attention_processor.py:541-545, reshape_batch_dim_to_heads_and_average): out[N, NK] (=|+=) mean_h softmax(Q_h K_h^T).
  * Q rows q_row0+[0,N), K rows k_row0+[0,NKrows) in the rt_op_attention layouts; NK valid keys (any count: processed in chunks of

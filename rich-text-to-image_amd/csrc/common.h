@@ -377,6 +377,15 @@ void launch_embed(const int* ids, const float* tok, const float* pos, float* out
 void launch_activation(const bf16_t* x, bf16_t* out, size_t n, int kind, hipStream_t st);      // 0 quick_gelu, 1 gelu(erf)
 void launch_causal_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, bf16_t* out, int ldo, int B, int H, int N, int d,
                              float scale, hipStream_t st);
+// CLIP vision encoder pieces (vision.hip)
+// uint8 RGB [B, S, S, 3] -> bf16 patch rows [B (S/p)^2, Kp], column (c p + ky) p + kx = (u / 255 - mean_c) / std_c, columns 3 p^2 .. Kp zero
+void launch_patchify(const uint8_t* img, bf16_t* out, int B, int S, int p, int Kp, const float* mean, const float* stdv, hipStream_t st);
+// fp32 trunk [B N, C] = LayerNorm(row 0: cls + pos[0]; row 1 + i: patch[b (N - 1) + i] + pos[1 + i]); C <= 2048
+void launch_vit_embed(const float* patch, int ldp, const float* cls, const float* pos, const float* gamma, const float* beta, float* out,
+                      int B, int N, int C, float eps, hipStream_t st);
+// unmasked self-attention, operands as launch_causal_attention; 1 <= N <= 640, d % 8 == 0, d <= 128
+void launch_bidir_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, bf16_t* out, int ldo, int B, int H, int N, int d,
+                            float scale, hipStream_t st);
 
 // weight packing (device side): strided gather fp32/fp16/bf16 -> bf16 (or f32) with scale.
 //   dst (r, c) <- scale * src[ srow(r)*s_r + (c / c_inner)*s_co + (c % c_inner)*s_ci ]   (0 where invalid)

@@ -2166,6 +2166,17 @@ int rt_op_causal_attention(const void* q, const void* k, const void* v, int ld, 
                            void* stream) {
     OP_TRY({ launch_causal_attention((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (bf16_t*)out, ldo, B, H, N, d, scale, (hipStream_t)stream); })
 }
+int rt_op_patchify(const void* img_u8, void* out_bf16, int B, int S, int p, int Kp, const float* mean_host, const float* std_host, void* stream) {
+    OP_TRY({ launch_patchify((const uint8_t*)img_u8, (bf16_t*)out_bf16, B, S, p, Kp, mean_host, std_host, (hipStream_t)stream); })
+}
+int rt_op_vit_embed(const float* patch, int ldp, const float* cls, const float* pos, const float* gamma, const float* beta, float* out,
+                    int B, int N, int C, float eps, void* stream) {
+    OP_TRY({ launch_vit_embed(patch, ldp, cls, pos, gamma, beta, out, B, N, C, eps, (hipStream_t)stream); })
+}
+int rt_op_bidir_attention(const void* q, const void* k, const void* v, int ld, void* out, int ldo, int B, int H, int N, int d, float scale,
+                          void* stream) {
+    OP_TRY({ launch_bidir_attention((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (bf16_t*)out, ldo, B, H, N, d, scale, (hipStream_t)stream); })
+}
 int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev, unsigned int* words_dev, void* stream) {
     OP_TRY({
         RT_REQUIRE(out_dev && step >= 0 && h >= 1 && w >= 1 && (long long)h * w <= (1ll << 30), "rt_op_step_noise: bad arguments");

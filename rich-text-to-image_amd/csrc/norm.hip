@@ -554,7 +554,7 @@ void launch_groupnorm(const GroupNormArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------- LayerNorm: one wave per row
 // A lane owns 8 consecutive channels per 512-channel pass: two 16-B loads, ONE 16-B store (with 4 channels per lane the kernel sat
 // at 4.0 TB/s, bound by the number of 8-B store instructions: guide T21).
-#define LN_MAXP 3   // C <= 1536 (8 channels per lane per 512-channel pass)
+#define LN_MAXP 4   // C <= 2048 (8 channels per lane per 512-channel pass); NP = 4 is its own instantiation (CLIP ViT-bigG's 1664)
 template <bool F16IN>
 __device__ __forceinline__ void ln_load8(const void* xr, int c, float4 (&v)[2]) {
     if (F16IN) {
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(256) void layernorm40_kernel(const void* __restrict
 
 void launch_layernorm(const void* x, int x_f16, const float* gamma, const float* beta, bf16_t* out, int rows, int C,
                       float eps, hipStream_t st) {
-    RT_REQUIRE(C % 8 == 0 && C >= 8 && C <= LN_MAXP * 512, "layernorm: C must be a multiple of 8 and <= 1536");
+    RT_REQUIRE(C % 8 == 0 && C >= 8 && C <= LN_MAXP * 512, "layernorm: C must be a multiple of 8 and <= 2048");
     if (C == 320 || C == 640 || C == 1280) {                        // 40 * LPR
         const int lpr = C / 40, rpb = 4 * (64 / lpr);
         const dim3 grid40(cdiv(rows, rpb)), block40(256);
@@ -700,8 +700,8 @@ void launch_layernorm(const void* x, int x_f16, const float* gamma, const float*
     const dim3 grid(cdiv(rows, 4)), block(256);
     const int np = cdiv(C, 512);
 #define RT_LN(F16_, NP_) hipLaunchKernelGGL((layernorm_kernel<F16_, NP_>), grid, block, 0, st, x, gamma, beta, out, rows, C, eps)
-    if (x_f16) { if (np == 1) RT_LN(true, 1); else if (np == 2) RT_LN(true, 2); else RT_LN(true, 3); }
-    else { if (np == 1) RT_LN(false, 1); else if (np == 2) RT_LN(false, 2); else RT_LN(false, 3); }
+    if (x_f16) { if (np == 1) RT_LN(true, 1); else if (np == 2) RT_LN(true, 2); else if (np == 3) RT_LN(true, 3); else RT_LN(true, 4); }
+    else { if (np == 1) RT_LN(false, 1); else if (np == 2) RT_LN(false, 2); else if (np == 3) RT_LN(false, 3); else RT_LN(false, 4); }
 #undef RT_LN
     HIP_CHECK(hipGetLastError());
 }

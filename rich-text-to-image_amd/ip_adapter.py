@@ -5,8 +5,11 @@ rt_set_image_prompts); this module holds the host side: the checkpoint loader, t
 once per image) and the pipeline attribute both facades share.  A stream uses the image of the prompt it runs, so a rich-text request
 can give every region its own reference image, one to the base prompt, or none.
 
-Not here: a CLIP vision encoder (image embeddings come from the caller, as prompt_embeds do for SD-2.x), the Resampler projection of the
-"plus" checkpoints (its ready tokens can be passed as `tokens=`), FaceID, several adapters at once, per-layer scales."""
+An entry may also be a picture (`image=`): `load_image_encoder` puts a CLIP vision encoder (clip_vision_encoder.py) on the pipeline, which
+encodes the picture once, outside the step.  Without one, image embeddings come from the caller, as prompt_embeds do for SD-2.x.
+
+Not here: the Resampler projection of the "plus" checkpoints (the encoder's hidden_states[-2] can be fed to one by the caller and its
+ready tokens passed as `tokens=`), FaceID, several adapters at once, per-layer scales."""
 import ctypes as C
 import math
 import os
@@ -133,12 +136,13 @@ def project(adapter, image_embeds, device=0):
     return out.float()
 
 
-def check_entry(entry, who, adapter):
-    """dict(embeds=[E] | tokens=[t <= T, D], scale=float) -> a checked copy (tensors on the CPU, fp32); ValueError otherwise."""
+def check_entry(entry, who, adapter, encoder=None):
+    """dict(embeds=[E] | tokens=[t <= T, D] | image=<path | PIL image | [H, W, 3] uint8>, scale=float) -> a checked copy (tensors on the
+    CPU, fp32; an image as the uint8 crop the encoder takes); ValueError otherwise.  `encoder`: the pipeline's image encoder or None."""
     import torch
-    if not isinstance(entry, dict) or ("embeds" in entry) == ("tokens" in entry) or set(entry) - {"embeds", "tokens", "scale"}:
-        raise ValueError(f"{who}: expected dict(embeds=[E] or tokens=[t, D], scale=number), got {entry!r}" if not isinstance(entry, dict)
-                         else f"{who}: expected exactly one of embeds= / tokens= and an optional scale=, got keys {sorted(entry)}")
+    if not isinstance(entry, dict) or sum(k in entry for k in ("embeds", "tokens", "image")) != 1 or set(entry) - {"embeds", "tokens", "image", "scale"}:
+        raise ValueError(f"{who}: expected dict(embeds=[E], tokens=[t, D] or image=picture, scale=number), got {entry!r}" if not isinstance(entry, dict)
+                         else f"{who}: expected exactly one of embeds= / tokens= / image= and an optional scale=, got keys {sorted(entry)}")
     try:
         scale = float(entry.get("scale", 1.0))
     except (TypeError, ValueError):
@@ -146,6 +150,17 @@ def check_entry(entry, who, adapter):
     if not math.isfinite(scale):
         raise ValueError(f"{who}: scale must be finite, got {scale}")
     out = dict(scale=scale)
+    if "image" in entry:
+        if encoder is None:
+            raise ValueError(f"{who}: image= needs an image encoder: none is loaded on this pipeline (load_image_encoder / --image_encoder)")
+        if encoder.projection_dim != adapter["E"]:
+            raise ValueError(f"{who}: the image encoder's projection_dim is {encoder.projection_dim}, the adapter's projection takes {adapter['E']}")
+        from .clip_vision_encoder import preprocess
+        try:
+            out["image"] = torch.from_numpy(preprocess(entry["image"], encoder.S).copy())
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}")
+        return out
     if "embeds" in entry:
         e = torch.as_tensor(entry["embeds"]).detach().float().cpu().reshape(-1)
         if e.numel() != adapter["E"]:
@@ -166,6 +181,7 @@ class IPAdapterMixin:
     pipeline (and of HipUNet2DConditionModel, which holds the engines): the adapter and the image prompts are attributes, read by every
     sampling call right after it has set its text prompts (apply_image_prompts)."""
     ip_adapter = None        # what load_ip_adapter() of this module returns, or None
+    image_encoder = None     # clip_vision_encoder.LazyImageEncoder / HipCLIPVisionEncoder (load_image_encoder), or None
     image_prompts = None     # dict(base=entry | None, regions={region index: entry}, negative=entry | None) or None
 
     def _ip_unet(self):
@@ -185,8 +201,24 @@ class IPAdapterMixin:
         self._ip_unet().install_ip_adapter(None)
         self.ip_adapter = self.image_prompts = None
 
+    def load_image_encoder(self, path_or_encoder):
+        """A CLIP vision encoder for `image=` entries: a directory in the Hugging Face layout (read and checked now, on the host; put on
+        the GPU by the first image that needs it) or a HipCLIPVisionEncoder.  ValueError naming the file or key for anything unusable."""
+        import os as _os
+        if isinstance(path_or_encoder, (str, _os.PathLike)):
+            from .clip_vision_encoder import LazyImageEncoder
+            path_or_encoder = LazyImageEncoder(path_or_encoder)
+        elif not (callable(path_or_encoder) and hasattr(path_or_encoder, "projection_dim") and hasattr(path_or_encoder, "S")):
+            raise ValueError(f"load_image_encoder: expected a directory or a HipCLIPVisionEncoder, got {type(path_or_encoder).__name__}")
+        self.image_encoder = path_or_encoder
+        return self
+
+    def unload_image_encoder(self):
+        """Image prompts given as pictures keep what has been encoded already; new `image=` entries are refused again."""
+        self.image_encoder = None
+
     def set_image_prompts(self, base=None, regions=None, negative=None):
-        """Each entry: dict(embeds=[E] | tokens=[t <= T, D], scale=float).  `base`: the base prompt, in the plain AND the rich pass;
+        """Each entry: dict(embeds=[E] | tokens=[t <= T, D] | image=picture (needs load_image_encoder), scale=float).  `base`: the base prompt, in the plain AND the rich pass;
         `regions`: {index of a region prompt in the rich pass's prompt list: entry}; `negative` (default none): the unconditional stream
         then stays text-only, so guidance amplifies the image like the text - the projection of a zero embedding there reproduces
         diffusers' single-image behaviour."""
@@ -199,9 +231,9 @@ class IPAdapterMixin:
         for k, v in (regions or {}).items():
             if isinstance(k, bool) or not isinstance(k, int) or k < 0:
                 raise ValueError(f"{who}: region index must be an integer >= 0, got {k!r}")
-            reg[k] = check_entry(v, f"{who}: regions[{k}]", self.ip_adapter)
-        ip = dict(base=check_entry(base, f"{who}: base", self.ip_adapter) if base is not None else None, regions=reg,
-                  negative=check_entry(negative, f"{who}: negative", self.ip_adapter) if negative is not None else None)
+            reg[k] = check_entry(v, f"{who}: regions[{k}]", self.ip_adapter, self.image_encoder)
+        ip = dict(base=check_entry(base, f"{who}: base", self.ip_adapter, self.image_encoder) if base is not None else None, regions=reg,
+                  negative=check_entry(negative, f"{who}: negative", self.ip_adapter, self.image_encoder) if negative is not None else None)
         self.image_prompts = ip if (ip["base"] or ip["regions"] or ip["negative"]) else None
 
     def clear_image_prompts(self):
@@ -238,8 +270,14 @@ class IPAdapterMixin:
         tokens = torch.zeros(n_prompts, T, D, device=dev)
         counts, scales = [T] * n_prompts, [0.0] * n_prompts
         for s, e in slots.items():
+            if "image" in e and "_embeds" not in e:                  # encoded once per picture, outside the step
+                enc = self.image_encoder
+                if enc is None:
+                    raise ValueError("image prompt given as a picture: the image encoder was unloaded before it was encoded")
+                enc = enc.on(eng.device) if hasattr(enc, "on") else enc
+                e["_embeds"] = enc(e["image"][None]).image_embeds[0].float().cpu()
             if "_tokens" not in e:                                   # projected once per image, outside the step
-                e["_tokens"] = project(ad, e["embeds"], eng.device).cpu() if "embeds" in e else e["tokens"]
+                e["_tokens"] = project(ad, e["_embeds"] if "image" in e else e["embeds"], eng.device).cpu() if "tokens" not in e else e["tokens"]
             t = e["_tokens"]
             tokens[s, :t.shape[0]] = t.to(dev)
             counts[s], scales[s] = int(t.shape[0]), e["scale"]
@@ -247,9 +285,7 @@ class IPAdapterMixin:
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
-def parse_embeds_arg(spec, who="--ip_image_embeds"):
-    """FILE[:TARGET[:SCALE]] -> (file, target, scale): TARGET is base (default), negative or a region number, SCALE a finite number
-    (default 1).  ValueError otherwise."""
+def _parse_spec(spec, who, suffixes, fold_case=False):
     parts = str(spec).split(":")
     if not parts[0] or len(parts) > 3:
         raise ValueError(f"{who}: expected FILE[:TARGET[:SCALE]], got {spec!r}")
@@ -264,9 +300,24 @@ def parse_embeds_arg(spec, who="--ip_image_embeds"):
         raise ValueError(f"{who}: SCALE must be a number, got {parts[2]!r}")
     if not math.isfinite(scale):
         raise ValueError(f"{who}: SCALE must be finite, got {parts[2]!r}")
-    if not os.path.splitext(parts[0])[1] in (".pt", ".npy", ".safetensors"):
-        raise ValueError(f"{who}: the file must be .pt, .npy or .safetensors, got {parts[0]!r}")
+    ext = os.path.splitext(parts[0])[1]
+    if not (ext.lower() if fold_case else ext) in suffixes:
+        raise ValueError(f"{who}: the file must be {', '.join(suffixes[:-1])} or {suffixes[-1]}, got {parts[0]!r}")
     return parts[0], target, scale
+
+
+def parse_embeds_arg(spec, who="--ip_image_embeds"):
+    """FILE[:TARGET[:SCALE]] -> (file, target, scale): TARGET is base (default), negative or a region number, SCALE a finite number
+    (default 1).  ValueError otherwise."""
+    return _parse_spec(spec, who, (".pt", ".npy", ".safetensors"))
+
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".webp", ".bmp")
+
+
+def parse_image_arg(spec, who="--ip_images"):
+    """FILE[:TARGET[:SCALE]] for a picture (.png, .jpg, ...) -> (file, target, scale), parse_embeds_arg's grammar.  ValueError otherwise."""
+    return _parse_spec(spec, who, IMAGE_SUFFIXES, fold_case=True)
 
 
 def read_embeds(path):
@@ -292,10 +343,28 @@ def read_embeds(path):
     return torch.as_tensor(d).float()
 
 
-def image_prompts_from_specs(specs, who="--ip_image_embeds"):
+def image_prompts_from_specs(specs, who="--ip_image_embeds", images=None, who_images="--ip_images"):
     """A list of FILE[:TARGET[:SCALE]] (or of dicts {"file", "target", "scale"} as a --requests line carries them) -> the keyword
-    arguments of set_image_prompts, the files not read yet: dict(base=, regions=, negative=) with entries dict(file=, scale=)."""
+    arguments of set_image_prompts, the files not read yet: dict(base=, regions=, negative=) with entries dict(file=, scale=).
+    `specs` may also be the object form {"embeds": [...], "images": [...]} of a --requests line; `images`: the same list grammar for
+    pictures (parse_image_arg), entries dict(image_file=, scale=).  Two prompts for one target are an error, whichever kind they are."""
+    if isinstance(specs, dict):
+        if set(specs) - {"embeds", "images"}:
+            raise ValueError(f"{who}: expected a list or {{\"embeds\": [...], \"images\": [...]}}, got keys {sorted(specs)}")
+        return image_prompts_from_specs(specs.get("embeds"), who, specs.get("images"), who + ": images")
     out = dict(base=None, regions={}, negative=None)
+    for spec in images or []:
+        if isinstance(spec, dict):
+            if "file" not in spec or set(spec) - {"file", "target", "scale"}:
+                raise ValueError(f"{who_images}: expected {{\"file\": ..., \"target\": ..., \"scale\": ...}}, got {spec!r}")
+            spec = ":".join(str(spec.get(k, d)) for k, d in (("file", ""), ("target", "base"), ("scale", 1.0)))
+        f, target, scale = parse_image_arg(spec, who_images)
+        if (out["regions"].get(target) if isinstance(target, int) else out[target]) is not None:
+            raise ValueError(f"{who_images}: two image prompts for target {target}")
+        if isinstance(target, int):
+            out["regions"][target] = dict(image_file=f, scale=scale)
+        else:
+            out[target] = dict(image_file=f, scale=scale)
     for spec in specs or []:
         if isinstance(spec, dict):
             if "file" not in spec or set(spec) - {"file", "target", "scale"}:
@@ -321,6 +390,8 @@ def apply_specs(model, parsed):
     def entry(e):
         if e is None:
             return None
+        if "image_file" in e:                                         # a picture: the pipeline's image encoder turns it into the embedding
+            return dict(image=e["image_file"], scale=e["scale"])
         t = read_embeds(e["file"])
         while t.dim() > 2 or (t.dim() == 2 and t.shape[0] == 1 and t.numel() == model.ip_adapter["E"]):
             t = t[0]                                                  # a leading batch dimension of one

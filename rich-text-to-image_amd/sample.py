@@ -217,25 +217,33 @@ def check_requests_freeu(path):
 
 
 def check_ip_args(a):
-    """--ip_adapter / --ip_image_embeds and the "image_prompts" keys of a --requests file, checked before any rank starts: the adapter
-    and every embedding file exist, every FILE[:TARGET[:SCALE]] parses, no image prompt without an adapter.  Bad values end the run
-    (SystemExit).  Returns the flag's image prompts (ip_adapter.image_prompts_from_specs) or None."""
+    """--ip_adapter / --image_encoder / --ip_image_embeds / --ip_images and the "image_prompts" keys of a --requests file, checked before
+    any rank starts: the adapter, the encoder directory and every embedding / image file exist, every FILE[:TARGET[:SCALE]] parses, no
+    image prompt without an adapter, no picture without an encoder.  Bad values end the run (SystemExit).  Returns the flags' image
+    prompts (ip_adapter.image_prompts_from_specs) or None."""
     from .ip_adapter import image_prompts_from_specs
 
-    def parse(specs, who):
+    def parse(specs, who, images=None, who_images="--ip_images"):
         try:
-            ip = image_prompts_from_specs(specs, who)
-            for e in [ip["base"], ip["negative"], *ip["regions"].values()]:
-                if e is not None and not os.path.isfile(e["file"]):
-                    raise ValueError(f"{who}: file not found: {e['file']}")
+            ip = image_prompts_from_specs(specs, who, images, who_images)
+            entries = [e for e in [ip["base"], ip["negative"], *ip["regions"].values()] if e is not None]
+            for e in entries:
+                if not os.path.isfile(e.get("file", e.get("image_file"))):
+                    raise ValueError(f"{who_images if 'image_file' in e else who}: file not found: {e.get('file', e.get('image_file'))}")
         except ValueError as e:
             raise SystemExit(f"sample: {e}")
+        pictures = any("image_file" in e for e in entries)
         if not getattr(a, "ip_adapter", None):
-            raise SystemExit(f"sample: {who} needs --ip_adapter")
+            raise SystemExit(f"sample: {who_images if pictures and not specs else who} needs --ip_adapter")
+        if pictures and not getattr(a, "image_encoder", None):
+            raise SystemExit(f"sample: {who_images if images else who} needs --image_encoder")
         return ip
     if getattr(a, "ip_adapter", None) and not os.path.isfile(a.ip_adapter):
         raise SystemExit(f"sample: --ip_adapter: file not found: {a.ip_adapter}")
-    flag = parse(a.ip_image_embeds, "--ip_image_embeds") if getattr(a, "ip_image_embeds", None) else None
+    if getattr(a, "image_encoder", None) and not os.path.isfile(os.path.join(a.image_encoder, "config.json")):
+        raise SystemExit(f"sample: --image_encoder: file not found: {os.path.join(a.image_encoder, 'config.json')}")
+    embeds, images = getattr(a, "ip_image_embeds", None), getattr(a, "ip_images", None)
+    flag = parse(embeds, "--ip_image_embeds", images) if (embeds or images) else None
     if getattr(a, "requests", None):
         with open(a.requests) as f:
             for n, line in enumerate(f, 1):
@@ -245,7 +253,8 @@ def check_ip_args(a):
 
 
 def _request_image_prompts(a, r):
-    """A --requests line's "image_prompts" (a list of FILE[:TARGET[:SCALE]] strings or {"file", "target", "scale"} objects), else the flag's."""
+    """A --requests line's "image_prompts" (a list of FILE[:TARGET[:SCALE]] strings or {"file", "target", "scale"} objects for embeddings,
+    or {"embeds": [...], "images": [...]} with the same lists for embeddings and pictures), else the flags'."""
     if r.get("image_prompts") is None:
         return getattr(a, "image_prompts", None)
     from .ip_adapter import image_prompts_from_specs
@@ -303,6 +312,11 @@ def build_model(a, rank=0, local_rank=0, world=1):
                 m.load_ip_adapter(a.ip_adapter)
             except ValueError as e:
                 raise SystemExit(f"sample: --ip_adapter: {e}")
+        if getattr(a, 'image_encoder', None):    # --image_encoder: read and checked on every rank, on the GPU with the first picture
+            try:
+                m.load_image_encoder(a.image_encoder)
+            except ValueError as e:
+                raise SystemExit(f"sample: --image_encoder: {e}")
         return m
     if world == 1:
         if a.model == 'SD':
@@ -442,6 +456,13 @@ def build_parser():
                    help='with --ip_adapter: a CLIP image embedding (.pt / .npy / .safetensors; a [t, D] matrix = ready image tokens) as the image '
                         'prompt of TARGET = base (default: the whole picture, both passes), negative, or a region number of the rich text '
                         '(that region alone); SCALE defaults to 1')
+    p.add_argument('--image_encoder', type=str, default=None, metavar='DIR',
+                   help='CLIP vision encoder directory in the Hugging Face layout (config.json + model.safetensors / pytorch_model.bin, '
+                        'optionally preprocessor_config.json: IP-Adapter\'s models/image_encoder): turns the pictures of --ip_images into '
+                        'image embeddings on the GPU.  At most 640 tokens per image.  Every rank of --gpus N loads its own')
+    p.add_argument('--ip_images', type=str, nargs='+', default=None, metavar='FILE[:TARGET[:SCALE]]',
+                   help='with --ip_adapter and --image_encoder: a picture (.png / .jpg / .jpeg / .webp / .bmp) as the image prompt of TARGET, '
+                        'as --ip_image_embeds; both flags may be given, two prompts for one TARGET are an error')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
                    help='what the UNet predicts; default: the checkpoint\'s scheduler/scheduler_config.json, else epsilon')
     p.add_argument('--timestep_spacing', type=str, default=None, choices=['leading', 'trailing'],
