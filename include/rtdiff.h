@@ -480,6 +480,15 @@ int rt_op_vit_embed(const float* patch, int ldp, const float* cls, const float* 
  * the PV product, fp32 accumulation.  Anything else is RT_E_INVALID. */
 int rt_op_bidir_attention(const void* q, const void* k, const void* v, int ld, void* out, int ldo, int B, int H, int N, int d, float scale,
                           void* stream);
+/* ---- The Resampler of the IP-Adapter "plus" checkpoints (rich_text_to_image_amd/resampler.py); its linear layers, LayerNorms and GELU are
+ * rt_op_gemm / rt_op_layernorm / rt_op_activation, rt_op_cast_bf16 in front.  Latent attention: 1 <= Nq <= 16 queries q bf16 [B*Nq, ldq]
+ * over 1 <= Nk <= 656 keys / values k, v bf16 [B*Nk, ldkv], head h at column h*d; out bf16 [B*Nq, ldo].  d % 8 == 0, d <= 128, ldq % 8 == 0,
+ * ldkv % 8 == 0, ldo % 4 == 0, q / k / v 16-byte and out 8-byte aligned; anything else is RT_E_INVALID before a launch.  One workgroup per
+ * (image, head), the keys split over its four waves in tiles of 64, the partial (max, sum, O) merged in wave order without atomics:
+ * the same bits on every launch.  Arithmetic as rt_op_bidir_attention: fp32 scores and online softmax in the exp2 domain, P rounded to
+ * bf16 for the PV product, fp32 accumulation, one bf16 rounding of the result. */
+int rt_op_latent_attention(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, int ldo, int B, int H, int Nq, int Nk, int d,
+                           float scale, void* stream);
 /* Head-averaged attention probabilities of ONE batch entry (the `attention_probs_avg` the reference processor returns,
  * attention_processor.py:541-545, reshape_batch_dim_to_heads_and_average): out[N, NK] (=|+=) mean_h softmax(Q_h K_h^T).
  * Q rows q_row0+[0,N), K rows k_row0+[0,NKrows) in the rt_op_attention layouts; NK valid keys (any count: processed in chunks of

@@ -100,7 +100,8 @@ class HipCLIPVisionEncoder:
         self.act = {"quick_gelu": 0, "gelu": 1}[g("hidden_act", "quick_gelu")]
         self.eps, self.S, self.p = g("layer_norm_eps", 1e-5), g("image_size", 224), g("patch_size", 14)
         self.projection_dim = g("projection_dim", 512)
-        self.N = (self.S // self.p) ** 2 + 1
+        self.hidden_size = self.C                                               # what a plus adapter's Resampler takes (hidden_states[-2])
+        self.N =(self.S // self.p) ** 2 + 1
         self.Kp = (3 * self.p * self.p + 7) // 8 * 8
         self.image_mean, self.image_std = tuple(float(x) for x in image_mean), tuple(float(x) for x in image_std)
         if len(self.image_mean) != 3 or len(self.image_std) != 3 or min(self.image_std) <= 0:
@@ -290,7 +291,7 @@ class LazyImageEncoder:
         self.path = os.fspath(path)
         self._host = read_image_encoder(self.path)
         cfg = self._host[1]
-        self.S, self.projection_dim = cfg["image_size"], cfg.get("projection_dim", 512)
+        self.S, self.projection_dim, self.hidden_size = cfg["image_size"], cfg.get("projection_dim", 512), cfg["hidden_size"]
         self._enc = {}
 
     def on(self, device):

@@ -386,6 +386,9 @@ void launch_vit_embed(const float* patch, int ldp, const float* cls, const float
 // unmasked self-attention, operands as launch_causal_attention; 1 <= N <= 640, d % 8 == 0, d <= 128
 void launch_bidir_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ld, bf16_t* out, int ldo, int B, int H, int N, int d,
                             float scale, hipStream_t st);
+// the Resampler's latent attention (resampler.hip): 1 <= Nq <= 16 queries [B Nq, ldq] over 1 <= Nk <= 656 keys / values [B Nk, ldkv]
+void launch_latent_attention(const bf16_t* q, int ldq, const bf16_t* k, const bf16_t* v, int ldkv, bf16_t* out, int ldo, int B, int H, int Nq,
+                             int Nk, int d, float scale, hipStream_t st);
 
 // weight packing (device side): strided gather fp32/fp16/bf16 -> bf16 (or f32) with scale.
 //   dst (r, c) <- scale * src[ srow(r)*s_r + (c / c_inner)*s_co + (c % c_inner)*s_ci ]   (0 where invalid)

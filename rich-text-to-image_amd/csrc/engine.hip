@@ -2177,6 +2177,10 @@ int rt_op_bidir_attention(const void* q, const void* k, const void* v, int ld, v
                           void* stream) {
     OP_TRY({ launch_bidir_attention((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ld, (bf16_t*)out, ldo, B, H, N, d, scale, (hipStream_t)stream); })
 }
+int rt_op_latent_attention(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, int ldo, int B, int H, int Nq, int Nk, int d,
+                           float scale, void* stream) {
+    OP_TRY({ launch_latent_attention((const bf16_t*)q, ldq, (const bf16_t*)k, (const bf16_t*)v, ldkv, (bf16_t*)out, ldo, B, H, Nq, Nk, d, scale, (hipStream_t)stream); })
+}
 int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev, unsigned int* words_dev, void* stream) {
     OP_TRY({
         RT_REQUIRE(out_dev && step >= 0 && h >= 1 && w >= 1 && (long long)h * w <= (1ll << 30), "rt_op_step_noise: bad arguments");

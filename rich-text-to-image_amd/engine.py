@@ -92,6 +92,7 @@ _SYMBOLS = [
     "rt_set_image_prompts", "rt_op_ip_attention",
     "rt_unet_forward_trace", "rt_trace_module_count", "rt_trace_module_info",
     "rt_op_patchify", "rt_op_vit_embed", "rt_op_bidir_attention",
+    "rt_op_latent_attention",
 ]
 
 

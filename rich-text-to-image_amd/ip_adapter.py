@@ -8,8 +8,11 @@ can give every region its own reference image, one to the base prompt, or none.
 An entry may also be a picture (`image=`): `load_image_encoder` puts a CLIP vision encoder (clip_vision_encoder.py) on the pipeline, which
 encodes the picture once, outside the step.  Without one, image embeddings come from the caller, as prompt_embeds do for SD-2.x.
 
-Not here: the Resampler projection of the "plus" checkpoints (the encoder's hidden_states[-2] can be fed to one by the caller and its
-ready tokens passed as `tokens=`), FaceID, several adapters at once, per-layer scales."""
+A "plus" checkpoint carries a Resampler in place of the linear projection (resampler.py): its input is the encoder's penultimate hidden
+states, not the pooled embedding, so an entry is then a picture (`image=`), hidden states from the caller (`hidden=[N, E]`) or ready
+tokens; `embeds=` is refused.
+
+Not here: FaceID, several adapters at once, per-layer scales, diffusers' renamed IPAdapterPlusImageProjection keys."""
 import ctypes as C
 import math
 import os
@@ -59,12 +62,14 @@ def _flatten(sd):
     return flat
 
 
-def load_ip_adapter(path_or_state_dict, config):
+def load_ip_adapter(path_or_state_dict, config, dim_head=64):
     """An IP-Adapter checkpoint for the UNet `config` -> dict(weights = {"<attn2>.to_k_ip.weight" / ".to_v_ip.weight": tensor} under the
     engine's names, image_proj = {"proj.weight", "proj.bias", "norm.weight", "norm.bias"}, T = image tokens per image, D, E).
     Reads the original layout - a .safetensors / .bin file or a dict with flat keys image_proj.* / ip_adapter.{2 k + 1}.to_k_ip.weight, or
-    the nested dict - and diffusers' names (<attn2>.processor.to_k_ip.0.weight).  ValueError naming the key for a missing or left-over
-    key, a shape that does not match the UNet, or a Resampler ("plus") projection."""
+    the nested dict - and diffusers' names (<attn2>.processor.to_k_ip.0.weight).  A "plus" checkpoint (image_proj.latents / proj_in /
+    layers.* / proj_out / norm_out: a Resampler, resampler.py) gives the same dict with an empty image_proj, E = the Resampler's
+    embedding_dim and resampler = resampler.check_resampler's result (`dim_head`: the one dimension its shapes do not tell).  ValueError
+    naming the key for a missing or left-over key, a shape that does not match the UNet, or Resampler keys next to proj.*."""
     sd = _read_file(path_or_state_dict) if isinstance(path_or_state_dict, (str, os.PathLike)) else path_or_state_dict
     sd = _flatten(dict(sd))
     D = int(config["cross_attention_dim"])
@@ -74,20 +79,32 @@ def load_ip_adapter(path_or_state_dict, config):
             proj[k[len("image_proj."):]] = v
         else:
             rest[k] = v
-    for k in proj:
-        if k not in ("proj.weight", "proj.bias", "norm.weight", "norm.bias"):
-            kind = "a Resampler (\"plus\") projection: pass its ready tokens as tokens=" if k.split(".")[0] in ("latents", "proj_in", "proj_out", "layers", "norm_out") else "unknown key"
-            raise ValueError(f"IP-Adapter: image_proj.{k}: {kind}")
-    for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias"):
-        if k not in proj:
-            raise ValueError(f"IP-Adapter: missing key image_proj.{k}")
-    rows, E = (int(s) for s in proj["proj.weight"].shape)
-    if rows % D != 0 or not 1 <= rows // D <= MAX_TOKENS:
-        raise ValueError(f"IP-Adapter: image_proj.proj.weight has {rows} rows: expected T * {D} (cross_attention_dim) with T in 1 .. {MAX_TOKENS}")
-    T = rows // D
-    for k, shape in (("proj.bias", (rows,)), ("norm.weight", (D,)), ("norm.bias", (D,))):
-        if tuple(proj[k].shape) != shape:
-            raise ValueError(f"IP-Adapter: image_proj.{k} has shape {tuple(proj[k].shape)}, expected {shape}")
+    linear_keys = ("proj.weight", "proj.bias", "norm.weight", "norm.bias")
+    plus_keys = [k for k in proj if k.split(".")[0] in ("latents", "proj_in", "proj_out", "layers", "norm_out")]
+    resampler = None
+    if plus_keys and not any(k in proj for k in linear_keys):
+        from .resampler import check_resampler
+        resampler = check_resampler(proj, dim_head)
+        if resampler["D"] != D:
+            raise ValueError(f"IP-Adapter: image_proj.proj_out.weight has {resampler['D']} rows, the UNet's cross_attention_dim is {D}")
+        T, E = resampler["T"], resampler["E"]
+        proj = {}
+    else:
+        for k in proj:
+            if k not in linear_keys:
+                kind = ("a Resampler (\"plus\") key next to the linear projection's image_proj.proj.* / norm.*: a checkpoint holds one projection"
+                        if k in plus_keys else "unknown key")
+                raise ValueError(f"IP-Adapter: image_proj.{k}: {kind}")
+        for k in linear_keys:
+            if k not in proj:
+                raise ValueError(f"IP-Adapter: missing key image_proj.{k}")
+        rows, E = (int(s) for s in proj["proj.weight"].shape)
+        if rows % D != 0 or not 1 <= rows // D <= MAX_TOKENS:
+            raise ValueError(f"IP-Adapter: image_proj.proj.weight has {rows} rows: expected T * {D} (cross_attention_dim) with T in 1 .. {MAX_TOKENS}")
+        T = rows // D
+        for k, shape in (("proj.bias", (rows,)), ("norm.weight", (D,)), ("norm.bias", (D,))):
+            if tuple(proj[k].shape) != shape:
+                raise ValueError(f"IP-Adapter: image_proj.{k} has shape {tuple(proj[k].shape)}, expected {shape}")
     weights = {}
     for k, (name, Cq) in enumerate(attn2_names(config)):
         for w in ("to_k_ip", "to_v_ip"):
@@ -101,7 +118,21 @@ def load_ip_adapter(path_or_state_dict, config):
             weights[f"{name}.{w}.weight"] = t
     if rest:
         raise ValueError(f"IP-Adapter: left-over key {sorted(rest)[0]} ({len(rest)} in all): the checkpoint does not belong to this UNet")
-    return dict(weights=weights, image_proj={k: v.detach().float() for k, v in proj.items()}, T=T, D=D, E=E)
+    out = dict(weights=weights, image_proj={k: v.detach().float() for k, v in proj.items()}, T=T, D=D, E=E)
+    if resampler is not None:
+        out["resampler"] = resampler
+    return out
+
+
+def resample(adapter, hidden, device=0):
+    """The Resampler of a plus adapter on ONE image's hidden states [N, E] -> tokens [T, D] fp32 on the GPU (resampler.HipResampler; its
+    weights go to the device with the first call).  Once per image, outside the step."""
+    import torch
+    from .resampler import LazyResampler
+    lazy = adapter.get("_resampler")
+    if lazy is None:
+        lazy = adapter["_resampler"] = LazyResampler(adapter["resampler"])
+    return lazy.on(device)(torch.as_tensor(hidden).detach().float()[None])[0]
 
 
 def project(adapter, image_embeds, device=0):
@@ -138,9 +169,16 @@ def project(adapter, image_embeds, device=0):
 
 def check_entry(entry, who, adapter, encoder=None):
     """dict(embeds=[E] | tokens=[t <= T, D] | image=<path | PIL image | [H, W, 3] uint8>, scale=float) -> a checked copy (tensors on the
-    CPU, fp32; an image as the uint8 crop the encoder takes); ValueError otherwise.  `encoder`: the pipeline's image encoder or None."""
+    CPU, fp32; an image as the uint8 crop the encoder takes); ValueError otherwise.  `encoder`: the pipeline's image encoder or None.
+    Under a plus adapter (adapter["resampler"]) an entry may be hidden=[N, E] - the encoder's penultimate hidden states -, and embeds= is
+    refused: the pooled embedding is not the Resampler's input."""
     import torch
-    if not isinstance(entry, dict) or sum(k in entry for k in ("embeds", "tokens", "image")) != 1 or set(entry) - {"embeds", "tokens", "image", "scale"}:
+    plus = adapter.get("resampler") is not None
+    if plus and isinstance(entry, dict) and sum(k in entry for k in ("embeds", "tokens", "image", "hidden")) == 1 and not set(entry) - {"embeds", "tokens", "image", "hidden", "scale"}:
+        if "embeds" in entry:
+            raise ValueError(f"{who}: embeds= is the pooled image embedding; the loaded adapter is a plus adapter, whose Resampler takes the encoder's "
+                             f"penultimate hidden states: pass image=, hidden=[N, {adapter['E']}] or tokens=")
+    elif not isinstance(entry, dict) or sum(k in entry for k in ("embeds", "tokens", "image")) != 1 or set(entry) - {"embeds", "tokens", "image", "scale"}:
         raise ValueError(f"{who}: expected dict(embeds=[E], tokens=[t, D] or image=picture, scale=number), got {entry!r}" if not isinstance(entry, dict)
                          else f"{who}: expected exactly one of embeds= / tokens= / image= and an optional scale=, got keys {sorted(entry)}")
     try:
@@ -153,7 +191,9 @@ def check_entry(entry, who, adapter, encoder=None):
     if "image" in entry:
         if encoder is None:
             raise ValueError(f"{who}: image= needs an image encoder: none is loaded on this pipeline (load_image_encoder / --image_encoder)")
-        if encoder.projection_dim != adapter["E"]:
+        if plus and getattr(encoder, "hidden_size", None) != adapter["E"]:
+            raise ValueError(f"{who}: the image encoder's hidden_size is {getattr(encoder, 'hidden_size', None)}, the plus adapter's Resampler takes {adapter['E']}")
+        if not plus and encoder.projection_dim != adapter["E"]:
             raise ValueError(f"{who}: the image encoder's projection_dim is {encoder.projection_dim}, the adapter's projection takes {adapter['E']}")
         from .clip_vision_encoder import preprocess
         try:
@@ -166,12 +206,18 @@ def check_entry(entry, who, adapter, encoder=None):
         if e.numel() != adapter["E"]:
             raise ValueError(f"{who}: embeds of {e.numel()} values: the adapter's projection takes {adapter['E']}")
         out["embeds"] = e
+    elif "hidden" in entry:
+        from .resampler import MAX_KEYS
+        t = torch.as_tensor(entry["hidden"]).detach().float().cpu()
+        if t.dim() != 2 or t.shape[0] < 1 or t.shape[0] + adapter["T"] > MAX_KEYS or t.shape[1] != adapter["E"]:
+            raise ValueError(f"{who}: hidden must be [N <= {MAX_KEYS - adapter['T']}, {adapter['E']}], got {tuple(t.shape)}")
+        out["hidden"] = t
     else:
         t = torch.as_tensor(entry["tokens"]).detach().float().cpu()
         if t.dim() != 2 or not 1 <= t.shape[0] <= adapter["T"] or t.shape[1] != adapter["D"]:
             raise ValueError(f"{who}: tokens must be [t <= {adapter['T']}, {adapter['D']}], got {tuple(t.shape)}")
         out["tokens"] = t
-    if not bool(torch.isfinite(out.get("embeds", out.get("tokens"))).all()):
+    if not bool(torch.isfinite(next(out[k] for k in ("embeds", "hidden", "tokens") if k in out)).all()):
         raise ValueError(f"{who}: non-finite values")
     return out
 
@@ -187,12 +233,12 @@ class IPAdapterMixin:
     def _ip_unet(self):
         return getattr(self, "unet", self)
 
-    def load_ip_adapter(self, path_or_state_dict):
-        """Engines are built with ip_tokens = T of this adapter from now on (existing ones are rebuilt on their next use).  On a rank
+    def load_ip_adapter(self, path_or_state_dict, dim_head=64):
+        """`dim_head`: the head dim of a plus checkpoint's Resampler (its shapes do not tell it; 64 in every published one).  Engines are built with ip_tokens = T of this adapter from now on (existing ones are rebuilt on their next use).  On a rank
         whose UNet weights arrive by broadcast, load (or unload) BEFORE the first engine exists: afterwards the engines hold the only
         copy of the weights and install_ip_adapter refuses (RuntimeError)."""
         u = self._ip_unet()
-        ad = load_ip_adapter(path_or_state_dict, u.config_dict)
+        ad = load_ip_adapter(path_or_state_dict, u.config_dict, dim_head)
         u.install_ip_adapter(ad)                                     # (may refuse: nothing has changed then)
         self.ip_adapter, self.image_prompts = ad, None
         return self
@@ -218,7 +264,8 @@ class IPAdapterMixin:
         self.image_encoder = None
 
     def set_image_prompts(self, base=None, regions=None, negative=None):
-        """Each entry: dict(embeds=[E] | tokens=[t <= T, D] | image=picture (needs load_image_encoder), scale=float).  `base`: the base prompt, in the plain AND the rich pass;
+        """Each entry: dict(embeds=[E] | tokens=[t <= T, D] | image=picture (needs load_image_encoder), scale=float); under a plus adapter
+        dict(image= | hidden=[N, E] | tokens=, scale=).  `base`: the base prompt, in the plain AND the rich pass;
         `regions`: {index of a region prompt in the rich pass's prompt list: entry}; `negative` (default none): the unconditional stream
         then stays text-only, so guidance amplifies the image like the text - the projection of a zero embedding there reproduces
         diffusers' single-image behaviour."""
@@ -270,7 +317,16 @@ class IPAdapterMixin:
         tokens = torch.zeros(n_prompts, T, D, device=dev)
         counts, scales = [T] * n_prompts, [0.0] * n_prompts
         for s, e in slots.items():
-            if "image" in e and "_embeds" not in e:                  # encoded once per picture, outside the step
+            if ad.get("resampler") is not None:                      # a plus adapter: penultimate hidden states -> Resampler -> tokens
+                if "image" in e and "_hidden" not in e:              # encoded once per picture, outside the step
+                    enc = self.image_encoder
+                    if enc is None:
+                        raise ValueError("image prompt given as a picture: the image encoder was unloaded before it was encoded")
+                    enc = enc.on(eng.device) if hasattr(enc, "on") else enc
+                    e["_hidden"] = enc(e["image"][None], output_hidden_states=True).hidden_states[-2][0].float().cpu()
+                if "_tokens" not in e:                               # resampled once per image, outside the step
+                    e["_tokens"] = e["tokens"] if "tokens" in e else resample(ad, e["_hidden"] if "image" in e else e["hidden"], eng.device).cpu()
+            if "image" in e and "_embeds" not in e and "_tokens" not in e:   # encoded once per picture, outside the step
                 enc = self.image_encoder
                 if enc is None:
                     raise ValueError("image prompt given as a picture: the image encoder was unloaded before it was encoded")
@@ -393,9 +449,13 @@ def apply_specs(model, parsed):
         if "image_file" in e:                                         # a picture: the pipeline's image encoder turns it into the embedding
             return dict(image=e["image_file"], scale=e["scale"])
         t = read_embeds(e["file"])
-        while t.dim() > 2 or (t.dim() == 2 and t.shape[0] == 1 and t.numel() == model.ip_adapter["E"]):
+        while t.dim() > 2 or (t.dim() == 2 and t.shape[0] == 1 and t.numel() == model.ip_adapter["E"] and model.ip_adapter.get("resampler") is None):
             t = t[0]                                                  # a leading batch dimension of one
-        # a [t, D] matrix = ready tokens (a Resampler's output, say); anything else = one image embedding
+        # a [t, D] matrix = ready tokens (a Resampler's output, say); anything else = one image embedding - or, under a plus adapter, any
+        # other matrix = the encoder's hidden states [N, E]
+        ad = model.ip_adapter
+        if t.dim() == 2 and ad.get("resampler") is not None and not (t.shape[0] <= ad["T"] and t.shape[1] == ad["D"]):
+            return dict(hidden=t, scale=e["scale"])
         return dict(tokens=t, scale=e["scale"]) if t.dim() == 2 else dict(embeds=t, scale=e["scale"])
     if parsed is None or not (parsed["base"] or parsed["regions"] or parsed["negative"]):
         model.clear_image_prompts()

@@ -1,6 +1,6 @@
 """Writes a randomly initialised CLIP vision encoder directory in the Hugging Face layout (config.json, model.safetensors,
 preprocessor_config.json) - what `--image_encoder` / `load_image_encoder` read - and, with --adapter, a synthetic IP-Adapter checkpoint
-for the tiny SD / XL UNet configs whose projection takes that encoder's embedding.  For trying the image-prompt path where no real
+for the tiny SD / XL UNet configs whose projection takes that encoder's embedding (--plus: whose Resampler takes its hidden states).  For trying the image-prompt path where no real
 checkpoint is at hand; the pictures that come out mean nothing.
 
   python tools/make_image_encoder.py OUT_DIR [--hidden 160 --heads 2 --layers 3 --mlp 320 --image 56 --patch 14 --proj 48 --act quick_gelu]"""
@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--proj", type=int, default=48); ap.add_argument("--act", default="quick_gelu", choices=["quick_gelu", "gelu"])
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--adapter", default=None, metavar="FILE", help="also write a synthetic IP-Adapter (.bin) for --unet whose E is --proj")
+    ap.add_argument("--plus", action="store_true", help="with --adapter: a \"plus\" adapter - a Resampler over the encoder's hidden states (E = --hidden, "
+                                                        "dim_head 64, 2 heads, 2 layers, 4 tokens) in place of the linear projection")
     ap.add_argument("--unet", default="tiny_sd", choices=["tiny_sd", "tiny_xl"])
     a = ap.parse_args()
     from rich_text_to_image_amd.clip_vision_encoder import CLIP_MEAN, CLIP_STD, check_config
@@ -59,9 +61,14 @@ def main():
         import ip_adapter_ref as R
         from oracle.unet import TINY_SD_CONFIG, TINY_XL_CONFIG, random_state_dict as unet_sd
         ucfg = TINY_SD_CONFIG if a.unet == "tiny_sd" else TINY_XL_CONFIG
-        ck, _ = R.synthetic_checkpoint(ucfg, unet_sd(ucfg, seed=3), T=4, E=a.proj)
+        if a.plus:
+            import resampler_ref as RS
+            ck = RS.synthetic_plus_checkpoint(ucfg, unet_sd(ucfg, seed=3), E=a.hidden, dim=64, dim_head=64, heads=2, T=4, depth=2)[0]
+        else:
+            ck, _ = R.synthetic_checkpoint(ucfg, unet_sd(ucfg, seed=3), T=4, E=a.proj)
         torch.save(ck, a.adapter)
-        print(f"wrote {a.adapter}: synthetic IP-Adapter for the {a.unet} UNet, T = 4, E = {a.proj}")
+        print(f"wrote {a.adapter}: synthetic IP-Adapter for the {a.unet} UNet, T = 4, E = {a.hidden if a.plus else a.proj}"
+              + (" (plus: a Resampler, dim_head 64)" if a.plus else ""))
 
 
 if __name__ == "__main__":
