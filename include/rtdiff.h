@@ -68,6 +68,12 @@ typedef struct rt_config {
                                          * state_dict layout - or 1 .. 16: every attn2 registers <module>.to_k_ip.weight / .to_v_ip.weight
                                          * [heads d, cross_attention_dim] (packed like to_k / to_v, in the same arena) and keeps two more caches of
                                          * 16 rows per prompt slot */
+    int controlnet;                     /* 1: the engine holds one ControlNet (rt_set_control_hint / rt_set_control_scales): a second copy of the
+                                         * UNet's encoder registered under the prefix "controlnet." in diffusers' ControlNetModel layout, in the same
+                                         * arena behind the UNet's own weights.  0 - what a zero-initialised struct gets - : nothing new is
+                                         * registered, allocated or launched and the weight table is the reference's state_dict layout */
+    int control_hint_channels;          /* channels of the hint image (0 = 3) */
+    int control_embed_channels[4];      /* channels of the hint embedder's four stages (all 0 = 16, 32, 96, 256); each a multiple of 8 */
 } rt_config;
 
 typedef struct rt_engine rt_engine;
@@ -113,6 +119,27 @@ int rt_set_prompts_keys(rt_engine* e, const float* prompt_embeds, const int* key
  * reset every scale to 0 (the slots change meaning); every other call leaves the state alone.  n_prompts above the prompts set, a count
  * out of range, a non-finite scale or an engine with ip_tokens == 0: RT_E_INVALID, the state is unchanged and the engine stays usable. */
 int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts_host, const float* scales_host, int n_prompts);
+/* ControlNet (no counterpart in the reference; diffusers' ControlNetModel, restated in tests/controlnet_ref.py - parity with diffusers is
+ * unpinned).  Engines with rt_config.controlnet == 1 only; on any other engine the three calls are RT_E_INVALID.
+ * rt_set_control_hint: hint [hint_channels, 8 h, 8 w] f32 on the device, values as the checkpoint expects (usually 0 .. 1), h x w = the latent
+ *   grid of the forwards it will steer (at most the plan's).  Runs controlnet_cond_embedding once - conv_in, blocks.0 .. 5 (3x3, pad 1; the odd
+ *   ones stride 2), SiLU behind each, conv_out without - in fp32 (csrc/control.hip, control_conv3_kernel), and caches the result,
+ *   [h w, block_out_channels[0]], which a step adds to controlnet.conv_in(x) of every controlled stream.  Once per image, outside the step:
+ *   it allocates and synchronises.  hint == NULL clears the hint.  The hint survives every other call.  A forward or step whose latent grid
+ *   differs from the hint's while a stream is controlled is RT_E_INVALID before anything is launched - never a resize.
+ * rt_control_embedding_read: copies the cached embedding to dst_dev as f32 [h w, C0] (dst_dev may be NULL: sizes only; rows = 0: no hint).
+ * rt_set_control_scales: one finite scale per prompt slot of rt_set_prompts (slots n_prompts .. are 0); 0 = a stream that runs that prompt
+ *   is not controlled.  rt_set_prompts / rt_set_prompts_keys reset every scale to 0; the hint stays.  A bad argument leaves the state alone.
+ * With a hint set, every stream b of a forward whose slot has a scale != 0 is controlled: the control copy runs for those streams only, in
+ * stream order, on the stream's own latents, input scale, timestep and prompt (its own key count) - plain softmax, its own Q / K, no
+ * injection, no token-map store, no image-prompt term, no FreeU - behind the main UNet's mid block; each of its skips and its mid output
+ * goes through its 1x1 zero convolution into fp32 scratch (released before the next), and ONE launch per residual computes
+ *   skip[b] <- f16(fmaf(scale[slot(b)], r[b'], float(skip[b])))
+ * in place on the main UNet's fp16 skip / mid output (the skip's other reader, the down path, is behind it in stream order).  A stream
+ * with scale 0, and a call with no hint or all scales 0, launches nothing new and keeps the bits of an engine without a ControlNet. */
+int rt_set_control_hint(rt_engine* e, const float* hint, int h, int w);
+int rt_control_embedding_read(rt_engine* e, float* dst_dev, int* rows, int* cols);
+int rt_set_control_scales(rt_engine* e, const float* scales_host, int n_prompts);
 /* region masks (model.masks, rd.py:97,119-128 / xl.py:775,810-821): [R,4,h,w] f32 */
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
 /* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables.
@@ -228,7 +255,9 @@ enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_
        RT_PROF_XATTN_FUSED = 5 /* to_q + 77-key cross-attention as one launch (gemm16 EPI_XATTN): FLOPs = 2*M*HD*C + 4*B*H*N*77*d */,
        RT_PROF_XBLOCK = 6 /* the whole cross-attention block as one launch (xblock.hip): FLOPs = 4*M*HD*C + 4*B*H*N*77*d */,
        RT_PROF_IP_ATTN = 7 /* the image-prompt term of attn2 (ipattn.hip; rt_set_image_prompts): FLOPs = 4*H*N*d*(image tokens of the launch's
-                            * streams), bytes = Q read once + O read and written once for the streams that carry an image */ };
+                            * streams), bytes = Q read once + O read and written once for the streams that carry an image */,
+       RT_PROF_CONTROL_ADD = 8 /* the ControlNet residual add (control.hip; rt_set_control_scales), priced in bytes: the fp32 residual read once, the
+                                * fp16 skip read and written once, for the controlled streams */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
 int rt_profile_read(rt_engine* e, int kernel_class, int* count, double* total_ms, double* total_flops);
 /* as rt_profile_read, plus the ALGORITHMIC HBM bytes of the launches (attention store: the fp32 accumulator read + written once and the
@@ -245,7 +274,11 @@ int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float tim
  * bit - which, when the module `module_name` has finished, copies the trunk tensor that module leaves (fp16 NHWC) to trace_out_dev as
  * fp32 NCHW [B, C, h', w'].  Traceable modules carry the reference's module names: "conv_in", every "...resnets.j", every
  * "...attentions.j" (the whole Transformer2DModel, residual included), every "...downsamplers.0.conv" / "...upsamplers.0.conv" and
- * "conv_out" (whose tensor is `out` itself).  rt_trace_module_info lists them in execution order with their channel count C and the
+ * "conv_out" (whose tensor is `out` itself).  Engines with a ControlNet also list, behind "mid_block.resnets.1" where they run:
+ * "controlnet.hint_embedding" (the cached embedding, ONE entry [1, C0, h, w]), "controlnet.<module>" for the control copy's conv_in (hint
+ * embedding added), resnets, attentions and downsamplers (the CONTROLLED streams of the call in stream order, [Bc, C, h', w'];
+ * RT_E_INVALID when the call controls none), and "controlnet.skip.{k}" / "controlnet.mid": the main UNet's k-th skip / mid output as the
+ * up path consumes it, after the add, all B streams.  rt_trace_module_info lists them in execution order with their channel count C and the
  * power of two their grid is smaller than the latent grid by (h' = h >> downshift); it needs no device.  An unknown name or
  * trace_cap_floats < B C h' w' is an error (rt_last_error) before anything is launched or written.  The copy is one plain kernel
  * between the module and its successor; a traced forward is not meant for hipGraph capture. */
@@ -445,6 +478,14 @@ int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream);
  * untouched).  C1, C2 multiples of 8, pointers 16-byte aligned, b, s finite and > 0 (RT_E_INVALID); the filter needs 2 <= H, W <= 2048
  * (RT_E_UNSUPPORTED). */
 int rt_op_freeu(void* hidden_f16, int C1, void* skip_f16, int C2, int B, int H, int W, float b, float s, void* stream);
+/* The ControlNet residual add alone (csrc/control.hip), in place on skip_f16: for entry i < n, with b = stream_host[i] (distinct, in [0, B)),
+ *   skip[b, t, c] <- f16(fmaf(scale_host[i], r[i, t, c], float(skip[b, t, c])))        t < HW, c < C: one fp32 rounding, then one to fp16
+ * skip fp16, stream b at skip + b skip_stride elements, token t at + t lds; r fp32, entry i at r + i r_stride, token t at + t ldr.  C % 8 == 0,
+ * lds >= C and % 8 == 0, ldr >= C and % 4 == 0, strides and pointers 16-byte multiples, scales finite (RT_E_INVALID otherwise, nothing
+ * launched).  Streams that are not named, and every byte outside the [HW, C] windows, are never addressed.  No atomics; an entry is a
+ * function of itself alone. */
+int rt_op_control_add(void* skip_f16, long long skip_stride, int lds, const float* r, long long r_stride, int ldr, const int* stream_host,
+                      const float* scale_host, int n, int B, int HW, int C, void* stream);
 /* The noise field a stochastic step with (seed, step index) adds on an h x w latent grid, from the same device function as the step
  * epilogue: out_dev [4, h, w] f32 normals; words_dev [h*w, 4] the raw Philox words of every pixel, or NULL. */
 int rt_op_step_noise(unsigned long long seed, int step, int h, int w, float* out_dev /* [4,h,w] */, unsigned int* words_dev /* [h*w,4] or NULL */,

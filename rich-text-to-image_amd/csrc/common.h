@@ -362,6 +362,12 @@ void launch_cast_f16_bf16(const f16_t* x, bf16_t* out, size_t n, hipStream_t st)
 // and skip [B, HW, C2] - the four lowest frequency bins {-1, 0}^2 of every (stream, channel) map scaled by s.  A null pointer, b == 1
 // or s == 1 launches nothing for that half; C1, C2 % 8 == 0, 16-byte aligned; the filter needs H, W >= 2 (RT_E_UNSUPPORTED below)
 void launch_freeu(f16_t* hidden, int C1, f16_t* skip, int C2, int B, int H, int W, float b, float s, hipStream_t st);
+// control.hip (ControlNet): the residual add of a step, the hint embedder's fp32 convolution and the hint's layout change
+void launch_control_add(f16_t* skip, size_t skip_stride, int lds, const float* r, size_t r_stride, int ldr, const int* /*host*/ stream,
+                        const float* /*host*/ scale, int n, int B, int HW, int C, hipStream_t st);
+void launch_control_conv3(const float* in, const float* w, const float* bias, float* out, f16_t* out16, int Hin, int Win, int CinP, int Cout,
+                          int stride, int silu, hipStream_t st);      // fp32 3x3 convolution (pad 1) of one NHWC image, optional SiLU, optional fp16 copy
+void launch_control_hint(const float* hint, float* out, int Ch, int CP, size_t HW, hipStream_t st);            // [Ch, HW] f32 -> [HW, CP] f32, pad channels zero
 void launch_cast_f32_bf16(const float* x, bf16_t* out, size_t n, hipStream_t st, bf16_t* out_lo = nullptr);
 // out[b][n] (+)= sum_k act(a[b][k]) * W[n][k] + bias[n];  B <= 8
 void launch_small_linear(const float* a, int lda, const bf16_t* W, int ldw, const float* bias, float* out, int ldo,

@@ -107,6 +107,31 @@ struct TransformerP {
 struct DownP { std::vector<ResnetP> res; std::vector<TransformerP> attn; bool has_attn = false, has_down = false; MatW down; int C = 0; };
 struct UpP { std::vector<ResnetP> res; std::vector<TransformerP> attn; bool has_attn = false, has_up = false; MatW up; int C = 0; };
 
+// ControlNet (rt_config.controlnet): a second copy of the encoder under the prefix "controlnet." - built by the same mk_* builders -, the
+// hint embedder in front and one 1x1 zero convolution per skip / for the mid block behind.  Its own time_emb_proj table and addition
+// embeddings, so that an engine without an active hint computes nothing for it.
+struct ControlP {
+    MatW conv_in, t1, t2, a1, a2;
+    std::vector<DownP> down;
+    ResnetP mid_r0, mid_r1;
+    TransformerP mid_t;
+    std::vector<MatW> zero;      // controlnet_down_blocks.{k}: one per skip, in the order unet_forward pushes them
+    MatW zero_mid;               // controlnet_mid_block
+    struct ConvF { float* w = nullptr; float* b = nullptr; int N = 0, CinP = 0; };      // fp32 [N][tap][CinP] + bias
+    ConvF ce_in, ce_blocks[6], ce_out;     // controlnet_cond_embedding: kept in fp32 (control_conv3_kernel)
+    int ce_ch[4] = {0, 0, 0, 0}, hint_ch = 3;
+    std::vector<TembEntry> temb_tab;
+    int temb_total = 0;
+    TembEntry* temb_tab_dev = nullptr;
+    float* aug_emb = nullptr;    // [maxP, temb_dim]
+    // per image: the cached hint embedding [h w, C0] (fp32 as rt_control_embedding_read returns it; fp16 = the same accumulators rounded once,
+    // the residual operand of controlnet.conv_in's epilogue) and the scale of every prompt slot
+    float* emb_f32 = nullptr; f16_t* emb_f16 = nullptr;
+    bool has_hint = false;
+    int hint_h = 0, hint_w = 0;
+    std::vector<float> scale;
+};
+
 struct WeightSlot {
     std::string name;
     std::vector<int64_t> shape;
@@ -133,6 +158,7 @@ struct FwdIn {
     int prompt[RT_MAXB], fontsize[RT_MAXB], qk_src[RT_MAXB], res_src[RT_MAXB];
     float* eps_out = nullptr;    // [B, HW, 4] fp32
     int store_stream = -1;       // stream whose head-averaged attention maps are recorded (plain pass: the conditional one)
+    bool control = false;        // the forward of the ControlNet's encoder copy (control_forward): no image-prompt term
 };
 
 extern int g_store_own_stats;
@@ -359,6 +385,8 @@ struct rt_engine {
     std::vector<UpP> up;
     ResnetP mid_r0, mid_r1;
     TransformerP mid_t;
+    ControlP ctl;                // rt_config.controlnet
+    bool building_control = false;
     int temb_dim = 0;
     // every resnet's time_emb_proj(silu(emb)) is computed by ONE launch at the start of a forward (launch_temb_all)
     std::vector<TembEntry> temb_tab;
@@ -477,6 +505,18 @@ struct rt_engine {
         add_slot(name + ".bias", {Cout}, pk_vec(m.b, Cout));
         return m;
     }
+    // the hint embedder's convolutions: the same slot layout as mk_conv3, packed as fp32
+    ControlP::ConvF mk_conv3_f32(const std::string& name, int Cin, int Cout) {
+        const int CinP = (Cin + 7) & ~7;
+        ControlP::ConvF m; m.N = Cout; m.CinP = CinP;
+        m.w = (float*)arena.alloc((size_t)Cout * 9 * CinP * 4);
+        PackArgs p{}; p.dst = m.w; p.dst_f32 = 1; p.rows = Cout; p.cols = 9 * CinP; p.ld_dst = 9 * CinP; p.row_map = PACK_ROWS_ID;
+        p.c_inner = CinP; p.ci_valid = Cin; p.s_r = (long)Cin * 9; p.s_co = 1; p.s_ci = 9; p.scale = 1.f;
+        add_slot(name + ".weight", {Cout, Cin, 3, 3}, p);
+        m.b = (float*)arena.alloc((size_t)Cout * 4);
+        add_slot(name + ".bias", {Cout}, pk_vec(m.b, Cout));
+        return m;
+    }
     ResnetP mk_resnet(const std::string& name, int cin, int cout) {
         RT_REQUIRE(cin % 8 == 0 && cout % 8 == 0, "resnet: channel counts must be multiples of 8");
         ResnetP r; r.name = name; r.cin = cin; r.cout = cout;
@@ -516,7 +556,7 @@ struct rt_engine {
     void ensure_fold() {
         if (!fold_dirty || !farena_base) { fold_dirty = false; return; }
         for (auto& sl : slots) if (!sl.bound) return;                   // not all weights are there yet
-        for_each_tblock([&](TransformerP& t, TBlockP& k) {
+        for_each_tblock_all([&](TransformerP& t, TBlockP& k) {
             if (!k.qk1f.w) return;
             launch_ln_fold_derive(k.qk1.w, k.qk1.K, k.qk1.b, k.ln1.g, k.ln1.b, k.qk1.N, k.qk1.K, k.qk1f.w, k.qk1s, stream);
             launch_ln_fold_derive(k.v1.w, k.v1.K, k.v1.b, k.ln1.g, k.ln1.b, k.v1.N, k.v1.K, k.v1f.w, k.v1s, stream);
@@ -551,7 +591,7 @@ struct rt_engine {
             k.k2 = mk_headproj(b + ".attn2.to_k", D, heads, t.d, t.DP, 1.f, k2, D);
             bf16_t* v2 = (bf16_t*)arena.alloc((size_t)HD * D * 2);
             k.v2 = mk_headproj(b + ".attn2.to_v", D, heads, t.d, t.DP, 1.f, v2, D);
-            if (cfg.ip_tokens > 0) {
+            if (cfg.ip_tokens > 0 && !building_control) {      // (the control copy has no image-prompt term)
                 bf16_t* kip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
                 k.kip = mk_headproj(b + ".attn2.to_k_ip", D, heads, t.d, t.DP, 1.f, kip, D);
                 bf16_t* vip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
@@ -569,7 +609,7 @@ struct rt_engine {
             k.ff2 = mk_linear(b + ".ff.net.2", 4 * C, C, true);
             k.kcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
             k.vtcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
-            if (cfg.ip_tokens > 0) {
+            if (cfg.ip_tokens > 0 && !building_control) {
                 k.kipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
                 k.vtipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
             }
@@ -587,6 +627,96 @@ struct rt_engine {
         return t;
     }
 
+    // the down blocks of the UNet, or - under the prefix "controlnet." - of the ControlNet's copy of them
+    void mk_down_blocks(const std::string& prefix, std::vector<DownP>& dst, std::vector<TraceMod>& tm) {
+        const int L = cfg.n_levels;
+        const int* boc = cfg.block_out_channels;
+        int out_c = boc[0];
+        for (int i = 0; i < L; ++i) {
+            DownP d; const int in_c = out_c; out_c = boc[i]; d.C = out_c;
+            d.has_attn = cfg.down_has_attn[i]; d.has_down = i != L - 1;
+            const std::string pre = prefix + "down_blocks." + std::to_string(i);
+            for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
+                d.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), j == 0 ? in_c : out_c, out_c));
+                tm.push_back({d.res.back().name, out_c, i});
+                if (d.has_attn) {
+                    d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i));
+                    tm.push_back({d.attn.back().name, out_c, i});
+                }
+            }
+            if (d.has_down) { d.down = mk_conv3(pre + ".downsamplers.0.conv", out_c, out_c); tm.push_back({pre + ".downsamplers.0.conv", out_c, i + 1}); }
+            dst.push_back(d);
+        }
+    }
+    // The ControlNet behind the UNet's own weights (diffusers' ControlNetModel layout under "controlnet."): slots, arena offsets and caches of
+    // the UNet are what they are without it.  Its traceable modules go where they run: behind the main mid block.
+    void build_control_plan() {
+        ctl = ControlP{};
+        const int L = cfg.n_levels;
+        const int* boc = cfg.block_out_channels;
+        const std::string P = "controlnet.";
+        static const int def_ch[4] = {16, 32, 96, 256};
+        bool all0 = true;
+        for (int i = 0; i < 4; ++i) all0 = all0 && cfg.control_embed_channels[i] == 0;
+        for (int i = 0; i < 4; ++i) {
+            ctl.ce_ch[i] = all0 ? def_ch[i] : cfg.control_embed_channels[i];
+            RT_REQUIRE(ctl.ce_ch[i] >= 8 && ctl.ce_ch[i] % 8 == 0, "rt_create: control_embed_channels must be multiples of 8");
+        }
+        ctl.hint_ch = cfg.control_hint_channels ? cfg.control_hint_channels : 3;
+        RT_REQUIRE(ctl.hint_ch >= 1 && ctl.hint_ch <= 64, "rt_create: control_hint_channels");
+        building_control = true;
+        std::swap(temb_tab, ctl.temb_tab); std::swap(temb_total, ctl.temb_total);      // mk_resnet fills the control copy's own table
+        std::vector<TraceMod> tm;
+        tm.push_back({P + "hint_embedding", boc[0], 0});
+        ctl.conv_in = mk_conv3(P + "conv_in", cfg.in_channels, boc[0]);
+        tm.push_back({P + "conv_in", boc[0], 0});
+        ctl.t1 = mk_linear(P + "time_embedding.linear_1", boc[0], temb_dim, true);
+        ctl.t2 = mk_linear(P + "time_embedding.linear_2", temb_dim, temb_dim, true);
+        if (cfg.addition_text_time) {
+            ctl.a1 = mk_linear(P + "add_embedding.linear_1", cfg.projection_class_embeddings_input_dim, temb_dim, true);
+            ctl.a2 = mk_linear(P + "add_embedding.linear_2", temb_dim, temb_dim, true);
+        }
+        std::vector<TraceMod> dm;
+        mk_down_blocks(P, ctl.down, dm);
+        ctl.mid_r0 = mk_resnet(P + "mid_block.resnets.0", boc[L - 1], boc[L - 1]);
+        ctl.mid_t = mk_transformer(P + "mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1);
+        ctl.mid_r1 = mk_resnet(P + "mid_block.resnets.1", boc[L - 1], boc[L - 1]);
+        ctl.ce_in = mk_conv3_f32(P + "controlnet_cond_embedding.conv_in", ctl.hint_ch, ctl.ce_ch[0]);
+        for (int i = 0; i < 3; ++i) {
+            ctl.ce_blocks[2 * i] = mk_conv3_f32(P + "controlnet_cond_embedding.blocks." + std::to_string(2 * i), ctl.ce_ch[i], ctl.ce_ch[i]);
+            ctl.ce_blocks[2 * i + 1] = mk_conv3_f32(P + "controlnet_cond_embedding.blocks." + std::to_string(2 * i + 1), ctl.ce_ch[i], ctl.ce_ch[i + 1]);
+        }
+        ctl.ce_out = mk_conv3_f32(P + "controlnet_cond_embedding.conv_out", ctl.ce_ch[3], boc[0]);
+        // one zero convolution per skip, in push order: conv_in, then every resnet (/ attention) and down-sampler; skip k's trace point
+        // follows the module that produces the control copy's k-th skip
+        int k = 0;
+        auto zc = [&](int C, int shift) {
+            ctl.zero.push_back(mk_linear(P + "controlnet_down_blocks." + std::to_string(k), C, C, true, true));
+            tm.push_back({P + "skip." + std::to_string(k), C, shift});
+            ++k;
+        };
+        zc(boc[0], 0);
+        size_t di = 0;
+        for (int i = 0; i < L; ++i) {
+            for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
+                tm.push_back(dm[di++]);
+                if (cfg.down_has_attn[i]) tm.push_back(dm[di++]);
+                zc(boc[i], i);
+            }
+            if (i != L - 1) { tm.push_back(dm[di++]); zc(boc[i], i + 1); }
+        }
+        ctl.zero_mid = mk_linear(P + "controlnet_mid_block", boc[L - 1], boc[L - 1], true, true);
+        for (const char* m : {"mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1"}) tm.push_back({P + m, boc[L - 1], L - 1});
+        tm.push_back({P + "mid", boc[L - 1], L - 1});
+        ctl.aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
+        std::swap(temb_tab, ctl.temb_tab); std::swap(temb_total, ctl.temb_total);
+        building_control = false;
+        ctl.scale.assign((size_t)std::max(1, cfg.max_prompts), 0.f);
+        size_t at = 0;
+        while (at < trace_mods.size() && trace_mods[at].name != "mid_block.resnets.1") ++at;
+        trace_mods.insert(trace_mods.begin() + (at < trace_mods.size() ? at + 1 : at), tm.begin(), tm.end());
+    }
+
     void build_plan() {
         slots.clear(); slot_index.clear(); down.clear(); up.clear(); temb_tab.clear(); temb_total = 0; trace_mods.clear();
         const int L = cfg.n_levels;
@@ -601,22 +731,8 @@ struct rt_engine {
             a1 = mk_linear("add_embedding.linear_1", cfg.projection_class_embeddings_input_dim, temb_dim, true);
             a2 = mk_linear("add_embedding.linear_2", temb_dim, temb_dim, true);
         }
-        int out_c = boc[0];
-        for (int i = 0; i < L; ++i) {
-            DownP d; const int in_c = out_c; out_c = boc[i]; d.C = out_c;
-            d.has_attn = cfg.down_has_attn[i]; d.has_down = i != L - 1;
-            const std::string pre = "down_blocks." + std::to_string(i);
-            for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
-                d.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), j == 0 ? in_c : out_c, out_c));
-                trace_mods.push_back({d.res.back().name, out_c, i});
-                if (d.has_attn) {
-                    d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i));
-                    trace_mods.push_back({d.attn.back().name, out_c, i});
-                }
-            }
-            if (d.has_down) { d.down = mk_conv3(pre + ".downsamplers.0.conv", out_c, out_c); trace_mods.push_back({pre + ".downsamplers.0.conv", out_c, i + 1}); }
-            down.push_back(d);
-        }
+        mk_down_blocks("", down, trace_mods);
+        int out_c = boc[L - 1];
         mid_r0 = mk_resnet("mid_block.resnets.0", boc[L - 1], boc[L - 1]);
         mid_t = mk_transformer("mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1);
         mid_r1 = mk_resnet("mid_block.resnets.1", boc[L - 1], boc[L - 1]);
@@ -657,6 +773,7 @@ struct rt_engine {
         gpred = (float*)sarena.alloc((size_t)2 * HW * 4 * 4);
         gpartials = (double*)sarena.alloc((size_t)cdiv((int)HW, 256) * RT_GUIDED_SERIES * 8);
         gfactors = (float*)sarena.alloc(2 * 4);
+        if (cfg.controlnet) build_control_plan();
     }
 
     // ---------------------------------------------------------------------------- launch helpers
@@ -871,14 +988,14 @@ struct rt_engine {
                 bool any_ip = false;
                 double ip_keys = 0;
                 for (int b = 0; b < B; ++b) {
-                    const bool on = cfg.ip_tokens > 0 && ip_scale[in.prompt[b]] != 0.f;
+                    const bool on = cfg.ip_tokens > 0 && !in.control && ip_scale[in.prompt[b]] != 0.f;
                     ip_slot[b] = on ? in.prompt[b] : -1; ip_cnt[b] = on ? ip_count[in.prompt[b]] : 0; ip_sc[b] = on ? ip_scale[in.prompt[b]] : 0.f;
                     if (on) { any_ip = true; ip_keys += ip_cnt[b]; }
                 }
                 // (Only RT_PROBES builds with their debug switches on ever reach the one-launch kinds.  The dry planning forward of an
                 // engine that can hold images takes the two-launch route as well, so that the to_q GEMM a launch with an image runs
                 // has been planned: its split-K scratch is recorded like every other GEMM's.)
-                if ((any_ip || (dry() && cfg.ip_tokens > 0)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
+                if ((any_ip || (dry() && cfg.ip_tokens > 0 && !in.control)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
                     route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2, false);
                 if (route.kind == CrossRoute::XBLOCK) {
                     if (!dry()) {
@@ -948,6 +1065,150 @@ struct rt_engine {
         return Tensor{out, C};
     }
 
+    // ---------------------------------------------------------------------------- ControlNet
+    // the controlled streams of a forward, in stream order: those whose prompt slot has a scale != 0 while a hint is set
+    int control_streams(const FwdIn& in, int* cs, float* csc) const {
+        int n = 0;
+        for (int b = 0; b < in.B; ++b) {
+            const float s = dry() ? 1.f : (ctl.has_hint ? ctl.scale[in.prompt[b]] : 0.f);      // the dry pass sizes the workspace for every stream controlled
+            if (s != 0.f) { cs[n] = b; csc[n] = s; ++n; }
+        }
+        return n;
+    }
+    // refusals of a forward, before anything is launched
+    void control_check(const FwdIn& in) {
+        int cs[RT_MAXB]; float csc[RT_MAXB];
+        const int Bc = control_streams(in, cs, csc);
+        if (Bc && (in.h != ctl.hint_h || in.w != ctl.hint_w))
+            throw rt_error(RT_E_INVALID, "forward: the control hint was set for a " + std::to_string(ctl.hint_h) + " x " + std::to_string(ctl.hint_w) +
+                                             " latent grid, the forward runs " + std::to_string(in.h) + " x " + std::to_string(in.w) + " (rt_set_control_hint again: a hint is never resized)");
+        if (tracing() && trace_name.compare(0, 11, "controlnet.") == 0) {
+            const bool main_side = trace_name.compare(0, 16, "controlnet.skip.") == 0 || trace_name == "controlnet.mid";
+            if (trace_name == "controlnet.hint_embedding") { if (!ctl.has_hint) throw rt_error(RT_E_INVALID, "rt_unet_forward_trace: no control hint is set"); }
+            else if (!main_side && !Bc) throw rt_error(RT_E_INVALID, "rt_unet_forward_trace: " + trace_name + " does not run: the call controls no stream");
+        }
+    }
+    // one residual: r = zero_conv(xc) of the controlled streams as ONE GEMM into fp32 scratch, then the add into the main UNet's tensor
+    void control_residual(const MatW& z, const Tensor& xc, Tensor& dst, const int* cs, const float* csc, int Bc, int B, int HW) {
+        RT_REQUIRE(xc.C == dst.C && z.K == xc.C && z.N == xc.C, "controlnet: zero convolution / skip channel mismatch");
+        Scope sc(ws);
+        const int C = xc.C;
+        bf16_t* xb = ws.b16((size_t)Bc * HW * C);
+        float* r = ws.f32((size_t)Bc * HW * C);
+        if (!dry()) launch_cast_f16_bf16(xc.p, xb, (size_t)Bc * HW * C, stream);
+        cur_hw = HW;
+        gemm(xb, C, z, Bc * HW, r, C, EPI_F32);
+        if (dry()) return;
+        prof_begin(RT_PROF_CONTROL_ADD, 0.0, 8.0 * Bc * HW * C);      // r read (4 B), skip read + written (2 + 2 B) per element
+        launch_control_add(dst.p, (size_t)HW * C, C, r, (size_t)HW * C, C, cs, csc, Bc, B, HW, C, stream);
+        prof_end();
+    }
+    // ControlNetModel.forward for the controlled streams of `in`, behind the main UNet's mid block: adds scale x zero_conv(skip_k) into
+    // skips[k] and scale x zero_conv(mid) into xmid, in place.  Everything it allocates is released when it returns.
+    void control_forward(const FwdIn& in, std::vector<Tensor>& skips, Tensor& xmid) {
+        int cs[RT_MAXB]; float csc[RT_MAXB];
+        const int Bc = control_streams(in, cs, csc), B = in.B, Hh = in.h, Ww = in.w, HW0 = Hh * Ww, C0 = cfg.block_out_channels[0];
+        const std::string P = "controlnet.";
+        auto trace_main = [&](const std::string& n, const Tensor& t, int HW) { if (tracing()) trace_point(P + n, t, B, HW); };
+        if (tracing() && trace_name == "controlnet.hint_embedding") launch_trace_f16_nhwc_to_nchw(ctl.emb_f16, trace_out, 1, C0, HW0, stream);
+        if (!Bc) {                        // nothing runs; the main-side trace points read the tensors as the up path will
+            if (tracing()) {
+                int ch = Hh, cw = Ww; size_t k = 0;
+                trace_main("skip.0", skips[k++], ch * cw);
+                for (size_t i = 0; i < down.size(); ++i) {
+                    for (size_t j = 0; j < down[i].res.size(); ++j, ++k) trace_main("skip." + std::to_string(k), skips[k], ch * cw);
+                    if (down[i].has_down) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; trace_main("skip." + std::to_string(k), skips[k], ch * cw); ++k; }
+                }
+                trace_main("mid", xmid, ch * cw);
+            }
+            return;
+        }
+        FwdIn c{}; c.B = Bc; c.h = Hh; c.w = Ww; c.t = in.t; c.control = true;
+        for (int i = 0; i < Bc; ++i) {
+            c.x[i] = in.x[cs[i]]; c.scale[i] = in.scale[cs[i]]; c.prompt[i] = in.prompt[cs[i]];
+            c.fontsize[i] = 0; c.qk_src[i] = i; c.res_src[i] = -1;
+        }
+        Scope sc(ws);
+        float* const main_temb = temb_all;
+        float* emb = ws.f32((size_t)Bc * temb_dim);
+        {
+            Scope s2(ws);
+            float* tsin = ws.f32(C0);
+            float* e1 = ws.f32(temb_dim); float* e2 = ws.f32(temb_dim);
+            if (!dry()) {
+                launch_timestep_embed_scalar(c.t, C0, tsin, stream);
+                launch_small_linear(tsin, C0, ctl.t1.w, ctl.t1.K, ctl.t1.b, e1, temb_dim, 1, temb_dim, ctl.t1.K, 0, 0, stream);
+                launch_small_linear(e1, temb_dim, ctl.t2.w, ctl.t2.K, ctl.t2.b, e2, temb_dim, 1, temb_dim, temb_dim, 1, 0, stream);
+                launch_gather_add_rows(e2, ctl.aug_emb, c.prompt, emb, Bc, temb_dim, stream);
+            }
+        }
+        temb_all = ws.f32((size_t)Bc * ctl.temb_total);      // resnet() reads the running forward's table: the control copy's while it runs
+        {
+            Scope s2(ws);
+            float* semb = ws.f32((size_t)Bc * temb_dim);
+            if (!dry()) launch_temb_all(emb, temb_dim, semb, ctl.temb_tab_dev, (int)ctl.temb_tab.size(), ctl.temb_total, Bc, temb_dim, temb_all, stream);
+        }
+        size_t k = 0;
+        Tensor x;
+        {
+            f16_t* x0 = ws.f16((size_t)Bc * HW0 * C0);
+            Scope s2(ws);
+            bf16_t* x8 = ws.b16((size_t)Bc * HW0 * 8);
+            if (!dry()) {
+                PrepArgs p{}; p.B = Bc; p.HW = HW0; p.dst = x8;
+                for (int i = 0; i < Bc; ++i) { p.src[i] = c.x[i]; p.scale[i] = c.scale[i]; }
+                launch_prep_latents(p, stream);
+            }
+            // conv_in(x) + hint embedding: the embedding [HW0, C0] is the residual operand of the convolution's epilogue (fp32 sum, one
+            // rounding to fp16) - one launch per controlled stream, each the launch of a stream that runs alone
+            for (int i = 0; i < Bc; ++i)
+                conv3(x8 + (size_t)i * HW0 * 8, A_CONV3, ctl.conv_in, 1, Hh, Ww, 8, x0 + (size_t)i * HW0 * C0, EPI_F16, ctl.emb_f16);
+            x = Tensor{x0, C0};
+        }
+        if (tracing()) trace_point(P + "conv_in", x, Bc, HW0);
+        auto residual = [&](int HW) {
+            RT_REQUIRE(k < skips.size() && k < ctl.zero.size(), "controlnet: more control skips than skips");
+            control_residual(ctl.zero[k], x, skips[k], cs, csc, Bc, B, HW);
+            trace_main("skip." + std::to_string(k), skips[k], HW);
+            ++k;
+        };
+        residual(HW0);
+        int ch = Hh, cw = Ww;
+        for (size_t i = 0; i < ctl.down.size(); ++i) {
+            DownP& d = ctl.down[i];
+            for (size_t j = 0; j < d.res.size(); ++j) {
+                x = resnet(d.res[j], c, ch * cw, ch, cw, x, nullptr, emb, false);
+                trace_point(d.res[j].name, x, Bc, ch * cw);
+                if (d.has_attn) { x = transformer(d.attn[j], c, ch * cw, x); trace_point(d.attn[j].name, x, Bc, ch * cw); }
+                residual(ch * cw);
+            }
+            if (d.has_down) {
+                const int nh = (ch + 1) / 2, nw = (cw + 1) / 2;
+                f16_t* y = ws.f16((size_t)Bc * nh * nw * d.C);
+                {
+                    Scope s2(ws);
+                    bf16_t* xb = ws.b16((size_t)Bc * ch * cw * d.C);
+                    if (!dry()) launch_cast_f16_bf16(x.p, xb, (size_t)Bc * ch * cw * d.C, stream);
+                    conv3(xb, A_CONV3_S2, d.down, Bc, ch, cw, d.C, y, EPI_F16);
+                }
+                ch = nh; cw = nw;
+                x = Tensor{y, d.C};
+                if (tracing()) trace_point(P + "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", x, Bc, ch * cw);
+                residual(ch * cw);
+            }
+        }
+        RT_REQUIRE(k == skips.size(), "controlnet: skip count");
+        x = resnet(ctl.mid_r0, c, ch * cw, ch, cw, x, nullptr, emb, false);
+        trace_point(ctl.mid_r0.name, x, Bc, ch * cw);
+        x = transformer(ctl.mid_t, c, ch * cw, x);
+        trace_point(ctl.mid_t.name, x, Bc, ch * cw);
+        x = resnet(ctl.mid_r1, c, ch * cw, ch, cw, x, nullptr, emb, false);
+        trace_point(ctl.mid_r1.name, x, Bc, ch * cw);
+        control_residual(ctl.zero_mid, x, xmid, cs, csc, Bc, B, ch * cw);
+        trace_main("mid", xmid, ch * cw);
+        temb_all = main_temb;
+    }
+
     // UNet2DConditionModel.forward (models/unet_2d_condition.py:703-983), batched over streams
     void unet_forward(const FwdIn& in) {
         const int B = in.B, Hh = in.h, Ww = in.w, HW0 = Hh * Ww;
@@ -957,6 +1218,7 @@ struct rt_engine {
         // FreeU (rt_set_freeu): the skip filter scales the bins {-1, 0} of both axes, which a side of 1 does not have - refused before any launch
         if (!dry() && freeu_on() && ((Hh >> (cfg.n_levels - 1)) < 2 || (Ww >> (cfg.n_levels - 1)) < 2))
             throw rt_error(RT_E_UNSUPPORTED, "forward: FreeU needs a deepest grid of at least 2 x 2 (latents of " + std::to_string(2 << (cfg.n_levels - 1)) + " or more per side)");
+        if (cfg.controlnet && !dry()) control_check(in);
         if (!dry()) ensure_fold();       // (normally a no-op: rt_set_prompts derived the folded projections already)
         const size_t m0 = ws.mark();
         // time / addition embeddings (unet_2d_condition.py:784-877)
@@ -1027,6 +1289,7 @@ struct rt_engine {
         trace_point(mid_t.name, x, B, ch * cw);
         x = resnet(mid_r1, in, ch * cw, ch, cw, x, nullptr, emb, false);
         trace_point(mid_r1.name, x, B, ch * cw);
+        if (cfg.controlnet) control_forward(in, skips, x);
         for (size_t i = 0; i < up.size(); ++i) {
             UpP& u = up[i];
             for (size_t j = 0; j < u.res.size(); ++j) {
@@ -1099,8 +1362,13 @@ struct rt_engine {
         for (auto& d : down) for (auto& t : d.attn) build(t);
         build(mid_t);
         for (auto& u : up) for (auto& t : u.attn) build(t);
+        if (cfg.controlnet) {
+            for (auto& d : ctl.down) for (auto& t : d.attn) build(t);
+            build(ctl.mid_t);
+        }
         cur_hw = 0;
         HIP_CHECK(hipMemsetAsync(aug_emb, 0, (size_t)cfg.max_prompts * temb_dim * 4, stream));
+        if (cfg.controlnet) HIP_CHECK(hipMemsetAsync(ctl.aug_emb, 0, (size_t)cfg.max_prompts * temb_dim * 4, stream));
         if (cfg.addition_text_time) {
             RT_REQUIRE(pooled && time_ids, "set_prompts: SDXL needs pooled embeds and time_ids");
             const int td = cfg.addition_time_embed_dim, Kin = cfg.projection_class_embeddings_input_dim;
@@ -1115,10 +1383,15 @@ struct rt_engine {
             }
             launch_small_linear(add, Kin, a1.w, a1.K, a1.b, hmid, temb_dim, P, temb_dim, Kin, 0, 0, stream);
             launch_small_linear(hmid, temb_dim, a2.w, a2.K, a2.b, aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
+            if (cfg.controlnet) {      // the control copy's own add_embedding of the same (pooled | time ids) rows
+                launch_small_linear(add, Kin, ctl.a1.w, ctl.a1.K, ctl.a1.b, hmid, temb_dim, P, temb_dim, Kin, 0, 0, stream);
+                launch_small_linear(hmid, temb_dim, ctl.a2.w, ctl.a2.K, ctl.a2.b, ctl.aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
+            }
         }
         n_prompts = P;
         for (int p_ = 0; p_ < P; ++p_) prompt_keys[p_] = counts ? counts[p_] : L;
         std::fill(ip_scale.begin(), ip_scale.end(), 0.f);              // the slots change meaning: no prompt has an image until rt_set_image_prompts
+        std::fill(ctl.scale.begin(), ctl.scale.end(), 0.f);            // ... and none is controlled until rt_set_control_scales (the hint stays)
         HIP_CHECK(hipStreamSynchronize(stream));   // host buffers (time_ids) may go away
     }
 
@@ -1157,6 +1430,55 @@ struct rt_engine {
         HIP_CHECK(hipStreamSynchronize(stream));   // the launches read the caller's tokens
     }
 
+    // controlnet_cond_embedding on the hint [Ch, 8 h, 8 w] (device, fp32): eight 3x3 convolutions in fp32 with the SiLU in their epilogue
+    // (control_conv3_kernel).  The arguments are validated before the state is touched; scratch lives for this call only.
+    void set_control_hint(const float* hint, int h, int w) {
+        RT_REQUIRE(cfg.controlnet, "set_control_hint: the engine was built without a ControlNet (rt_config.controlnet == 0)");
+        if (!hint) { ctl.has_hint = false; ctl.hint_h = ctl.hint_w = 0; return; }
+        RT_REQUIRE(h >= 1 && w >= 1 && h <= cfg.latent_h && w <= cfg.latent_w, "set_control_hint: latent grid outside the plan");
+        require_bound();
+        const int C0 = cfg.block_out_channels[0], CP = (ctl.hint_ch + 7) & ~7;
+        const size_t HWi = (size_t)64 * h * w;
+        // the largest activation of the chain: the input, conv_in / blocks.0 at full size, then a quarter of the pixels per stride-2 block
+        size_t need = HWi * std::max(CP, ctl.ce_ch[0]);
+        for (int i = 1; i < 4; ++i) need = std::max(need, (HWi >> (2 * i)) * (size_t)ctl.ce_ch[i]);
+        if (!ctl.emb_f32) {
+            HIP_CHECK(hipMalloc((void**)&ctl.emb_f32, (size_t)cfg.latent_h * cfg.latent_w * C0 * 4));
+            HIP_CHECK(hipMalloc((void**)&ctl.emb_f16, (size_t)cfg.latent_h * cfg.latent_w * C0 * 2));
+        }
+        struct Tmp { void* p = nullptr; ~Tmp() { (void)hipFree(p); } } a_, b_;
+        HIP_CHECK(hipMalloc(&a_.p, need * 4)); HIP_CHECK(hipMalloc(&b_.p, need * 4));
+        float* cur = (float*)a_.p; float* nxt = (float*)b_.p;
+        ctl.has_hint = false;                 // (an error below leaves the engine without a hint, never with half of one)
+        int Hc = 8 * h, Wc = 8 * w;
+        auto conv_silu = [&](const ControlP::ConvF& W, int stride, int CinP) {
+            RT_REQUIRE(W.CinP == CinP, "set_control_hint: weight / input channel mismatch");
+            const int Ho = stride == 2 ? (Hc + 1) / 2 : Hc, Wo = stride == 2 ? (Wc + 1) / 2 : Wc;
+            RT_REQUIRE((size_t)Hc * Wc * CinP <= need && (size_t)Ho * Wo * W.N <= need, "set_control_hint: scratch");
+            launch_control_conv3(cur, W.w, W.b, nxt, nullptr, Hc, Wc, CinP, W.N, stride, 1, stream);
+            Hc = Ho; Wc = Wo;
+            std::swap(cur, nxt);
+        };
+        launch_control_hint(hint, cur, ctl.hint_ch, CP, HWi, stream);
+        conv_silu(ctl.ce_in, 1, CP);
+        for (int i = 0; i < 3; ++i) {
+            conv_silu(ctl.ce_blocks[2 * i], 1, ctl.ce_ch[i]);
+            conv_silu(ctl.ce_blocks[2 * i + 1], 2, ctl.ce_ch[i]);
+        }
+        RT_REQUIRE(Hc == h && Wc == w && ctl.ce_out.CinP == ctl.ce_ch[3], "set_control_hint: embedder grid");
+        // conv_out: the fp32 embedding and the same values rounded once to the trunk's fp16 (the residual operand of controlnet.conv_in)
+        launch_control_conv3(cur, ctl.ce_out.w, ctl.ce_out.b, ctl.emb_f32, ctl.emb_f16, h, w, ctl.ce_ch[3], C0, 1, 0, stream);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        ctl.has_hint = true; ctl.hint_h = h; ctl.hint_w = w;
+    }
+    void set_control_scales(const float* scales, int P) {
+        RT_REQUIRE(cfg.controlnet, "set_control_scales: the engine was built without a ControlNet (rt_config.controlnet == 0)");
+        RT_REQUIRE(scales, "set_control_scales: scales");
+        RT_REQUIRE(P >= 1 && P <= n_prompts, "set_control_scales: more slots than prompts set (rt_set_prompts first)");
+        for (int p_ = 0; p_ < P; ++p_) RT_REQUIRE(std::isfinite(scales[p_]), "set_control_scales: a scale must be finite");
+        for (int p_ = 0; p_ < cfg.max_prompts; ++p_) ctl.scale[p_] = p_ < P ? scales[p_] : 0.f;
+    }
+
     void set_fontsize(const int64_t* word_pos, const float* font_size, int n) {
         // set 0: plain softmax; set 1: font-size softmax (attention_processor.py:386-396).  wabs = 0 on padded keys.
         // One table row per key POSITION of the longest prompt the engine holds (KP = 96 rows per chunk, keys first): chunk c of a prompt
@@ -1184,6 +1506,12 @@ struct rt_engine {
         for (auto& d : down) for (auto& t : d.attn) for (auto& k : t.blocks) f(t, k);
         for (auto& k : mid_t.blocks) f(mid_t, k);
         for (auto& u : up) for (auto& t : u.attn) for (auto& k : t.blocks) f(t, k);
+    }
+    // ... and the ControlNet's copy behind them (the token-map store and the image prompts are the UNet's alone: they keep for_each_tblock)
+    template <typename F> void for_each_tblock_all(F f) {
+        for_each_tblock(f);
+        for (auto& d : ctl.down) for (auto& t : d.attn) for (auto& k : t.blocks) f(t, k);
+        for (auto& k : ctl.mid_t.blocks) f(ctl.mid_t, k);
     }
     bool any_store() { bool any = false; for_each_tblock([&](TransformerP&, TBlockP& k) { any |= k.store_mode[0] || k.store_mode[1]; }); return any; }
     void attn_store_enable(const std::string& name, int mode) {
@@ -1262,6 +1590,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         RT_REQUIRE(cfg->cross_attention_dim % 8 == 0, "rt_create: cross_attention_dim % 8");
         RT_REQUIRE(cfg->max_keys == 0 || cfg->max_keys == 77 || cfg->max_keys == 154 || cfg->max_keys == 231, "rt_create: max_keys must be 77, 154 or 231 (0 = 77)");
         RT_REQUIRE(cfg->ip_tokens >= 0 && cfg->ip_tokens <= 16, "rt_create: ip_tokens must be 0 (no image prompts) or 1 .. 16");
+        RT_REQUIRE(cfg->controlnet == 0 || cfg->controlnet == 1, "rt_create: controlnet must be 0 or 1");
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
         e->ip_count.assign((size_t)std::max(1, cfg->max_prompts), 0); e->ip_scale.assign((size_t)std::max(1, cfg->max_prompts), 0.f);
@@ -1301,10 +1630,10 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
             {   // the K / V^T cache GEMMs of rt_set_prompts (one prompt = one 96-row stream) at the largest prompt count
                 const int D = cfg->cross_attention_dim, P96 = cfg->max_prompts * e->KP();
                 e->cur_hw = 96;
-                e->for_each_tblock([&](TransformerP& t, TBlockP& k) {
+                e->for_each_tblock_all([&](TransformerP& t, TBlockP& k) {
                     e->gemm(nullptr, D, k.k2, P96, nullptr, t.heads * t.DP, EPI_BF16);
                     e->gemm_vt(k.v2, nullptr, D, P96, nullptr, P96);
-                    if (cfg->ip_tokens > 0) {      // ... and those of rt_set_image_prompts (one slot = one 16-row stream)
+                    if (cfg->ip_tokens > 0 && k.kip.w) {      // ... and those of rt_set_image_prompts (one slot = one 16-row stream)
                         e->cur_hw = 16;
                         e->gemm(nullptr, D, k.kip, cfg->max_prompts * 16, nullptr, t.heads * t.DP, EPI_BF16);
                         e->gemm_vt(k.vip, nullptr, D, cfg->max_prompts * 16, nullptr, cfg->max_prompts * 16);
@@ -1341,6 +1670,10 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
                 HIP_CHECK(hipMalloc((void**)&e->temb_tab_dev, e->temb_tab.size() * sizeof(TembEntry)));
                 HIP_CHECK(hipMemcpy(e->temb_tab_dev, e->temb_tab.data(), e->temb_tab.size() * sizeof(TembEntry), hipMemcpyHostToDevice));
             }
+            if (!e->ctl.temb_tab.empty()) {
+                HIP_CHECK(hipMalloc((void**)&e->ctl.temb_tab_dev, e->ctl.temb_tab.size() * sizeof(TembEntry)));
+                HIP_CHECK(hipMemcpy(e->ctl.temb_tab_dev, e->ctl.temb_tab.data(), e->ctl.temb_tab.size() * sizeof(TembEntry), hipMemcpyHostToDevice));
+            }
         }
         e->set_fontsize(nullptr, nullptr, 0);      // multiplier set 0/1 = plain softmax until rt_set_fontsize is called
         *out = e;
@@ -1357,7 +1690,9 @@ int rt_destroy(rt_engine* e) {
     if (e->arena_base) {
         (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->stream);
         for (auto& r : e->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->temb_tab_dev); (void)hipFree(e->splitk_buf); (void)hipFree(e->src_buf); (void)hipStreamDestroy(e->own_stream);
+        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->temb_tab_dev); (void)hipFree(e->splitk_buf); (void)hipFree(e->src_buf);
+        (void)hipFree(e->ctl.temb_tab_dev); (void)hipFree(e->ctl.emb_f32); (void)hipFree(e->ctl.emb_f16);
+        (void)hipStreamDestroy(e->own_stream);
     }
     delete e;
     return RT_OK;
@@ -1400,7 +1735,8 @@ int rt_bind_weight(rt_engine* e, const char* name, const void* ptr, int dtype, c
         // (attn2.to_k / to_v, to_k_ip / to_v_ip) and the addition embeddings (add_embedding.*) - cannot be rebuilt here (the engine does
         // not keep the prompt embeddings): the prompts are discarded, and a forward or step before the next rt_set_prompts is an error.
         e->fold_dirty = true;
-        if (s.name.compare(0, 14, "add_embedding.") == 0 || s.name.find(".attn2.to_k") != std::string::npos || s.name.find(".attn2.to_v") != std::string::npos)
+        if (s.name.find("controlnet_cond_embedding.") != std::string::npos) e->ctl.has_hint = false;      // the cached embedding came from the old weight
+        if (s.name.compare(0, 14, "add_embedding.") == 0 || s.name.compare(0, 25, "controlnet.add_embedding.") == 0 || s.name.find(".attn2.to_k") != std::string::npos || s.name.find(".attn2.to_v") != std::string::npos)
             e->n_prompts = 0;
     })
 }
@@ -1411,7 +1747,7 @@ int rt_weights_missing(rt_engine* e, char* buf, int cap) {
     return n;
 }
 int rt_arena_info(rt_engine* e, void** p, uint64_t* bytes) { RT_TRY(e, { need_device(e); *p = e->arena_base; *bytes = e->arena_bytes; }) }
-int rt_arena_mark_bound(rt_engine* e) { for (auto& s : e->slots) s.bound = true; e->fold_dirty = true; e->n_prompts = 0; return RT_OK; }
+int rt_arena_mark_bound(rt_engine* e) { for (auto& s : e->slots) s.bound = true; e->fold_dirty = true; e->n_prompts = 0; e->ctl.has_hint = false; return RT_OK; }
 
 int rt_set_prompts(rt_engine* e, const float* pe, const float* pooled, const float* tids, int P, int pooled_dim) {
     RT_TRY(e, { need_device(e); e->ensure_fold(); e->set_prompts(pe, nullptr, 77, pooled, tids, P, pooled_dim); })
@@ -1421,6 +1757,21 @@ int rt_set_prompts_keys(rt_engine* e, const float* pe, const int* key_counts, in
 }
 int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts, const float* scales, int P) {
     RT_TRY(e, { need_device(e); e->set_image_prompts(tokens, counts, scales, P); })
+}
+int rt_set_control_hint(rt_engine* e, const float* hint, int h, int w) { RT_TRY(e, { need_device(e); e->set_control_hint(hint, h, w); }) }
+int rt_set_control_scales(rt_engine* e, const float* scales, int P) { RT_TRY(e, { need_device(e); e->set_control_scales(scales, P); }) }
+int rt_control_embedding_read(rt_engine* e, float* dst, int* rows, int* cols) {
+    RT_TRY(e, {
+        need_device(e);
+        RT_REQUIRE(e->cfg.controlnet, "rt_control_embedding_read: the engine was built without a ControlNet (rt_config.controlnet == 0)");
+        const int n = e->ctl.has_hint ? e->ctl.hint_h * e->ctl.hint_w : 0, C0 = e->cfg.block_out_channels[0];
+        if (rows) *rows = n;
+        if (cols) *cols = C0;
+        if (dst && n) {
+            HIP_CHECK(hipMemcpyAsync(dst, e->ctl.emb_f32, (size_t)n * C0 * 4, hipMemcpyDeviceToDevice, e->stream));
+            HIP_CHECK(hipStreamSynchronize(e->stream));
+        }
+    })
 }
 int rt_set_masks(rt_engine* e, const float* m, int R, int h, int w) {
     RT_TRY(e, {
@@ -2208,6 +2559,13 @@ int rt_op_freeu(void* hidden_f16, int C1, void* skip_f16, int C2, int B, int H, 
     OP_TRY({
         RT_REQUIRE(std::isfinite(b) && b > 0.f && std::isfinite(s) && s > 0.f, "rt_op_freeu: b and s must be finite and > 0");
         launch_freeu((f16_t*)hidden_f16, C1, (f16_t*)skip_f16, C2, B, H, W, b, s, (hipStream_t)stream);
+    })
+}
+int rt_op_control_add(void* skip_f16, long long skip_stride, int lds, const float* r, long long r_stride, int ldr, const int* stream_host,
+                      const float* scale_host, int n, int B, int HW, int C, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(skip_f16 && r && stream_host && scale_host && skip_stride >= 0 && r_stride >= 0, "rt_op_control_add: null argument / negative stride");
+        launch_control_add((f16_t*)skip_f16, (size_t)skip_stride, lds, r, (size_t)r_stride, ldr, stream_host, scale_host, n, B, HW, C, (hipStream_t)stream);
     })
 }
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream) {

@@ -3,6 +3,8 @@ start, the rich-text and the plain step loops, the finish, and the VAE encoder b
 (its scheduler, masks, device, split_image flag and token-map hooks are read), `eng` its engine."""
 import torch
 
+from .controlnet import switch_control
+
 
 def start(pipe, eng, latents, x0=None, keep=None):
     """Sets the engine's start latents: `latents` as given, or - with a source x0 - a*x0 + b*latents at the scheduler's start level
@@ -27,6 +29,7 @@ def rich_steps(pipe, eng, h, w, guidance_scale, inject_selfattn, inject_backgrou
                keep=None, levels=None, callback=None, callback_steps=1):
     split = getattr(pipe, "split_image", False)
     for i in range(len(pipe.scheduler.timesteps)):
+        switch_control(pipe, eng, i)             # ControlNet (set_control's start / end): the scales go on and off between steps
         if split:
             # intra-image split (launcher.split_region_step): the ranks of the process group share THIS image's step - each runs
             # the forwards of its stream range, one exchange of the noise predictions, every rank finishes the step
@@ -65,6 +68,7 @@ def plain_steps(pipe, eng, guidance_scale):
     if hooks:
         pipe._store_begin(eng)
     for i in range(n):
+        switch_control(pipe, eng, i)
         if getattr(pipe, "split_image", False):                  # one stream per rank, the text stream's rank records the maps
             from .launcher import split_plain_step
             split_plain_step(eng, i, guidance_scale)

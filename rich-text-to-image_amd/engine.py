@@ -55,6 +55,9 @@ class RtConfig(C.Structure):
         ("max_streams", C.c_int), ("max_prompts", C.c_int),
         ("max_keys", C.c_int),
         ("ip_tokens", C.c_int),
+        ("controlnet", C.c_int),
+        ("control_hint_channels", C.c_int),
+        ("control_embed_channels", C.c_int * 4),
     ]
 
 
@@ -93,6 +96,7 @@ _SYMBOLS = [
     "rt_unet_forward_trace", "rt_trace_module_count", "rt_trace_module_info",
     "rt_op_patchify", "rt_op_vit_embed", "rt_op_bidir_attention",
     "rt_op_latent_attention",
+    "rt_set_control_hint", "rt_control_embedding_read", "rt_set_control_scales", "rt_op_control_add",
 ]
 
 
@@ -133,9 +137,13 @@ def _tup(v, n):
     return tuple(v) if isinstance(v, (tuple, list)) else (v,) * n
 
 
-def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0):
+CONTROL_EMBED_CHANNELS = (16, 32, 96, 256)      # diffusers' ControlNetModel default `conditioning_embedding_out_channels`
+
+
+def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None):
     """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window).
-    ip_tokens: image tokens per prompt slot of an IP-Adapter (1 .. 16); 0 = none: the weight table is the reference's state_dict layout."""
+    ip_tokens: image tokens per prompt slot of an IP-Adapter (1 .. 16); 0 = none: the weight table is the reference's state_dict layout.
+    controlnet: None = no ControlNet (likewise), or dict(embed_channels=(16, 32, 96, 256), hint_channels=3) - either key optional."""
     c = RtConfig()
     boc = tuple(cfg["block_out_channels"])
     n = len(boc)
@@ -163,6 +171,17 @@ def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_
     c.max_streams, c.max_prompts = max_streams, max_prompts
     c.max_keys = max_keys
     c.ip_tokens = int(ip_tokens)
+    if controlnet is not None:
+        unknown = set(controlnet) - {"embed_channels", "hint_channels"}
+        if unknown:
+            raise ValueError(f"controlnet: unknown keys {sorted(unknown)}")
+        ch = tuple(int(v) for v in (controlnet.get("embed_channels") or CONTROL_EMBED_CHANNELS))
+        if len(ch) != 4 or any(v < 8 or v % 8 for v in ch):
+            raise ValueError(f"controlnet: embed_channels must be four multiples of 8, got {ch}")
+        c.controlnet = 1
+        c.control_hint_channels = int(controlnet.get("hint_channels") or 3)
+        for i, v in enumerate(ch):
+            c.control_embed_channels[i] = v
     return c
 
 
@@ -173,10 +192,11 @@ def _ptr(t):
 class Engine:
     """One engine = one GPU.  Mirrors the C ABI one to one; see include/rtdiff.h for semantics."""
 
-    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0):
+    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None):
         self.lib = load_library()
         self.cfg_dict = dict(cfg_dict)
-        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens)
+        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens, controlnet)
+        self.controlnet = dict(controlnet) if controlnet is not None else None
         self.max_keys = max_keys
         self.ip_tokens = int(ip_tokens)
         self.h = C.c_void_p()
@@ -304,6 +324,46 @@ class Engine:
             if len(cn) != P:
                 raise ValueError(f"set_image_prompts: {len(cn)} counts for {P} scales")
         self._chk(self.lib.rt_set_image_prompts(self.h, _ptr(tk), (C.c_int * P)(*cn) if cn is not None else None, (C.c_float * max(1, P))(*sc), P))
+
+    # ---- ControlNet (include/rtdiff.h: rt_set_control_hint / rt_set_control_scales; engines built with controlnet=dict(...))
+    def set_control_hint(self, hint):
+        """hint [hint_channels, 8 h, 8 w] (or [1, ...]) fp32, values as the checkpoint expects (usually 0 .. 1): runs the hint embedder once
+        and caches the [h w, C0] embedding every controlled stream adds to controlnet.conv_in(x).  None clears the hint.  The hint
+        survives set_prompts; a forward at another latent size while a stream is controlled raises."""
+        if hint is None:
+            self._chk(self.lib.rt_set_control_hint(self.h, None, 0, 0))
+            return
+        t = hint.to(f"cuda:{self.device}").float().contiguous()
+        if t.dim() == 4 and t.shape[0] == 1:
+            t = t[0]
+        ch = self.cfg.control_hint_channels or 3
+        if t.dim() != 3 or t.shape[0] != ch or t.shape[1] % 8 or t.shape[2] % 8:
+            raise RtError(-1, f"set_control_hint: the hint must be [{ch}, 8 h, 8 w], got {tuple(hint.shape)}")
+        self._chk(self.lib.rt_set_control_hint(self.h, _ptr(t), t.shape[1] // 8, t.shape[2] // 8))
+
+    def set_control_scales(self, scales):
+        """One finite scale per prompt slot of the last set_prompts; 0 = a stream that runs that prompt is not controlled (it launches
+        nothing new and keeps its bits).  set_prompts resets every scale to 0."""
+        sc = [float(v) for v in scales]
+        self._chk(self.lib.rt_set_control_scales(self.h, (C.c_float * max(1, len(sc)))(*sc), len(sc)))
+
+    def control_embedding(self):
+        """The cached hint embedding as fp32 [h w, C0] on the GPU, or None when no hint is set (test seam)."""
+        import torch
+        r, c = C.c_int(), C.c_int()
+        self._chk(self.lib.rt_control_embedding_read(self.h, None, C.byref(r), C.byref(c)))
+        if r.value == 0:
+            return None
+        out = torch.empty(r.value, c.value, device=f"cuda:{self.device}")
+        self._chk(self.lib.rt_control_embedding_read(self.h, _ptr(out), C.byref(r), C.byref(c)))
+        return out
+
+    PROF_CONTROL = 8        # control_add_kernel (the ControlNet residual adds of a step): priced in algorithmic HBM bytes
+
+    def profile_read_control(self):
+        n, ms, fl, by = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.rt_profile_read2(self.h, self.PROF_CONTROL, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)))
+        return dict(launches=n.value, total_ms=ms.value, total_flops=fl.value, total_bytes=by.value)
 
     def set_masks(self, masks):
         """masks: list of [1,4,h,w] tensors (model.masks) or one [R,4,h,w] tensor."""
@@ -516,6 +576,8 @@ class Engine:
                 raise RtError(-1, f"unet_forward: not a traceable module: {trace}")
             ch, sh = shapes[trace]
             tr = torch.empty(B, ch, h >> sh, w >> sh, device=x.device)
+            if trace.startswith("controlnet."):      # the control copy's own modules leave the CONTROLLED streams only, the hint embedding one entry: the rest stays NaN
+                tr.fill_(float("nan"))
             self._chk(self.lib.rt_unet_forward_trace(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
                                                      iarr(qk_src), iarr(res_src), _ptr(out), trace.encode(), _ptr(tr), C.c_longlong(tr.numel())))
             self.synchronize()
@@ -585,6 +647,27 @@ def freeu(hidden, skip, H, W, b=1.0, s=1.0):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return hidden, skip
+
+
+def control_add(skip, r, streams, scales, C_=None):
+    """The ControlNet residual add alone (rt_op_control_add), IN PLACE on skip: fp16 [B, HW, >= C] (a view with row / stream strides is
+    fine: they are the leading dimension and the stream stride), r fp32 [n, HW, >= C]; entry i adds scales[i] * r[i] into stream
+    streams[i].  C_ = the channel count when the tensors are wider views (default: skip's last dimension).  Returns skip."""
+    import torch
+    lib = load_library()
+    n = len(streams)
+    assert skip.dtype == torch.float16 and r.dtype == torch.float32 and skip.dim() == 3 and r.dim() == 3, "control_add: fp16 [B, HW, C] and fp32 [n, HW, C]"
+    assert skip.stride(2) == 1 and r.stride(2) == 1 and skip.device == r.device and r.shape[0] >= n and len(scales) == n and r.shape[1] == skip.shape[1]
+    Cc = int(C_ or skip.shape[2])
+    assert Cc <= skip.shape[2] and Cc <= r.shape[2]
+    with torch.cuda.device(skip.device):
+        rc = lib.rt_op_control_add(_ptr(skip), C.c_longlong(skip.stride(0)), int(skip.stride(1)), _ptr(r), C.c_longlong(r.stride(0)), int(r.stride(1)),
+                                   (C.c_int * max(1, n))(*[int(v) for v in streams]), (C.c_float * max(1, n))(*[float(v) for v in scales]), n,
+                                   int(skip.shape[0]), int(skip.shape[1]), Cc, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return skip
 
 
 def guided_prediction(eps, lat, g, s_uncond=0, s_base=1, masks=None, lat_ref=None, s_uref=-1, s_tref=-1, s_region=(), plain=True,

@@ -42,9 +42,22 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     (enable_freeu) for the duration of the call, restored after it; absent / None: the pipeline as it is.
     `param['image_prompts']` (optional; ip_adapter.image_prompts_from_specs' result: dict(base=, regions=, negative=) of dict(file=,
     scale=)): the image prompts of THIS request on a pipeline with an IP-Adapter loaded - set for the call, restored after it; `base`
-    holds in both passes, `regions` (by region number) in the rich pass; absent / None: the pipeline as it is."""
+    holds in both passes, `regions` (by region number) in the rich pass; absent / None: the pipeline as it is.
+    `param['control']` (optional; set_control's keyword arguments, controlnet.control_from_request / check_control_args' result: image=
+    a file, scale=, regions=, negative=, start=, end=): the ControlNet hint and scales of THIS request on a pipeline with a ControlNet
+    loaded - set for the call, restored after it; the hint is resized to the request's height x width; absent / None: the pipeline as it is."""
     args = (model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background, latents,
             init_image, strength, keep_source)
+    cn = param.get('control')
+    if cn is not None:
+        if getattr(model, 'controlnet', None) is None:
+            raise ValueError("control needs a ControlNet: none is loaded on this pipeline (load_controlnet / --controlnet)")
+        keep_cn = getattr(model, 'control', None)
+        model.set_control(**cn)
+        try:
+            return generate(model, {k: v for k, v in param.items() if k != 'control'}, *args)
+        finally:
+            model.control = keep_cn
     ip = param.get('image_prompts')
     if ip is not None:
         from .ip_adapter import apply_specs
@@ -252,6 +265,56 @@ def check_ip_args(a):
     return flag
 
 
+def check_control_args(a):
+    """--controlnet / --control_image / --control_scale / --control_start / --control_end and the "control" keys of a --requests file,
+    checked before any rank starts: the checkpoint and every hint image exist, every scale parses, no control without a ControlNet.  Bad
+    values end the run (SystemExit).  Returns the flags' control request (set_control's keyword arguments) or None."""
+    from .controlnet import control_from_request, parse_scale_args
+
+    def checked(kw, who):
+        if not getattr(a, "controlnet", None):
+            raise SystemExit(f"sample: {who} needs --controlnet")
+        if not os.path.isfile(kw["image"]):
+            raise SystemExit(f"sample: {who}: file not found: {kw['image']}")
+        if not (0.0 <= kw["start"] < kw["end"] <= 1.0):
+            raise SystemExit(f"sample: {who}: need 0 <= start < end <= 1, got start {kw['start']}, end {kw['end']}")
+        return kw
+    cn = getattr(a, "controlnet", None)
+    if cn and not (os.path.isfile(cn) or os.path.isdir(cn)):
+        raise SystemExit(f"sample: --controlnet: file not found: {cn}")
+    flag = None
+    image = getattr(a, "control_image", None)
+    if image:
+        try:
+            kw = parse_scale_args(getattr(a, "control_scale", None))
+        except ValueError as e:
+            raise SystemExit(f"sample: {e}")
+        kw.update(image=image, start=float(getattr(a, "control_start", 0.0)), end=float(getattr(a, "control_end", 1.0)))
+        flag = checked(kw, "--control_image")
+    elif getattr(a, "control_scale", None):
+        raise SystemExit("sample: --control_scale needs --control_image")
+    if getattr(a, "requests", None):
+        with open(a.requests) as f:
+            for n, line in enumerate(f, 1):
+                if line.strip() and json.loads(line).get("control") is not None:
+                    try:
+                        checked(control_from_request(json.loads(line)["control"], f"--requests line {n}: control"), f"--requests line {n}: control")
+                    except ValueError as e:
+                        raise SystemExit(f"sample: {e}")
+    return flag
+
+
+def _request_control(a, r):
+    """A --requests line's "control" ({"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b}), else the flags'."""
+    if r.get("control") is None:
+        return getattr(a, "control", None)
+    from .controlnet import control_from_request
+    try:
+        return control_from_request(r["control"], "--requests: control")
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
+
+
 def _request_image_prompts(a, r):
     """A --requests line's "image_prompts" (a list of FILE[:TARGET[:SCALE]] strings or {"file", "target", "scale"} objects for embeddings,
     or {"embeds": [...], "images": [...]} with the same lists for embeddings and pictures), else the flags'."""
@@ -269,7 +332,7 @@ def build_requests(a):
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
     one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
-    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
+    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); "control": {"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b} = the ControlNet hint and scales of that request alone (--controlnet); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -283,13 +346,13 @@ def build_requests(a):
                                  negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
                                  max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1)))),
                                  freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu"),
-                                 image_prompts=_request_image_prompts(a, r)))
+                                 image_prompts=_request_image_prompts(a, r), control=_request_control(a, r)))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
         reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1),
-                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None)) for j, sd in pairs]
+                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None), control=getattr(a, "control", None)) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -317,6 +380,11 @@ def build_model(a, rank=0, local_rank=0, world=1):
                 m.load_image_encoder(a.image_encoder)
             except ValueError as e:
                 raise SystemExit(f"sample: --image_encoder: {e}")
+        if getattr(a, 'controlnet', None):       # --controlnet: every rank reads the file itself and checks it; on ranks > 0 the weights travel in the arena
+            try:
+                m.load_controlnet(a.controlnet)
+            except ValueError as e:
+                raise SystemExit(f"sample: --controlnet: {e}")
         return m
     if world == 1:
         if a.model == 'SD':
@@ -463,6 +531,17 @@ def build_parser():
     p.add_argument('--ip_images', type=str, nargs='+', default=None, metavar='FILE[:TARGET[:SCALE]]',
                    help='with --ip_adapter and --image_encoder: a picture (.png / .jpg / .jpeg / .webp / .bmp) as the image prompt of TARGET, '
                         'as --ip_image_embeds; both flags may be given, two prompts for one TARGET are an error')
+    p.add_argument('--controlnet', type=str, default=None, metavar='PATH',
+                   help='ControlNet checkpoint (.safetensors / .bin in diffusers\' ControlNetModel layout, or its directory) for this UNet: a '
+                        'hint image steers the geometry of both passes, see --control_image.  Holds on every rank of --gpus N')
+    p.add_argument('--control_image', type=str, default=None, metavar='FILE',
+                   help='with --controlnet: the hint (edges, depth, pose, a scribble - already preprocessed), resized to height x width')
+    p.add_argument('--control_scale', type=str, nargs='+', default=None, metavar='S|TARGET:S',
+                   help='with --control_image: the conditioning scale.  A bare S is the default of every prompt (the negative one included, as '
+                        'in diffusers); TARGET:S overrides it for TARGET = negative or a region number of the rich text; base:S is the bare S. '
+                        'A prompt with scale 0 is not controlled.  Default 1')
+    p.add_argument('--control_start', type=float, default=0.0, help='with --control_image: the fraction of the executed schedule at which control begins (control_guidance_start)')
+    p.add_argument('--control_end', type=float, default=1.0, help='... and at which it ends (control_guidance_end)')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
                    help='what the UNet predicts; default: the checkpoint\'s scheduler/scheduler_config.json, else epsilon')
     p.add_argument('--timestep_spacing', type=str, default=None, choices=['leading', 'trailing'],
@@ -508,6 +587,7 @@ def main(argv=None):
     if a.requests:
         check_requests_freeu(a.requests)
     a.image_prompts = check_ip_args(a)                 # ... and a missing adapter / embedding file or a malformed FILE[:TARGET[:SCALE]]
+    a.control = check_control_args(a)                  # ... and a missing ControlNet / hint image or a malformed --control_scale
     if a.init_image is None and a.keep_source != 'none':
         raise SystemExit("sample: --keep_source needs --init_image")
     if a.init_image is not None and a.keep_source != 'none' and a.split_image:
@@ -544,7 +624,8 @@ def main(argv=None):
         apply_request_scheduler(model, flag_scheduler, r, a)
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
-                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu'), 'image_prompts': r.get('image_prompts')}
+                 'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu'), 'image_prompts': r.get('image_prompts'),
+                 'control': r.get('control')}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

@@ -5,13 +5,15 @@ import types
 import torch
 
 from .engine import Engine
+from .controlnet import ControlNetMixin
 from .ip_adapter import IPAdapterMixin
 
 
-class HipUNet2DConditionModel(IPAdapterMixin):
+class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin):
     """Holds the engine(s) for one set of weights; engines are created lazily per latent size.  With an IP-Adapter installed
-    (load_ip_adapter) every engine is built with its image tokens per prompt and carries its to_k_ip / to_v_ip weights; the operator
-    seam __call__ stays text-only."""
+    (load_ip_adapter) every engine is built with its image tokens per prompt and carries its to_k_ip / to_v_ip weights; with a ControlNet installed
+    (load_controlnet) every engine is built with it and carries its weights under "controlnet.".  The operator seam __call__ stays
+    text-only and uncontrolled."""
 
     def __init__(self, config, state_dict=None, device=0, max_streams=8, max_prompts=8, max_keys=77):
         self.config_dict = dict(config)
@@ -23,6 +25,19 @@ class HipUNet2DConditionModel(IPAdapterMixin):
         self._engines = {}
         self.freeu = None                          # (s1, s2, b1, b2) or None = off: on every engine of this model, present and future
         self.ip_tokens, self._ip_weights = 0, None # install_ip_adapter: image tokens per prompt slot (0 = no adapter) and the adapter's layer weights
+        self._cn_config, self._cn_weights = None, None   # install_controlnet: Engine's controlnet= argument (None = no ControlNet) and the ControlNet's weights
+
+    def install_controlnet(self, cn):
+        """cn: what controlnet.load_controlnet returns, or None = remove it.  As install_ip_adapter: the weight table changes, the engines
+        are dropped and rebuilt on their next use, and a model whose weights arrived by broadcast refuses once it has an engine."""
+        if isinstance(self._state_dict, str) and self._state_dict == "empty" and self._engines:
+            raise RuntimeError("HipUNet2DConditionModel: the weights of this model arrived by broadcast and live in its engines only; "
+                               "load / unload a ControlNet before the first engine is built")
+        self._cn_config = dict(embed_channels=cn["embed_channels"], hint_channels=cn["hint_channels"]) if cn is not None else None
+        self._cn_weights = cn["weights"] if cn is not None else None
+        for e in self._engines.values():
+            e.close()
+        self._engines = {}
 
     def install_ip_adapter(self, adapter):
         """adapter: what ip_adapter.load_ip_adapter returns, or None = remove it.  The weight table - and with it the arena - changes, so
@@ -88,7 +103,7 @@ class HipUNet2DConditionModel(IPAdapterMixin):
                 raise RuntimeError("HipUNet2DConditionModel: no weights loaded (call load_state_dict)")
             try:
                 e = Engine(self.config_dict, h, w, device=self.device_index, max_streams=self.max_streams,
-                           max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens)
+                           max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens, controlnet=self._cn_config)
                 try:
                     if empty:
                         if donor is not None:
@@ -102,11 +117,11 @@ class HipUNet2DConditionModel(IPAdapterMixin):
                         # otherwise the packed arena arrives by launcher.broadcast_weights
                     elif isinstance(self._state_dict, str) and self._state_dict.startswith("random"):
                         e.init_random_weights(seed=int(self._state_dict[6:] or 0))      # "random<seed>": benchmarks without checkpoints
-                        for name, t in (self._ip_weights or {}).items():
+                        for name, t in {**(self._ip_weights or {}), **(self._cn_weights or {})}.items():
                             e.bind_weight(name, t.to(f"cuda:{self.device_index}"))
                         e.synchronize()
-                    elif self._ip_weights:
-                        e.load_state_dict({**self._state_dict, **self._ip_weights})
+                    elif self._ip_weights or self._cn_weights:
+                        e.load_state_dict({**self._state_dict, **(self._ip_weights or {}), **(self._cn_weights or {})})
                     else:
                         e.load_state_dict(self._state_dict)
                     if self.freeu is not None:
