@@ -74,6 +74,13 @@ typedef struct rt_config {
                                          * registered, allocated or launched and the weight table is the reference's state_dict layout */
     int control_hint_channels;          /* channels of the hint image (0 = 3) */
     int control_embed_channels[4];      /* channels of the hint embedder's four stages (all 0 = 16, 32, 96, 256); each a multiple of 8 */
+    int lora_rank;                      /* rank columns R of the regional LoRA adapters (rt_set_lora_scales; csrc/lora.hip): 0 = none - what a
+                                         * zero-initialised struct gets: nothing new is registered, allocated or launched and the weight table is the
+                                         * reference's state_dict layout - or a multiple of 16 up to 128: each of the eight attention projections
+                                         * attn{1,2}.{to_q,to_k,to_v,to_out.0} of every transformer block of the main UNet (never the ControlNet copy)
+                                         * registers lora.<module>.down.weight [R, K], lora.<module>.up.weight [N, R] and
+                                         * lora.<module>.alpha_over_rank [R] in the same arena, packed like the base weight they sit beside, and the
+                                         * engine keeps the padded bf16 prompt embeddings (max_prompts * 96 * max_keys / 77 rows) for the attn2 caches */
 } rt_config;
 
 typedef struct rt_engine rt_engine;
@@ -140,6 +147,29 @@ int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts_ho
 int rt_set_control_hint(rt_engine* e, const float* hint, int h, int w);
 int rt_control_embedding_read(rt_engine* e, float* dst_dev, int* rows, int* cols);
 int rt_set_control_scales(rt_engine* e, const float* scales_host, int n_prompts);
+/* Regional LoRA (rt_config.lora_rank = R > 0; csrc/lora.hip): low-rank adapters kept UNMERGED and scaled per prompt slot.  The factors are
+ * ordinary weights (lora.<module>.down.weight / .up.weight / .alpha_over_rank, bound like any other; up to 4 adapters concatenated along
+ * the rank, each block zero-padded to a multiple of 16 columns, pad columns with alpha_over_rank 0).
+ * rt_set_lora_columns: the adapter (0 .. 3) every rank column belongs to, R host ints (all 0 after rt_create); the same for every module.
+ * rt_set_lora_scales: scales_host [n_prompts][4], one finite scale per prompt slot of rt_set_prompts and adapter (slots n_prompts .. are
+ *   0).  rt_set_prompts / rt_set_prompts_keys reset every scale to 0.  A bad argument (n_prompts, a non-finite scale, an engine without
+ *   adapters or without its weights) returns RT_E_INVALID / RT_E_STATE with the state unchanged.
+ * Stream b of a forward whose slot has a non-zero scale computes, on each of the eight projections, y = W x + bf16(f_b (x down^T)) up^T
+ * with f_b[j] = scale[slot(b)][adapter(j)] * alpha_over_rank[j] in fp32 (rt_op_lora_add), in place behind the projection's GEMM:
+ *   attn1 to_q / to_k (streams some stream attends with: an injected region stream attends with text_ref's Q and K, so its own to_q /
+ *   to_k adapters are moot while its to_v and to_out adapters act), to_v (into V^T), attn2 to_q, both to_out.0 (into the fp16 trunk: a
+ *   second rounding of the adapted rows, like the ControlNet add).  attn2 to_k / to_v cost nothing in a step: rt_set_lora_scales rebuilds
+ *   the K / V^T caches of the main UNet with the GEMMs of rt_set_prompts (same bits) and adds the term to the 96-row blocks of the slots
+ *   with a non-zero scale; all scales back to 0 leaves the bits rt_set_prompts left.
+ * A stream whose slot has all-zero scales is in no new launch and keeps its bits; an adapted stream's bits do not depend on its
+ * neighbours; with every scale 0 no new kernel is launched.  The ControlNet copy runs without adapters.  Nothing is allocated in a step,
+ * which stays capturable. */
+int rt_set_lora_columns(rt_engine* e, const int* col_adapter_host, int R);
+/* Test seam: the device addresses of the attn2 K / V^T caches of transformer block idx of the main UNet (0 .. rt_attn_module_count / 2 - 1, in
+ * execution order; [max_prompts * KP, H * DP] and [H * DP, max_prompts * KP] bf16, bytes_each bytes each) - what rt_set_prompts fills and
+ * rt_set_lora_scales adapts. */
+int rt_attn_cache_info(rt_engine* e, int idx, void** kcache, void** vtcache, long long* bytes_each);
+int rt_set_lora_scales(rt_engine* e, const float* scales_host /* [n_prompts][4] */, int n_prompts);
 /* region masks (model.masks, rd.py:97,119-128 / xl.py:775,810-821): [R,4,h,w] f32 */
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
 /* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables.
@@ -257,7 +287,9 @@ enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_
        RT_PROF_IP_ATTN = 7 /* the image-prompt term of attn2 (ipattn.hip; rt_set_image_prompts): FLOPs = 4*H*N*d*(image tokens of the launch's
                             * streams), bytes = Q read once + O read and written once for the streams that carry an image */,
        RT_PROF_CONTROL_ADD = 8 /* the ControlNet residual add (control.hip; rt_set_control_scales), priced in bytes: the fp32 residual read once, the
-                                * fp16 skip read and written once, for the controlled streams */ };
+                                * fp16 skip read and written once, for the controlled streams */,
+       RT_PROF_LORA = 9 /* the regional LoRA term of one projection (lora.hip; rt_set_lora_scales), for the adapted streams of the launch:
+                         * FLOPs = 2 * rows * R * (K + N), bytes = X read once + Y read and written once */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
 int rt_profile_read(rt_engine* e, int kernel_class, int* count, double* total_ms, double* total_flops);
 /* as rt_profile_read, plus the ALGORITHMIC HBM bytes of the launches (attention store: the fp32 accumulator read + written once and the
@@ -320,6 +352,23 @@ int rt_op_attention_keys(const void* Q, int ldq, const void* K, int ldk, const v
  * Each entry is a function of itself alone: deterministic and batch invariant. */
 int rt_op_ip_attention(const void* Q, int ldq, const void* Kip, int ldk, const void* VTip, int ldvt, void* O, int ldo,
                        const int* slot_host, const int* count_host, const float* scale_host, int B, int H, int N, int DP, void* stream);
+/* The unmerged low-rank (LoRA) term of a projection (csrc/lora.hip), added in place into that projection's output, per stream.  Up to
+ * 4 adapters are concatenated along the rank into R rank columns (R % 16 == 0, 16 <= R <= 128; every adapter's block zero-padded to a
+ * multiple of 16): down [R, ldd] bf16 (K contiguous), up [N, ldu] bf16 (R contiguous), alpha_over_rank [R] f32 and col_adapter [R] int32
+ * (0 .. 3) on the device, 16-byte aligned.  Batch entry b with its rows at row_host[b] (a multiple of 8) and scale_host[4 b + l] for
+ * adapter l (finite), f_b[j] = scale_host[4 b + col_adapter[j]] * alpha_over_rank[j]:
+ *   T[m, j]  = sum_k X[row_b + m, k] down[j, k]                      bf16 operands, fp32 accumulation
+ *   Ts[m, j] = bf16(f_b[j] T[m, j])                                  the fp32 factor is applied BEFORE the one bf16 rounding
+ *   Y[m, n]  = round(fp32(Y[m, n]) + sum_j Ts[m, j] up[n, j])        ONE rounding to Y's type
+ * form 0: Y bf16 [*, ldy], element (row_b + m, n); form 1: Y bf16 transposed [N, ldy], element (n, row_b + m); form 2: Y fp16 as form 0.
+ * X [*, ldx] bf16.  rows % 8 == 0, K % 8 == 0, N % 8 == 0, leading dimensions % 8 == 0, B <= 16.  An entry whose four scales are all 0 is
+ * not in the grid and keeps its bytes; with no entry left nothing is launched (*launched, optional: the entries in the grid).  An
+ * element whose term is exactly 0 (rows of `up` that are zero: head padding) keeps its bits.  Each row is a function of itself alone:
+ * deterministic and batch invariant.  The packed weights carry whatever the base projection's pack carries (head padding, to_q's
+ * d^-1/2 log2 e): the kernel knows nothing of heads. */
+int rt_op_lora_add(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank,
+                   const int* col_adapter, void* Y, int ldy, int form, const int* row_host, const float* scale_host, int B, int rows, int K,
+                   int N, int R, int* launched, void* stream);
 /* Host-only (no GPU): the partition of a self-attention launch into shared-probability units (round 6; csrc/attention.hip).  Streams that
  * attend with the same (q_src, k_src) - text_ref and the region streams that take its probabilities, attention_processor.py:522-524 - are dealt
  * G at a time into units that compute softmax(QK^T) once; mode 0 = the shape rule (tokens >= 2048: units of four in their own launch, else

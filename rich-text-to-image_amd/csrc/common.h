@@ -174,7 +174,7 @@ struct GemmArgs {
 int gemm_ln_emit_bn(const GemmArgs& a);                 // column-tile width (160 / 320) of the partials launch_gemm(a) with a.ln_emit set would leave; 0: this route has no such epilogue
 bool gemm_ln_fold_ok(const GemmArgs& a);                // launch_gemm(a) with a.ln_part set has a folded instantiation
 bool gemm16_ln_variant_ok(const GemmArgs& a, int v);    // gemm16.hip: variant v has the LayerNorm-fold instantiation a.ln_part / a.ln_emit ask for
-void launch_ln_partials(const f16_t* x, bf16_t* xb, float* part, int rows, int C, int bn, hipStream_t st);      // stand-alone producer of xb + partials (column tiles of bn = 160 / 320) from an fp16 trunk (norm.hip)
+void launch_ln_partials(const f16_t* x, bf16_t* xb, float* part, int rows, int C, int bn, hipStream_t st, int part_ld = 0);      // (part_ld: the rows are a run inside a partials array of that many rows) stand-alone producer of xb + partials (column tiles of bn = 160 / 320) from an fp16 trunk (norm.hip)
 void launch_ln_fold_derive(const bf16_t* W, int ldw, const float* bias, const float* gamma, const float* beta, int N, int K,
                            bf16_t* Wf, float* sc, hipStream_t st);                         // W' = bf16(gamma W), sc[n] = (row sum of W', bias + W beta)
 int gemm16_variant_bn(int v);                           // column-tile width of a gemm16 variant
@@ -305,6 +305,10 @@ void launch_crossmw(const AttnArgs& a, hipStream_t st);
 // keys (Kip [*, ldk] 16 rows per slot, VTip [H*DP, ldvt] 16 columns per slot); host arrays; slot < 0 or scale == 0: the stream is not launched
 void launch_ip_attention(const bf16_t* Q, int ldq, const bf16_t* Kip, int ldk, const bf16_t* VTip, int ldvt, bf16_t* O, int ldo, const int* slot,
                          const int* count, const float* scale, int B, int H, int N, int DP, hipStream_t st);
+// lora.hip: the unmerged low-rank term Y += bf16(f_b (X down^T)) up^T in place, per stream (form 0 bf16 row-major, 1 bf16 transposed [N, ldy],
+// 2 fp16 row-major); row / scale [B][4] are host arrays; a stream whose scales are all 0 is not launched; returns the streams in the grid
+int launch_lora_add(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const bf16_t* up, int ldu, const float* aor, const int* adapter, void* Y,
+                    int ldy, int form, const int* row, const float* scale, int B, int rows, int K, int N, int R, hipStream_t st);
 bool gemm_cross77_enabled();      // debug bit 19 clear
 int attention_units_plan_host(const int* q_src, const int* k_src, int B, int N, int DP, int mode, int* launch_of, int* unit_of, int* members_of);   // host-only: the partition launch_attention would take
 void gemm16_set_tall(int on);        // (A/B) rt_op_gemm_debug bit 27

@@ -76,6 +76,7 @@ struct ResnetP {
     MatW c1, c2, temb, sc;
     bool has_sc = false;
 };
+struct LoraW { bf16_t* down = nullptr; bf16_t* up = nullptr; float* aor = nullptr; int K = 0, N = 0; };      // down [R, K], up [N, R], alpha / rank [R]
 struct TBlockP {
     NormW ln1, ln2, ln3;
     MatW qk1, v1, out1, q2, k2, v2, out2, ff1, ff2;
@@ -89,6 +90,9 @@ struct TBlockP {
     MatW kip, vip;
     bf16_t* kipcache = nullptr;  // [maxP*16, H*DP]   a slot's valid image tokens come first, the rest of its 16 rows are zero
     bf16_t* vtipcache = nullptr; // [H*DP, maxP*16]
+    // regional LoRA (rt_config.lora_rank > 0, main UNet only; lora.hip): the factors of the eight attention projections, packed like the
+    // base weight they sit beside - index 4 a + {0 to_q, 1 to_k, 2 to_v, 3 to_out.0} of attn(a + 1)
+    LoraW lora[8];
     // token-map attention store: index 0 = attn1, 1 = attn2
     std::string mod_name[2];
     float* store[2] = {nullptr, nullptr};
@@ -401,6 +405,18 @@ struct rt_engine {
     // sizes both to max_prompts, rt_set_prompts zeroes the scales
     std::vector<int> ip_count;
     std::vector<float> ip_scale;
+    // rt_set_lora_scales (rt_config.lora_rank > 0): [max_prompts][4] adapter scales per prompt slot, zeroed by rt_set_prompts; the padded bf16
+    // prompt embeddings rt_set_prompts builds (kept, so that the attn2 caches can be rebuilt and adapted: [max_prompts * KP, D]); the adapter
+    // of every rank column (device: the kernel reads it; all 0 until rt_set_lora_columns); whether the attn2 caches carry a LoRA term
+    std::vector<float> lora_scale;
+    bf16_t* lora_ctx = nullptr;
+    int* lora_col = nullptr;
+    bool lora_cache_dirty = false;
+    bool lora_on(int slot) const {
+        if (cfg.lora_rank <= 0) return false;
+        for (int l = 0; l < 4; ++l) if (lora_scale[(size_t)slot * 4 + l] != 0.f) return true;
+        return false;
+    }
     int KP() const { return 96 * (cfg.max_keys / 77); }      // rows per prompt in the K / V^T caches and the multiplier tables
     float* aug_emb = nullptr;        // [maxP, temb_dim] (zeros when no addition embedding)
     float* wabs = nullptr;           // [2, KP]
@@ -621,6 +637,32 @@ struct rt_engine {
                 };
                 mkf(k.qk1, k.qk1f, k.qk1s); mkf(k.v1, k.v1f, k.v1s); mkf(k.q2, k.q2f, k.q2s); mkf(k.ff1, k.ff1f, k.ff1s);
             }
+            if (cfg.lora_rank > 0 && !building_control) {          // (the control copy runs without adapters)
+                const int R = cfg.lora_rank;
+                static const char* leaf[4] = {"to_q", "to_k", "to_v", "to_out.0"};
+                for (int a = 0; a < 2; ++a)
+                    for (int j = 0; j < 4; ++j) {
+                        const std::string m = "lora." + b + ".attn" + std::to_string(a + 1) + "." + leaf[j];
+                        LoraW& w = k.lora[4 * a + j];
+                        const int Kin = a == 1 && (j == 1 || j == 2) ? D : C;      // attn2's to_k / to_v read the prompt embeddings
+                        w.K = j == 3 ? HD : Kin; w.N = j == 3 ? C : HD;
+                        w.down = (bf16_t*)arena.alloc((size_t)R * w.K * 2);
+                        w.up = (bf16_t*)arena.alloc((size_t)w.N * R * 2);
+                        w.aor = (float*)arena.alloc((size_t)R * 4);
+                        if (j == 3) {      // to_out.0: `down` reads the head-padded attention output (mk_outproj's columns), `up` is plain
+                            PackArgs p{}; p.dst = w.down; p.rows = R; p.cols = HD; p.ld_dst = HD; p.row_map = PACK_ROWS_ID;
+                            p.c_inner = t.DP; p.ci_valid = t.d; p.s_r = (long)heads * t.d; p.s_co = t.d; p.s_ci = 1; p.scale = 1.f;
+                            add_slot(m + ".down.weight", {R, heads * t.d}, p);
+                            add_slot(m + ".up.weight", {C, R}, pk_matrix(w.up, C, R, R, R));
+                        } else {           // to_q / to_k / to_v: `up` rows head-padded like mk_headproj's, to_q's with the same qscale
+                            add_slot(m + ".down.weight", {R, Kin}, pk_matrix(w.down, R, Kin, Kin, Kin));
+                            PackArgs p = pk_matrix(w.up, HD, R, R, R);
+                            p.row_map = PACK_ROWS_HEADPAD; p.rm_a = t.DP; p.rm_b = t.d; p.scale = j == 0 ? qscale : 1.f;
+                            add_slot(m + ".up.weight", {heads * t.d, R}, p);
+                        }
+                        add_slot(m + ".alpha_over_rank", {R}, pk_vec(w.aor, R));
+                    }
+            }
             t.blocks.push_back(k);
         }
         t.pout = mk_linear(name + ".proj_out", C, C, true, !cfg.use_linear_projection);
@@ -773,6 +815,10 @@ struct rt_engine {
         gpred = (float*)sarena.alloc((size_t)2 * HW * 4 * 4);
         gpartials = (double*)sarena.alloc((size_t)cdiv((int)HW, 256) * RT_GUIDED_SERIES * 8);
         gfactors = (float*)sarena.alloc(2 * 4);
+        if (cfg.lora_rank > 0) {         // regional LoRA: behind everything else as well
+            lora_ctx = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * cfg.cross_attention_dim * 2);
+            lora_col = (int*)sarena.alloc((size_t)cfg.lora_rank * 4);
+        }
         if (cfg.controlnet) build_control_plan();
     }
 
@@ -927,6 +973,33 @@ struct rt_engine {
             // partials of the trunk as it stands, for the LayerNorm that follows: from the producer's epilogue (`em` was passed to it) or here
             auto partials_after = [&](bool emitted) { if (!emitted && !dry()) launch_ln_partials(hcur, xb, part, M, C, ln_bn, stream); };
             LnFold em; em.emit = part; em.copy = xb;
+            // regional LoRA (rt_set_lora_scales): the adapted streams of this forward - those whose prompt slot has a non-zero scale - get the
+            // low-rank term added behind each of the eight attention projections; every other stream is in none of these launches
+            int l_rows[RT_MAXB]; float l_sc[RT_MAXB * 4];
+            bool any_lora = false;
+            for (int b = 0; b < B; ++b) {
+                const bool on = !dry() && !in.control && lora_on(in.prompt[b]);
+                l_rows[b] = b * HW;
+                for (int l = 0; l < 4; ++l) l_sc[4 * b + l] = on ? lora_scale[(size_t)in.prompt[b] * 4 + l] : 0.f;
+                any_lora = any_lora || on;
+            }
+            auto l_on = [&](int b) { return l_sc[4 * b] != 0.f || l_sc[4 * b + 1] != 0.f || l_sc[4 * b + 2] != 0.f || l_sc[4 * b + 3] != 0.f; };
+            // run f(first stream, streams) over the maximal runs of adapted streams (the row-wise kernels below take a run as one launch)
+            auto l_runs = [&](auto f) {
+                for (int b = 0; b < B;) {
+                    if (!l_on(b)) { ++b; continue; }
+                    int e = b; while (e < B && l_on(e)) ++e;
+                    f(b, e - b); b = e;
+                }
+            };
+            // a folded LayerNorm is never materialised: the adapters' input is computed for the adapted rows only, into `n`
+            auto l_norm = [&](const NormW& ln, bf16_t* n) {
+                l_runs([&](int b, int nb) { launch_layernorm(hcur + (size_t)b * HW * C, 1, ln.g, ln.b, n + (size_t)b * HW * C, nb * HW, C, 1e-5f, stream); });
+            };
+            // the adapted rows of the trunk changed behind a GEMM that emitted their LayerNorm partials and bf16 copy: recompute those rows'
+            auto l_partials = [&]() {
+                l_runs([&](int b, int nb) { launch_ln_partials(hcur + (size_t)b * HW * C, xb + (size_t)b * HW * C, part + (size_t)b * HW * 4, nb * HW, C, ln_bn, stream, M); });
+            };
             {
                 Scope s2(ws);
                 bf16_t* g = ws.b16((size_t)M * C);
@@ -954,6 +1027,14 @@ struct rt_engine {
                     LnFold lv; lv.part = part; lv.npair = npair; lv.ld = M; lv.s = k.v1s;
                     gemm_qk_vt(xb, C, k.qk1f, nqk * HW, qk, 2 * HD, k.v1f, M, vt, M, &lq, &lv);
                 } else gemm_qk_vt(n, C, k.qk1, nqk * HW, qk, 2 * HD, k.v1, M, vt, M);
+                if (any_lora) {
+                    // (an injected region stream attends with text_ref's Q and K - rows >= nqk are not even computed -, so its own to_q /
+                    // to_k adapters are moot; its to_v and to_out adapters act)
+                    if (fold1) l_norm(k.ln1, n);
+                    lora_add(k.lora[0], n, C, qk, 2 * HD, 0, l_rows, l_sc, nqk, HW);
+                    lora_add(k.lora[1], n, C, qk + HD, 2 * HD, 0, l_rows, l_sc, nqk, HW);
+                    lora_add(k.lora[2], n, C, vt, M, 1, l_rows, l_sc, B, HW);
+                }
                 if (!dry()) {
                     // a layer whose map is recorded in this call: the attention launch leaves the softmax statistics of the recorded stream,
                     // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
@@ -973,7 +1054,9 @@ struct rt_engine {
                     }
                 }
                 gemm(o, HD, k.out1, M, hcur, C, EPI_F16, hcur, C, fold2 && emit_out ? &em : nullptr);
+                if (any_lora) lora_add(k.lora[3], o, HD, hcur, C, 2, l_rows, l_sc, B, HW);      // a second fp16 rounding of the adapted rows (control_add_kernel's precedent)
                 if (fold2) partials_after(emit_out);
+                if (fold2 && emit_out && any_lora) l_partials();
                 // --- attn2 (cross, K/V from the per-prompt cache; font-size softmax on flagged streams)
                 if (!fold2) layernorm(hcur, k.ln2, n, M);
                 // the route (cross_route): a layer with its map enabled counts as recorded whether or not this call is past the tenth
@@ -995,7 +1078,8 @@ struct rt_engine {
                 // (Only RT_PROBES builds with their debug switches on ever reach the one-launch kinds.  The dry planning forward of an
                 // engine that can hold images takes the two-launch route as well, so that the to_q GEMM a launch with an image runs
                 // has been planned: its split-K scratch is recorded like every other GEMM's.)
-                if ((any_ip || (dry() && cfg.ip_tokens > 0 && !in.control)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
+                // (regional LoRA likewise: to_q's term is added to a materialised Q, to_out's behind the GEMM)
+                if ((any_ip || any_lora || (dry() && (cfg.ip_tokens > 0 || cfg.lora_rank > 0) && !in.control)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
                     route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2, false);
                 if (route.kind == CrossRoute::XBLOCK) {
                     if (!dry()) {
@@ -1015,6 +1099,10 @@ struct rt_engine {
                     LnFold l2; l2.part = part; l2.npair = npair; l2.ld = M; l2.s = k.q2s;
                     gemm(xb, C, k.q2f, M, qk, HD, EPI_BF16, nullptr, 0, &l2);
                 } else gemm(n, C, k.q2, M, qk, HD, EPI_BF16);
+                if (any_lora) {
+                    if (fold2) l_norm(k.ln2, n);
+                    lora_add(k.lora[4], n, C, qk, HD, 0, l_rows, l_sc, B, HW);
+                }
                 if (!dry()) {
                     // (a recorded layer on cross77_kernel hands its statistics over as attn1 does, from the eleventh recorded call on)
                     const AttnArgs a = unet_cross_attn_args(AttnIO{qk, HD, k.kcache, HD, k.vtcache, ldvt2, o, HD}, in.prompt, wset2, nkeys, wabs, wsgn, B, t.heads, HW,
@@ -1041,7 +1129,9 @@ struct rt_engine {
                 }
                 const bool out2_done = route.kind == CrossRoute::XBLOCK;      // to_out + residual were part of that launch
                 if (!out2_done) gemm(o, HD, k.out2, M, hcur, C, EPI_F16, hcur, C, fold3 && emit_out ? &em : nullptr);
+                if (any_lora) lora_add(k.lora[7], o, HD, hcur, C, 2, l_rows, l_sc, B, HW);      // (any_lora: never the one-launch block)
                 if (fold3) partials_after(!out2_done && emit_out);
+                if (fold3 && !out2_done && emit_out && any_lora) l_partials();
                 // --- GEGLU feed-forward (attention.py:209-304)
                 bf16_t* gg = ws.b16((size_t)M * 4 * C);
                 if (fold3) {
@@ -1346,6 +1436,7 @@ struct rt_engine {
         const int D = cfg.cross_attention_dim, KPr = KP();
         Scope sc(ws);
         bf16_t* ctx = ws.b16((size_t)cfg.max_prompts * KPr * D);
+        if (cfg.lora_rank > 0) ctx = lora_ctx;                        // kept for rt_set_lora_scales (the scratch above stays reserved: same workspace plan)
         // rows past a prompt's own keys are zeros: their K / V^T rows are finite, and masked by every attention kernel
         for (int p_ = 0; p_ < P; ++p_)
             launch_pad_ctx(pe + (size_t)p_ * L * D, ctx + (size_t)p_ * KPr * D, counts ? counts[p_] : L, KPr, D, stream);
@@ -1392,7 +1483,64 @@ struct rt_engine {
         for (int p_ = 0; p_ < P; ++p_) prompt_keys[p_] = counts ? counts[p_] : L;
         std::fill(ip_scale.begin(), ip_scale.end(), 0.f);              // the slots change meaning: no prompt has an image until rt_set_image_prompts
         std::fill(ctl.scale.begin(), ctl.scale.end(), 0.f);            // ... and none is controlled until rt_set_control_scales (the hint stays)
+        std::fill(lora_scale.begin(), lora_scale.end(), 0.f);          // ... and none is adapted until rt_set_lora_scales (the caches above carry no term)
+        lora_cache_dirty = false;
         HIP_CHECK(hipStreamSynchronize(stream));   // host buffers (time_ids) may go away
+    }
+
+    // The regional LoRA term of one projection for up to RT_MAXB streams (rows_at / sc4 host arrays): profiled as RT_PROF_LORA
+    void lora_add(const LoraW& w, const bf16_t* X, int ldx, void* Y, int ldy, int form, const int* rows_at, const float* sc4, int B, int rows) {
+        double nact = 0;
+        for (int b = 0; b < B; ++b) nact += sc4[4 * b] != 0.f || sc4[4 * b + 1] != 0.f || sc4[4 * b + 2] != 0.f || sc4[4 * b + 3] != 0.f;
+        if (nact == 0) return;
+        const int R = cfg.lora_rank;
+        prof_begin(RT_PROF_LORA, 2.0 * nact * rows * R * ((double)w.K + w.N), 2.0 * nact * rows * ((double)w.K + 2.0 * w.N));
+        launch_lora_add(X, ldx, w.down, w.K, w.up, R, w.aor, lora_col, Y, ldy, form, rows_at, sc4, B, rows, w.K, w.N, R, stream);
+        prof_end();
+    }
+    void set_lora_columns(const int* col, int R) {
+        RT_REQUIRE(cfg.lora_rank > 0, "set_lora_columns: the engine was built without regional LoRA (rt_config.lora_rank == 0)");
+        RT_REQUIRE(col && R == cfg.lora_rank, "set_lora_columns: one adapter index per rank column (rt_config.lora_rank of them)");
+        for (int j = 0; j < R; ++j) RT_REQUIRE(col[j] >= 0 && col[j] < 4, "set_lora_columns: an adapter index must be 0 .. 3");
+        for (float s : lora_scale) RT_REQUIRE(s == 0.f, "set_lora_columns: scales are set (rt_set_lora_scales with zeros, or rt_set_prompts, first)");
+        HIP_CHECK(hipMemcpyAsync(lora_col, col, (size_t)R * 4, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    // scales [P][4].  Validates everything before it touches the state.  The attn2 K / V^T caches of the main UNet: rebuilt with the GEMMs
+    // of set_prompts (same arguments, same bits) when they carry a term, then the term of every slot with a non-zero scale is added to
+    // that slot's KP rows - row-major into kcache, transposed into vtcache.
+    void set_lora_scales(const float* scales, int P) {
+        RT_REQUIRE(cfg.lora_rank > 0, "set_lora_scales: the engine was built without regional LoRA (rt_config.lora_rank == 0)");
+        RT_REQUIRE(scales, "set_lora_scales: scales");
+        RT_REQUIRE(P >= 1 && P <= n_prompts, "set_lora_scales: more slots than prompts set (rt_set_prompts first)");
+        bool any = false;
+        for (int i = 0; i < 4 * P; ++i) { RT_REQUIRE(std::isfinite(scales[i]), "set_lora_scales: a scale must be finite"); any = any || scales[i] != 0.f; }
+        require_bound();
+        const int D = cfg.cross_attention_dim, KPr = KP();
+        if (lora_cache_dirty) {
+            cur_hw = 96;
+            for_each_tblock([&](TransformerP& t, TBlockP& k) {
+                gemm(lora_ctx, D, k.k2, n_prompts * KPr, k.kcache, t.heads * t.DP, EPI_BF16);
+                gemm_vt(k.v2, lora_ctx, D, n_prompts * KPr, k.vtcache, cfg.max_prompts * KPr);
+            });
+            cur_hw = 0;
+            lora_cache_dirty = false;
+        }
+        for (int p_ = 0; p_ < cfg.max_prompts; ++p_)
+            for (int l = 0; l < 4; ++l) lora_scale[(size_t)p_ * 4 + l] = p_ < P ? scales[4 * p_ + l] : 0.f;
+        if (any) {
+            for (int p0 = 0; p0 < P; p0 += RT_MAXB) {
+                const int nb = std::min(RT_MAXB, P - p0);
+                int rows_at[RT_MAXB];
+                for (int b = 0; b < nb; ++b) rows_at[b] = (p0 + b) * KPr;
+                for_each_tblock([&](TransformerP& t, TBlockP& k) {
+                    lora_add(k.lora[5], lora_ctx, D, k.kcache, t.heads * t.DP, 0, rows_at, scales + 4 * p0, nb, KPr);
+                    lora_add(k.lora[6], lora_ctx, D, k.vtcache, cfg.max_prompts * KPr, 1, rows_at, scales + 4 * p0, nb, KPr);
+                });
+            }
+            lora_cache_dirty = true;
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
     }
 
     // tokens [P, ip_tokens, D] fp32 (device): slot p's first counts[p] rows are its image tokens.  Validates everything before it touches the state.
@@ -1591,8 +1739,10 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         RT_REQUIRE(cfg->max_keys == 0 || cfg->max_keys == 77 || cfg->max_keys == 154 || cfg->max_keys == 231, "rt_create: max_keys must be 77, 154 or 231 (0 = 77)");
         RT_REQUIRE(cfg->ip_tokens >= 0 && cfg->ip_tokens <= 16, "rt_create: ip_tokens must be 0 (no image prompts) or 1 .. 16");
         RT_REQUIRE(cfg->controlnet == 0 || cfg->controlnet == 1, "rt_create: controlnet must be 0 or 1");
+        RT_REQUIRE(cfg->lora_rank >= 0 && cfg->lora_rank <= 128 && cfg->lora_rank % 16 == 0, "rt_create: lora_rank must be 0 (no regional LoRA) or a multiple of 16 up to 128");
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
+        e->lora_scale.assign((size_t)std::max(1, cfg->max_prompts) * 4, 0.f);
         e->ip_count.assign((size_t)std::max(1, cfg->max_prompts), 0); e->ip_scale.assign((size_t)std::max(1, cfg->max_prompts), 0.f);
         if (e->cfg.max_keys == 0) e->cfg.max_keys = 77;
         e->prompt_keys.assign((size_t)std::max(1, e->cfg.max_prompts), 77);
@@ -1760,6 +1910,22 @@ int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts, c
 }
 int rt_set_control_hint(rt_engine* e, const float* hint, int h, int w) { RT_TRY(e, { need_device(e); e->set_control_hint(hint, h, w); }) }
 int rt_set_control_scales(rt_engine* e, const float* scales, int P) { RT_TRY(e, { need_device(e); e->set_control_scales(scales, P); }) }
+int rt_attn_cache_info(rt_engine* e, int idx, void** kcache, void** vtcache, long long* bytes_each) {
+    RT_TRY(e, {
+        need_device(e);
+        RT_REQUIRE(kcache && vtcache && bytes_each, "rt_attn_cache_info: null outputs");
+        int i = 0; bool found = false;
+        e->for_each_tblock([&](TransformerP& t, TBlockP& k) {
+            if (i++ != idx) return;
+            *kcache = k.kcache; *vtcache = k.vtcache;
+            *bytes_each = (long long)e->cfg.max_prompts * e->KP() * t.heads * t.DP * 2;
+            found = true;
+        });
+        RT_REQUIRE(found, "rt_attn_cache_info: block index out of range (rt_attn_module_count / 2 blocks)");
+    })
+}
+int rt_set_lora_columns(rt_engine* e, const int* col, int R) { RT_TRY(e, { need_device(e); e->set_lora_columns(col, R); }) }
+int rt_set_lora_scales(rt_engine* e, const float* scales, int P) { RT_TRY(e, { need_device(e); e->set_lora_scales(scales, P); }) }
 int rt_control_embedding_read(rt_engine* e, float* dst, int* rows, int* cols) {
     RT_TRY(e, {
         need_device(e);
@@ -2566,6 +2732,16 @@ int rt_op_control_add(void* skip_f16, long long skip_stride, int lds, const floa
     OP_TRY({
         RT_REQUIRE(skip_f16 && r && stream_host && scale_host && skip_stride >= 0 && r_stride >= 0, "rt_op_control_add: null argument / negative stride");
         launch_control_add((f16_t*)skip_f16, (size_t)skip_stride, lds, r, (size_t)r_stride, ldr, stream_host, scale_host, n, B, HW, C, (hipStream_t)stream);
+    })
+}
+int rt_op_lora_add(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank, const int* col_adapter,
+                   void* Y, int ldy, int form, const int* row_host, const float* scale_host, int B, int rows, int K, int N, int R, int* launched,
+                   void* stream) {
+    OP_TRY({
+        RT_REQUIRE(X && down && up && alpha_over_rank && col_adapter && Y && row_host && scale_host, "rt_op_lora_add: null argument");
+        const int n = launch_lora_add((const bf16_t*)X, ldx, (const bf16_t*)down, ldd, (const bf16_t*)up, ldu, alpha_over_rank, col_adapter, Y, ldy, form,
+                                      row_host, scale_host, B, rows, K, N, R, (hipStream_t)stream);
+        if (launched) *launched = n;
     })
 }
 int rt_op_cast_bf16(const float* x, void* out_bf16, long long n, void* stream) {

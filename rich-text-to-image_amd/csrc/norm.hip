@@ -744,7 +744,7 @@ void launch_ln_fold_derive(const bf16_t* W, int ldw, const float* bias, const fl
 // j, j + 4, j + 8 per quarter of an 80-column block; the quarters as (q0 + q1) + (q2 + q3); the blocks of a tile in ascending order).
 // (The epilogue rounds xb from the fp32 value it also rounds the trunk from; here only the fp16 trunk exists: same statistics of its own
 //  xb, not the same bits as an emitting producer - which of the two a layer uses is a function of its shape alone.)
-__global__ __launch_bounds__(256) void ln_partials_kernel(const f16_t* __restrict__ x, bf16_t* __restrict__ xb, float* __restrict__ part, int rows, int C, int bn) {
+__global__ __launch_bounds__(256) void ln_partials_kernel(const f16_t* __restrict__ x, bf16_t* __restrict__ xb, float* __restrict__ part, int rows, int C, int bn, int part_ld) {
     const int ntn = C / bn, nb = bn / 80;
     const long id = (long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long)rows * ntn) return;
@@ -780,11 +780,14 @@ __global__ __launch_bounds__(256) void ln_partials_kernel(const f16_t* __restric
         const float b1 = (q1[0] + q1[1]) + (q1[2] + q1[3]), b2 = (q2[0] + q2[1]) + (q2[2] + q2[3]);
         if (b == 0) { t1 = b1; t2 = b2; } else { t1 += b1; t2 += b2; }
     }
-    *((float2*)part + ((long)(tn >> 1) * rows + row) * 2 + (tn & 1)) = make_float2(t1, t2);
+    *((float2*)part + ((long)(tn >> 1) * part_ld + row) * 2 + (tn & 1)) = make_float2(t1, t2);
 }
-void launch_ln_partials(const f16_t* x, bf16_t* xb, float* part, int rows, int C, int bn, hipStream_t st) {
+// part_ld: rows of the partials array the `rows` rows are a run of (x, xb and part point at the run's first row); 0 = rows
+void launch_ln_partials(const f16_t* x, bf16_t* xb, float* part, int rows, int C, int bn, hipStream_t st, int part_ld) {
     RT_REQUIRE(rows > 0 && (bn == 160 || bn == 320) && C % (2 * bn) == 0 && C / bn <= 8, "ln_partials: column tiles of 160 / 320, an even number (at most 8) per row");
+    RT_REQUIRE(part_ld == 0 || part_ld >= rows, "ln_partials: a run of rows inside the partials array");
+    if (!part_ld) part_ld = rows;
     const long n = (long)rows * (C / bn);
-    hipLaunchKernelGGL(ln_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, xb, part, rows, C, bn);
+    hipLaunchKernelGGL(ln_partials_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, xb, part, rows, C, bn, part_ld);
     HIP_CHECK(hipGetLastError());
 }

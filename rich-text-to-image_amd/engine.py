@@ -58,6 +58,7 @@ class RtConfig(C.Structure):
         ("controlnet", C.c_int),
         ("control_hint_channels", C.c_int),
         ("control_embed_channels", C.c_int * 4),
+        ("lora_rank", C.c_int),
     ]
 
 
@@ -97,6 +98,7 @@ _SYMBOLS = [
     "rt_op_patchify", "rt_op_vit_embed", "rt_op_bidir_attention",
     "rt_op_latent_attention",
     "rt_set_control_hint", "rt_control_embedding_read", "rt_set_control_scales", "rt_op_control_add",
+    "rt_op_lora_add", "rt_set_lora_columns", "rt_set_lora_scales", "rt_attn_cache_info",
 ]
 
 
@@ -140,8 +142,9 @@ def _tup(v, n):
 CONTROL_EMBED_CHANNELS = (16, 32, 96, 256)      # diffusers' ControlNetModel default `conditioning_embedding_out_channels`
 
 
-def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None):
+def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None, lora_rank=0):
     """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window).
+    lora_rank: rank columns of the regional LoRA adapters (a multiple of 16 up to 128); 0 = none: the weight table is the reference's.
     ip_tokens: image tokens per prompt slot of an IP-Adapter (1 .. 16); 0 = none: the weight table is the reference's state_dict layout.
     controlnet: None = no ControlNet (likewise), or dict(embed_channels=(16, 32, 96, 256), hint_channels=3) - either key optional."""
     c = RtConfig()
@@ -171,6 +174,7 @@ def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_
     c.max_streams, c.max_prompts = max_streams, max_prompts
     c.max_keys = max_keys
     c.ip_tokens = int(ip_tokens)
+    c.lora_rank = int(lora_rank)
     if controlnet is not None:
         unknown = set(controlnet) - {"embed_channels", "hint_channels"}
         if unknown:
@@ -192,10 +196,12 @@ def _ptr(t):
 class Engine:
     """One engine = one GPU.  Mirrors the C ABI one to one; see include/rtdiff.h for semantics."""
 
-    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None):
+    def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None,
+                 lora_rank=0):
         self.lib = load_library()
         self.cfg_dict = dict(cfg_dict)
-        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens, controlnet)
+        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens, controlnet, lora_rank)
+        self.lora_rank = int(lora_rank)
         self.controlnet = dict(controlnet) if controlnet is not None else None
         self.max_keys = max_keys
         self.ip_tokens = int(ip_tokens)
@@ -245,6 +251,9 @@ class Engine:
         import torch
         dev = device or f"cuda:{self.device}"
         for name, shape in self.weight_table():
+            if name not in sd and name.startswith("lora."):          # no regional adapter resident (bind_regional_loras fills these): zero factors
+                self.bind_weight(name, torch.zeros(shape, device=dev))
+                continue
             if name not in sd:
                 raise RtError(-4, f"missing weight {name}")
             t = sd[name].to(dev, non_blocking=False)
@@ -346,6 +355,60 @@ class Engine:
         nothing new and keeps its bits).  set_prompts resets every scale to 0."""
         sc = [float(v) for v in scales]
         self._chk(self.lib.rt_set_control_scales(self.h, (C.c_float * max(1, len(sc)))(*sc), len(sc)))
+
+    # ---- regional LoRA (include/rtdiff.h: rt_set_lora_columns / rt_set_lora_scales; engines built with lora_rank > 0)
+    def bind_regional_loras(self, adapters):
+        """adapters: {name: modules} of regional_lora.parse_adapter, in load order (an empty dict: zero factors everywhere).  Binds the
+        lora.* slots of every adapted projection - the concatenation along the rank of regional_lora.concat_module, which the engine
+        packs like the base weight beside it - and the column -> adapter map.  Returns the adapter names in column order."""
+        import torch
+        from . import regional_lora as RL
+        dev = f"cuda:{self.device}"
+        R = self.lora_rank
+        if R <= 0:
+            raise RtError(-1, "bind_regional_loras: the engine was built without regional LoRA (lora_rank=0)")
+        layout = None
+        if adapters:
+            layout = RL.rank_layout(adapters)
+            if layout[3] > R:
+                raise ValueError(f"the adapters' padded ranks {dict(zip(layout[0], layout[1]))} add up to {layout[3]} rank columns; this engine was built for {R}")
+        col = [0] * R
+        table = dict(self.weight_table())
+        for name, shape in table.items():
+            if not name.startswith("lora.") or not name.endswith(".down.weight"):
+                continue
+            mod = name[len("lora."):-len(".down.weight")]
+            K, N = shape[1], table[f"lora.{mod}.up.weight"][0]
+            down, up, aor = torch.zeros(R, K), torch.zeros(N, R), torch.zeros(R)
+            if adapters:
+                d, u, a, c = RL.concat_module(adapters, mod, K, N, layout)
+                down[:d.shape[0]], up[:, :u.shape[1]], aor[:a.shape[0]] = d, u, a
+                col[:c.shape[0]] = [int(v) for v in c]
+            self.bind_weight(f"lora.{mod}.down.weight", down.to(dev))
+            self.bind_weight(f"lora.{mod}.up.weight", up.to(dev))
+            self.bind_weight(f"lora.{mod}.alpha_over_rank", aor.to(dev))
+        self.synchronize()
+        self._chk(self.lib.rt_set_lora_columns(self.h, (C.c_int * R)(*col), R))
+        return list(layout[0]) if layout else []
+
+    def set_lora_scales(self, scales):
+        """scales [P][<= 4]: per prompt slot of the last set_prompts, one finite scale per resident adapter (0 = a stream that runs that
+        prompt is not adapted: it is in no new launch and keeps its bits).  set_prompts resets every scale to 0."""
+        rows = [[float(s[l]) if l < len(s) else 0.0 for l in range(4)] for s in scales]
+        flat = [v for r in rows for v in r]
+        self._chk(self.lib.rt_set_lora_scales(self.h, (C.c_float * max(1, len(flat)))(*flat), len(rows)))
+
+    def attn_caches(self):
+        """Test seam (rt_attn_cache_info): the attn2 K / V^T caches of every transformer block of the main UNet, in execution order, as
+        a list of (kcache, vtcache) int16 views of the engine's own memory (bf16 bits)."""
+        import torch
+        from .launcher import _DevicePointer
+        out = []
+        for i in range(self.lib.rt_attn_module_count(self.h) // 2):
+            k, v, n = C.c_void_p(), C.c_void_p(), C.c_longlong()
+            self._chk(self.lib.rt_attn_cache_info(self.h, i, C.byref(k), C.byref(v), C.byref(n)))
+            out.append(tuple(torch.as_tensor(_DevicePointer(p.value, n.value), device=f"cuda:{self.device}").view(torch.int16) for p in (k, v)))
+        return out
 
     def control_embedding(self):
         """The cached hint embedding as fp32 [h w, C0] on the GPU, or None when no hint is set (test seam)."""
@@ -626,6 +689,41 @@ def ip_attention(Q, Kip, VTip, O, slots, counts, scales, H, N, DP):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return O
+
+
+LORA_FORMS = {"bf16": 0, "bf16_t": 1, "f16": 2}
+
+
+def lora_add(X, down, up, alpha_over_rank, col_adapter, Y, form, rows_at, scales, rows):
+    """The unmerged low-rank term of one projection alone (rt_op_lora_add), IN PLACE on Y: per batch entry b with its `rows` rows at
+    rows_at[b] and the adapter scales scales[b] (up to 4), Y += bf16(f_b (X down^T)) up^T, f_b[j] = scales[b][col_adapter[j]] *
+    alpha_over_rank[j].  X [*, >= K], down [R, >= K], up [N, >= R] bf16 2-D tensors (views with a row stride are fine: the stride is the
+    leading dimension), alpha_over_rank [R] fp32, col_adapter [R] int32; form "bf16": Y bf16 [*, >= N]; "bf16_t": Y bf16 [N, >= columns]
+    holding the transpose, entry b at columns rows_at[b] ...; "f16": Y fp16 [*, >= N].  An entry whose scales are all 0 is skipped.
+    Returns the number of entries launched."""
+    import torch
+    lib = load_library()
+    f = LORA_FORMS[form]
+    B = len(rows_at)
+    R, K = down.shape
+    N = up.shape[0]
+    for t in (X, down, up, Y):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.device == Y.device, "lora_add: [rows, ld] tensors on one device"
+    assert X.dtype == down.dtype == up.dtype == torch.bfloat16 and Y.dtype == (torch.float16 if f == 2 else torch.bfloat16), "lora_add: dtypes"
+    assert alpha_over_rank.dtype == torch.float32 and col_adapter.dtype == torch.int32 and alpha_over_rank.numel() == R == col_adapter.numel() == up.shape[1]
+    assert alpha_over_rank.is_contiguous() and col_adapter.is_contiguous() and X.shape[1] >= K and len(scales) == B
+    top = max(int(r) for r in rows_at) + rows
+    assert X.shape[0] >= top and (Y.shape[1] >= top and Y.shape[0] >= N if f == 1 else Y.shape[0] >= top and Y.shape[1] >= N), "lora_add: a stream outside the tensors"
+    sc = [float(s[l]) if l < len(s) else 0.0 for s in scales for l in range(4)]
+    n = C.c_int(0)
+    with torch.cuda.device(Y.device):
+        rc = lib.rt_op_lora_add(_ptr(X), int(X.stride(0)), _ptr(down), int(down.stride(0)), _ptr(up), int(up.stride(0)), _ptr(alpha_over_rank),
+                                _ptr(col_adapter), _ptr(Y), int(Y.stride(0)), f, (C.c_int * B)(*[int(v) for v in rows_at]), (C.c_float * (4 * B))(*sc),
+                                B, int(rows), int(K), int(N), int(R), C.byref(n), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return n.value
 
 
 def freeu(hidden, skip, H, W, b=1.0, s=1.0):

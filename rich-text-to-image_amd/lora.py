@@ -28,17 +28,18 @@ def _split(key):
     return None, None
 
 
-def merge_lora(unet_state_dict, lora_state_dict, scale=1.0):
-    """Returns (merged_state_dict, report).  report = dict(merged=[...], text_encoder=[...], alpha_default=[...])."""
+def resolve_targets(unet_state_dict, lora_state_dict):
+    """Key parsing alone, for all four layouts: -> (paths, groups, text_encoder) with paths = module path -> weight key of the UNet,
+    groups = module path -> {'down': t, 'up': t, 'alpha': t} in checkpoint order, text_encoder = the text-encoder keys (not resolved)."""
     paths, kohya = _targets(unet_state_dict)
     groups = {}
-    report = dict(merged=[], text_encoder=[], alpha_default=[])
+    text_encoder = []
     for key, t in lora_state_dict.items():
         mod, role = _split(key)
         if mod is None:
             raise KeyError(f"not a LoRA tensor: {key}")
         if mod.startswith("lora_te") or mod.startswith("text_encoder"):
-            report["text_encoder"].append(key)
+            text_encoder.append(key)
             continue
         if mod in kohya:
             path = kohya[mod]
@@ -51,6 +52,13 @@ def merge_lora(unet_state_dict, lora_state_dict, scale=1.0):
         if path not in paths:
             raise KeyError(f"LoRA tensor {key} targets '{path}', which is not a weight of this UNet")
         groups.setdefault(path, {})[role] = t
+    return paths, groups, text_encoder
+
+
+def merge_lora(unet_state_dict, lora_state_dict, scale=1.0):
+    """Returns (merged_state_dict, report).  report = dict(merged=[...], text_encoder=[...], alpha_default=[...])."""
+    paths, groups, text_encoder = resolve_targets(unet_state_dict, lora_state_dict)
+    report = dict(merged=[], text_encoder=text_encoder, alpha_default=[])
     out = dict(unet_state_dict)
     for path, g in groups.items():
         if "down" not in g or "up" not in g:

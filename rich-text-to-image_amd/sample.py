@@ -43,11 +43,23 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     `param['image_prompts']` (optional; ip_adapter.image_prompts_from_specs' result: dict(base=, regions=, negative=) of dict(file=,
     scale=)): the image prompts of THIS request on a pipeline with an IP-Adapter loaded - set for the call, restored after it; `base`
     holds in both passes, `regions` (by region number) in the rich pass; absent / None: the pipeline as it is.
+    `param['region_loras']` (optional; set_lora_scales' keyword arguments, regional_lora.lora_request_from_specs' result): the regional LoRA
+    scales of THIS request on a pipeline with adapters loaded - set for the call, restored after it; absent / None: the pipeline as it is.
     `param['control']` (optional; set_control's keyword arguments, controlnet.control_from_request / check_control_args' result: image=
     a file, scale=, regions=, negative=, start=, end=): the ControlNet hint and scales of THIS request on a pipeline with a ControlNet
     loaded - set for the call, restored after it; the hint is resized to the request's height x width; absent / None: the pipeline as it is."""
     args = (model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background, latents,
             init_image, strength, keep_source)
+    rl = param.get('region_loras')
+    if rl is not None:
+        if not getattr(model, 'regional_loras', None):
+            raise ValueError("region_loras needs regional LoRA adapters: none is loaded on this pipeline (load_regional_loras / --region_lora)")
+        keep_rl = getattr(model, 'lora_request', None)
+        model.set_lora_scales(**rl)
+        try:
+            return generate(model, {k: v for k, v in param.items() if k != 'region_loras'}, *args)
+        finally:
+            model.lora_request = keep_rl
     cn = param.get('control')
     if cn is not None:
         if getattr(model, 'controlnet', None) is None:
@@ -304,6 +316,48 @@ def check_control_args(a):
     return flag
 
 
+def check_region_lora_args(a):
+    """--region_lora and the "region_loras" keys of a --requests file, checked before any rank starts: every file exists, every spec
+    parses, at most four adapters in all.  Bad values end the run (SystemExit).  Sets a.region_lora_files = {name: path} of every adapter
+    the run loads and returns the flags' request (set_lora_scales' keyword arguments) or None."""
+    from .regional_lora import MAX_ADAPTERS, lora_request_from_specs
+    files, flag = {}, None
+
+    def parse(specs, who):
+        try:
+            f, req = lora_request_from_specs(specs, who)
+        except ValueError as e:
+            raise SystemExit(f"sample: {e}")
+        for name, path in f.items():
+            if not os.path.isfile(path):
+                raise SystemExit(f"sample: {who}: file not found: {path}")
+            if files.setdefault(name, path) != path:
+                raise SystemExit(f"sample: {who}: two adapter files share the name {name!r}: {files[name]} and {path}")
+        return req
+    if getattr(a, "region_lora", None):
+        flag = parse(a.region_lora, "--region_lora")
+    if getattr(a, "requests", None) and os.path.isfile(a.requests):
+        with open(a.requests) as f:
+            for n, line in enumerate(f, 1):
+                if line.strip() and json.loads(line).get("region_loras") is not None:
+                    parse(json.loads(line)["region_loras"], f"--requests line {n}: region_loras")
+    if len(files) > MAX_ADAPTERS:
+        raise SystemExit(f"sample: --region_lora / region_loras name {len(files)} adapters; at most {MAX_ADAPTERS} can be resident")
+    a.region_lora_files = files
+    return flag
+
+
+def _request_region_loras(a, r):
+    """A --requests line's "region_loras" (["PATH[:TARGET[:SCALE]]", ...], files the run has loaded), else the flags'."""
+    if r.get("region_loras") is None:
+        return getattr(a, "region_loras", None)
+    from .regional_lora import lora_request_from_specs
+    try:
+        return lora_request_from_specs(r["region_loras"], "--requests: region_loras")[1]
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
+
+
 def _request_control(a, r):
     """A --requests line's "control" ({"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b}), else the flags'."""
     if r.get("control") is None:
@@ -332,7 +386,7 @@ def build_requests(a):
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
     one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
-    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); "control": {"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b} = the ControlNet hint and scales of that request alone (--controlnet); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
+    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); "control": {"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b} = the ControlNet hint and scales of that request alone (--controlnet); "region_loras": ["PATH[:TARGET[:SCALE]]", ...] = the regional LoRA scales of that request alone (every PATH is loaded at start-up, at most four in all); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -346,13 +400,13 @@ def build_requests(a):
                                  negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
                                  max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1)))),
                                  freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu"),
-                                 image_prompts=_request_image_prompts(a, r), control=_request_control(a, r)))
+                                 image_prompts=_request_image_prompts(a, r), control=_request_control(a, r), region_loras=_request_region_loras(a, r)))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
         reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1),
-                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None), control=getattr(a, "control", None)) for j, sd in pairs]
+                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None), control=getattr(a, "control", None), region_loras=getattr(a, "region_loras", None)) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -385,6 +439,11 @@ def build_model(a, rank=0, local_rank=0, world=1):
                 m.load_controlnet(a.controlnet)
             except ValueError as e:
                 raise SystemExit(f"sample: --controlnet: {e}")
+        if getattr(a, 'region_lora_files', None):    # --region_lora: every rank reads the files itself (the column map is per engine; the factors travel in the arena)
+            try:
+                m.load_regional_loras(a.region_lora_files, attention_only=bool(getattr(a, 'region_lora_attention_only', False)))
+            except (ValueError, KeyError) as e:
+                raise SystemExit(f"sample: --region_lora: {e}")
         return m
     if world == 1:
         if a.model == 'SD':
@@ -540,6 +599,12 @@ def build_parser():
                    help='with --control_image: the conditioning scale.  A bare S is the default of every prompt (the negative one included, as '
                         'in diffusers); TARGET:S overrides it for TARGET = negative or a region number of the rich text; base:S is the bare S. '
                         'A prompt with scale 0 is not controlled.  Default 1')
+    p.add_argument('--region_lora', type=str, nargs='+', default=None, metavar='PATH[:TARGET[:SCALE]]',
+                   help='regional LoRA: adapters (kohya / diffusers / peft layouts, on the attention projections) kept unmerged and scaled per '
+                        'prompt.  TARGET: all (default), base, negative or a region number; SCALE default 1.  Up to four files, 128 rank columns '
+                        'in all; the same file may be named with several targets.  (load_components(lora_path=) merges ONE adapter into the weights instead)')
+    p.add_argument('--region_lora_attention_only', action='store_true',
+                   help='with --region_lora: drop a checkpoint\'s tensors on other modules (feed-forward, proj_in / proj_out, resnets) instead of refusing it')
     p.add_argument('--control_start', type=float, default=0.0, help='with --control_image: the fraction of the executed schedule at which control begins (control_guidance_start)')
     p.add_argument('--control_end', type=float, default=1.0, help='... and at which it ends (control_guidance_end)')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
@@ -588,6 +653,7 @@ def main(argv=None):
         check_requests_freeu(a.requests)
     a.image_prompts = check_ip_args(a)                 # ... and a missing adapter / embedding file or a malformed FILE[:TARGET[:SCALE]]
     a.control = check_control_args(a)                  # ... and a missing ControlNet / hint image or a malformed --control_scale
+    a.region_loras = check_region_lora_args(a)         # ... and a missing adapter file or a malformed PATH[:TARGET[:SCALE]]
     if a.init_image is None and a.keep_source != 'none':
         raise SystemExit("sample: --keep_source needs --init_image")
     if a.init_image is not None and a.keep_source != 'none' and a.split_image:
@@ -625,7 +691,7 @@ def main(argv=None):
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
                  'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu'), 'image_prompts': r.get('image_prompts'),
-                 'control': r.get('control')}
+                 'control': r.get('control'), 'region_loras': r.get('region_loras')}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

@@ -7,13 +7,15 @@ import torch
 from .engine import Engine
 from .controlnet import ControlNetMixin
 from .ip_adapter import IPAdapterMixin
+from .regional_lora import RegionalLoraMixin, rank_layout
 
 
-class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin):
+class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin):
     """Holds the engine(s) for one set of weights; engines are created lazily per latent size.  With an IP-Adapter installed
     (load_ip_adapter) every engine is built with its image tokens per prompt and carries its to_k_ip / to_v_ip weights; with a ControlNet installed
-    (load_controlnet) every engine is built with it and carries its weights under "controlnet.".  The operator seam __call__ stays
-    text-only and uncontrolled."""
+    (load_controlnet) every engine is built with it and carries its weights under "controlnet.".  With regional LoRA adapters installed
+    (load_regional_loras) every engine is built with their rank columns and carries their factors under "lora.".  The operator seam
+    __call__ stays text-only, uncontrolled and un-adapted."""
 
     def __init__(self, config, state_dict=None, device=0, max_streams=8, max_prompts=8, max_keys=77):
         self.config_dict = dict(config)
@@ -26,6 +28,18 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin):
         self.freeu = None                          # (s1, s2, b1, b2) or None = off: on every engine of this model, present and future
         self.ip_tokens, self._ip_weights = 0, None # install_ip_adapter: image tokens per prompt slot (0 = no adapter) and the adapter's layer weights
         self._cn_config, self._cn_weights = None, None   # install_controlnet: Engine's controlnet= argument (None = no ControlNet) and the ControlNet's weights
+        self.lora_rank, self._rl_adapters = 0, None      # install_regional_loras: Engine's lora_rank= argument (0 = none) and the parsed adapters
+
+    def install_regional_loras(self, adapters):
+        """adapters: {name: modules} (regional_lora.parse_adapter) or None = remove them.  As install_ip_adapter: the weight table changes,
+        the engines are dropped and rebuilt on their next use, and a model whose weights arrived by broadcast refuses once it has an engine."""
+        if isinstance(self._state_dict, str) and self._state_dict == "empty" and self._engines:
+            raise RuntimeError("HipUNet2DConditionModel: the weights of this model arrived by broadcast and live in its engines only; "
+                               "load / unload regional LoRA adapters before the first engine is built")
+        self.lora_rank, self._rl_adapters = (rank_layout(adapters)[3], adapters) if adapters else (0, None)
+        for e in self._engines.values():
+            e.close()
+        self._engines = {}
 
     def install_controlnet(self, cn):
         """cn: what controlnet.load_controlnet returns, or None = remove it.  As install_ip_adapter: the weight table changes, the engines
@@ -103,7 +117,8 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin):
                 raise RuntimeError("HipUNet2DConditionModel: no weights loaded (call load_state_dict)")
             try:
                 e = Engine(self.config_dict, h, w, device=self.device_index, max_streams=self.max_streams,
-                           max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens, controlnet=self._cn_config)
+                           max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens, controlnet=self._cn_config,
+                           lora_rank=self.lora_rank)
                 try:
                     if empty:
                         if donor is not None:
@@ -124,6 +139,8 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin):
                         e.load_state_dict({**self._state_dict, **(self._ip_weights or {}), **(self._cn_weights or {})})
                     else:
                         e.load_state_dict(self._state_dict)
+                    if self.lora_rank:                     # (on a broadcast-fed rank the arena that arrives carries the same factors)
+                        e.bind_regional_loras(self._rl_adapters)
                     if self.freeu is not None:
                         e.set_freeu(*self.freeu)
                 except BaseException:
