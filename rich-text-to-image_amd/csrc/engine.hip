@@ -111,23 +111,37 @@ struct TransformerP {
 struct DownP { std::vector<ResnetP> res; std::vector<TransformerP> attn; bool has_attn = false, has_down = false; MatW down; int C = 0; };
 struct UpP { std::vector<ResnetP> res; std::vector<TransformerP> attn; bool has_attn = false, has_up = false; MatW up; int C = 0; };
 
-// ControlNet (rt_config.controlnet): a second copy of the encoder under the prefix "controlnet." - built by the same mk_* builders -, the
-// hint embedder in front and one 1x1 zero convolution per skip / for the mid block behind.  Its own time_emb_proj table and addition
-// embeddings, so that an engine without an active hint computes nothing for it.
-struct ControlP {
+// One network: the time-embedding head, conv_in, the down blocks and the mid block, with its own time_emb_proj table and addition embeddings.
+// The engine owns two, built (build_encoder) and walked (time_embed, encode) by the same code: the UNet - which alone has up blocks, their
+// resnets in the same table - and, with rt_config.controlnet, the ControlNet's copy of the encoder under the prefix "controlnet.".
+struct NetP {
+    std::string prefix;
+    bool adapters = true;        // its transformer blocks carry the image-prompt and LoRA slots (the UNet's do, the ControlNet's never)
     MatW conv_in, t1, t2, a1, a2;
     std::vector<DownP> down;
     ResnetP mid_r0, mid_r1;
     TransformerP mid_t;
+    std::vector<UpP> up;
+    // every resnet's time_emb_proj(silu(emb)) is computed by ONE launch at the start of a forward (launch_temb_all)
+    std::vector<TembEntry> temb_tab;
+    int temb_total = 0;
+    TembEntry* temb_tab_dev = nullptr;
+    float* aug_emb = nullptr;    // [maxP, temb_dim] (zeros when no addition embedding)
+    template <typename F> void for_each_tblock(F f) {
+        for (auto& d : down) for (auto& t : d.attn) for (auto& k : t.blocks) f(t, k);
+        for (auto& k : mid_t.blocks) f(mid_t, k);
+        for (auto& u : up) for (auto& t : u.attn) for (auto& k : t.blocks) f(t, k);
+    }
+};
+
+// ControlNet (rt_config.controlnet): what it has beyond its NetP - the hint embedder in front and one 1x1 zero convolution per skip / for the
+// mid block behind.  An engine without an active hint computes nothing for it.
+struct ControlP {
     std::vector<MatW> zero;      // controlnet_down_blocks.{k}: one per skip, in the order unet_forward pushes them
     MatW zero_mid;               // controlnet_mid_block
     struct ConvF { float* w = nullptr; float* b = nullptr; int N = 0, CinP = 0; };      // fp32 [N][tap][CinP] + bias
     ConvF ce_in, ce_blocks[6], ce_out;     // controlnet_cond_embedding: kept in fp32 (control_conv3_kernel)
     int ce_ch[4] = {0, 0, 0, 0}, hint_ch = 3;
-    std::vector<TembEntry> temb_tab;
-    int temb_total = 0;
-    TembEntry* temb_tab_dev = nullptr;
-    float* aug_emb = nullptr;    // [maxP, temb_dim]
     // per image: the cached hint embedding [h w, C0] (fp32 as rt_control_embedding_read returns it; fp16 = the same accumulators rounded once,
     // the residual operand of controlnet.conv_in's epilogue) and the scale of every prompt slot
     float* emb_f32 = nullptr; f16_t* emb_f16 = nullptr;
@@ -162,7 +176,7 @@ struct FwdIn {
     int prompt[RT_MAXB], fontsize[RT_MAXB], qk_src[RT_MAXB], res_src[RT_MAXB];
     float* eps_out = nullptr;    // [B, HW, 4] fp32
     int store_stream = -1;       // stream whose head-averaged attention maps are recorded (plain pass: the conditional one)
-    bool control = false;        // the forward of the ControlNet's encoder copy (control_forward): no image-prompt term
+    bool control = false;        // the forward of the ControlNet's encoder copy (control_pass): no image-prompt term, no adapters
 };
 
 extern int g_store_own_stats;
@@ -383,20 +397,13 @@ struct rt_engine {
     std::map<std::string, int> slot_index;
 
     // plan
-    MatW conv_in, conv_out, t1, t2, a1, a2;
+    NetP unet, cnet;             // cnet: rt_config.controlnet
+    std::vector<NetP*> nets;     // the networks this engine has, the UNet first: what is done "for both" loops over this
+    MatW conv_out;
     NormW norm_out;
-    std::vector<DownP> down;
-    std::vector<UpP> up;
-    ResnetP mid_r0, mid_r1;
-    TransformerP mid_t;
     ControlP ctl;                // rt_config.controlnet
-    bool building_control = false;
     int temb_dim = 0;
-    // every resnet's time_emb_proj(silu(emb)) is computed by ONE launch at the start of a forward (launch_temb_all)
-    std::vector<TembEntry> temb_tab;
-    int temb_total = 0;
-    TembEntry* temb_tab_dev = nullptr;
-    float* temb_all = nullptr;       // [resnet][B][cout] of the running forward
+    template <typename F> void for_each_tblock(F f) { unet.for_each_tblock(f); }      // the token-map store, the image prompts and the adapters are the UNet's alone
 
     // per-image state
     int n_prompts = 0;
@@ -418,7 +425,6 @@ struct rt_engine {
         return false;
     }
     int KP() const { return 96 * (cfg.max_keys / 77); }      // rows per prompt in the K / V^T caches and the multiplier tables
-    float* aug_emb = nullptr;        // [maxP, temb_dim] (zeros when no addition embedding)
     float* wabs = nullptr;           // [2, KP]
     float* wsgn = nullptr;
     float* masks = nullptr;          // [R, 4, HW]
@@ -533,7 +539,7 @@ struct rt_engine {
         add_slot(name + ".bias", {Cout}, pk_vec(m.b, Cout));
         return m;
     }
-    ResnetP mk_resnet(const std::string& name, int cin, int cout) {
+    ResnetP mk_resnet(NetP& net, const std::string& name, int cin, int cout) {      // net: whose time_emb_proj table it joins
         RT_REQUIRE(cin % 8 == 0 && cout % 8 == 0, "resnet: channel counts must be multiples of 8");
         ResnetP r; r.name = name; r.cin = cin; r.cout = cout;
         r.n1 = mk_norm(name + ".norm1", cin);
@@ -543,8 +549,8 @@ struct rt_engine {
         r.c2 = mk_conv3(name + ".conv2", cout, cout);
         r.has_sc = cin != cout;
         if (r.has_sc) r.sc = mk_linear(name + ".conv_shortcut", cin, cout, true, true);
-        r.temb_first = temb_total; temb_total += cout;
-        temb_tab.push_back(TembEntry{r.temb.w, r.temb.b, cout, r.temb_first});
+        r.temb_first = net.temb_total; net.temb_total += cout;
+        net.temb_tab.push_back(TembEntry{r.temb.w, r.temb.b, cout, r.temb_first});
         return r;
     }
     // q/k/v projection with head padding d -> DP on the output rows
@@ -572,7 +578,7 @@ struct rt_engine {
     void ensure_fold() {
         if (!fold_dirty || !farena_base) { fold_dirty = false; return; }
         for (auto& sl : slots) if (!sl.bound) return;                   // not all weights are there yet
-        for_each_tblock_all([&](TransformerP& t, TBlockP& k) {
+        for (NetP* net : nets) net->for_each_tblock([&](TransformerP& t, TBlockP& k) {
             if (!k.qk1f.w) return;
             launch_ln_fold_derive(k.qk1.w, k.qk1.K, k.qk1.b, k.ln1.g, k.ln1.b, k.qk1.N, k.qk1.K, k.qk1f.w, k.qk1s, stream);
             launch_ln_fold_derive(k.v1.w, k.v1.K, k.v1.b, k.ln1.g, k.ln1.b, k.v1.N, k.v1.K, k.v1f.w, k.v1s, stream);
@@ -581,7 +587,8 @@ struct rt_engine {
         });
         fold_dirty = false;
     }
-    TransformerP mk_transformer(const std::string& name, int C, int heads, int nlayers, int level) {
+    // adapters: the blocks get the image-prompt (rt_config.ip_tokens) and LoRA (rt_config.lora_rank) slots - NetP.adapters of their network
+    TransformerP mk_transformer(const std::string& name, int C, int heads, int nlayers, int level, bool adapters) {
         TransformerP t; t.name = name; t.C = C; t.heads = heads; t.d = C / heads; t.DP = pad_head_dim(t.d); t.level = level;
         RT_REQUIRE(C % heads == 0, "channels not divisible by heads");
         const int HD = heads * t.DP, D = cfg.cross_attention_dim;
@@ -607,7 +614,7 @@ struct rt_engine {
             k.k2 = mk_headproj(b + ".attn2.to_k", D, heads, t.d, t.DP, 1.f, k2, D);
             bf16_t* v2 = (bf16_t*)arena.alloc((size_t)HD * D * 2);
             k.v2 = mk_headproj(b + ".attn2.to_v", D, heads, t.d, t.DP, 1.f, v2, D);
-            if (cfg.ip_tokens > 0 && !building_control) {      // (the control copy has no image-prompt term)
+            if (cfg.ip_tokens > 0 && adapters) {
                 bf16_t* kip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
                 k.kip = mk_headproj(b + ".attn2.to_k_ip", D, heads, t.d, t.DP, 1.f, kip, D);
                 bf16_t* vip = (bf16_t*)arena.alloc((size_t)HD * D * 2);
@@ -625,7 +632,7 @@ struct rt_engine {
             k.ff2 = mk_linear(b + ".ff.net.2", 4 * C, C, true);
             k.kcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
             k.vtcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * KP() * HD * 2);
-            if (cfg.ip_tokens > 0 && !building_control) {
+            if (cfg.ip_tokens > 0 && adapters) {
                 k.kipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
                 k.vtipcache = (bf16_t*)sarena.alloc((size_t)cfg.max_prompts * 16 * HD * 2);
             }
@@ -637,7 +644,7 @@ struct rt_engine {
                 };
                 mkf(k.qk1, k.qk1f, k.qk1s); mkf(k.v1, k.v1f, k.v1s); mkf(k.q2, k.q2f, k.q2s); mkf(k.ff1, k.ff1f, k.ff1s);
             }
-            if (cfg.lora_rank > 0 && !building_control) {          // (the control copy runs without adapters)
+            if (cfg.lora_rank > 0 && adapters) {
                 const int R = cfg.lora_rank;
                 static const char* leaf[4] = {"to_q", "to_k", "to_v", "to_out.0"};
                 for (int a = 0; a < 2; ++a)
@@ -669,26 +676,39 @@ struct rt_engine {
         return t;
     }
 
-    // the down blocks of the UNet, or - under the prefix "controlnet." - of the ControlNet's copy of them
-    void mk_down_blocks(const std::string& prefix, std::vector<DownP>& dst, std::vector<TraceMod>& tm) {
+    // The encoder of `net` under net.prefix, its slots in the order of the checkpoint; tm: its traceable modules in execution order
+    void build_encoder(NetP& net, std::vector<TraceMod>& tm) {
         const int L = cfg.n_levels;
         const int* boc = cfg.block_out_channels;
+        const std::string& P = net.prefix;
+        net.conv_in = mk_conv3(P + "conv_in", cfg.in_channels, boc[0]);
+        tm.push_back({P + "conv_in", boc[0], 0});
+        net.t1 = mk_linear(P + "time_embedding.linear_1", boc[0], temb_dim, true);
+        net.t2 = mk_linear(P + "time_embedding.linear_2", temb_dim, temb_dim, true);
+        if (cfg.addition_text_time) {
+            net.a1 = mk_linear(P + "add_embedding.linear_1", cfg.projection_class_embeddings_input_dim, temb_dim, true);
+            net.a2 = mk_linear(P + "add_embedding.linear_2", temb_dim, temb_dim, true);
+        }
         int out_c = boc[0];
         for (int i = 0; i < L; ++i) {
             DownP d; const int in_c = out_c; out_c = boc[i]; d.C = out_c;
             d.has_attn = cfg.down_has_attn[i]; d.has_down = i != L - 1;
-            const std::string pre = prefix + "down_blocks." + std::to_string(i);
+            const std::string pre = P + "down_blocks." + std::to_string(i);
             for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
-                d.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), j == 0 ? in_c : out_c, out_c));
+                d.res.push_back(mk_resnet(net, pre + ".resnets." + std::to_string(j), j == 0 ? in_c : out_c, out_c));
                 tm.push_back({d.res.back().name, out_c, i});
                 if (d.has_attn) {
-                    d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i));
+                    d.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[i], cfg.transformer_layers[i], i, net.adapters));
                     tm.push_back({d.attn.back().name, out_c, i});
                 }
             }
             if (d.has_down) { d.down = mk_conv3(pre + ".downsamplers.0.conv", out_c, out_c); tm.push_back({pre + ".downsamplers.0.conv", out_c, i + 1}); }
-            dst.push_back(d);
+            net.down.push_back(d);
         }
+        net.mid_r0 = mk_resnet(net, P + "mid_block.resnets.0", boc[L - 1], boc[L - 1]);
+        net.mid_t = mk_transformer(P + "mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1, net.adapters);
+        net.mid_r1 = mk_resnet(net, P + "mid_block.resnets.1", boc[L - 1], boc[L - 1]);
+        for (const char* m : {"mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1"}) tm.push_back({P + m, boc[L - 1], L - 1});
     }
     // The ControlNet behind the UNet's own weights (diffusers' ControlNetModel layout under "controlnet."): slots, arena offsets and caches of
     // the UNet are what they are without it.  Its traceable modules go where they run: behind the main mid block.
@@ -696,7 +716,7 @@ struct rt_engine {
         ctl = ControlP{};
         const int L = cfg.n_levels;
         const int* boc = cfg.block_out_channels;
-        const std::string P = "controlnet.";
+        const std::string& P = cnet.prefix;
         static const int def_ch[4] = {16, 32, 96, 256};
         bool all0 = true;
         for (int i = 0; i < 4; ++i) all0 = all0 && cfg.control_embed_channels[i] == 0;
@@ -706,23 +726,10 @@ struct rt_engine {
         }
         ctl.hint_ch = cfg.control_hint_channels ? cfg.control_hint_channels : 3;
         RT_REQUIRE(ctl.hint_ch >= 1 && ctl.hint_ch <= 64, "rt_create: control_hint_channels");
-        building_control = true;
-        std::swap(temb_tab, ctl.temb_tab); std::swap(temb_total, ctl.temb_total);      // mk_resnet fills the control copy's own table
-        std::vector<TraceMod> tm;
+        std::vector<TraceMod> em, tm;      // em: the encoder's modules as build_encoder lists them; tm: all of the ControlNet's, the skips between them
+        build_encoder(cnet, em);
         tm.push_back({P + "hint_embedding", boc[0], 0});
-        ctl.conv_in = mk_conv3(P + "conv_in", cfg.in_channels, boc[0]);
-        tm.push_back({P + "conv_in", boc[0], 0});
-        ctl.t1 = mk_linear(P + "time_embedding.linear_1", boc[0], temb_dim, true);
-        ctl.t2 = mk_linear(P + "time_embedding.linear_2", temb_dim, temb_dim, true);
-        if (cfg.addition_text_time) {
-            ctl.a1 = mk_linear(P + "add_embedding.linear_1", cfg.projection_class_embeddings_input_dim, temb_dim, true);
-            ctl.a2 = mk_linear(P + "add_embedding.linear_2", temb_dim, temb_dim, true);
-        }
-        std::vector<TraceMod> dm;
-        mk_down_blocks(P, ctl.down, dm);
-        ctl.mid_r0 = mk_resnet(P + "mid_block.resnets.0", boc[L - 1], boc[L - 1]);
-        ctl.mid_t = mk_transformer(P + "mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1);
-        ctl.mid_r1 = mk_resnet(P + "mid_block.resnets.1", boc[L - 1], boc[L - 1]);
+        tm.push_back(em[0]);
         ctl.ce_in = mk_conv3_f32(P + "controlnet_cond_embedding.conv_in", ctl.hint_ch, ctl.ce_ch[0]);
         for (int i = 0; i < 3; ++i) {
             ctl.ce_blocks[2 * i] = mk_conv3_f32(P + "controlnet_cond_embedding.blocks." + std::to_string(2 * i), ctl.ce_ch[i], ctl.ce_ch[i]);
@@ -738,21 +745,19 @@ struct rt_engine {
             ++k;
         };
         zc(boc[0], 0);
-        size_t di = 0;
+        size_t di = 1;
         for (int i = 0; i < L; ++i) {
             for (int j = 0; j < cfg.layers_per_block[i]; ++j) {
-                tm.push_back(dm[di++]);
-                if (cfg.down_has_attn[i]) tm.push_back(dm[di++]);
+                tm.push_back(em[di++]);
+                if (cfg.down_has_attn[i]) tm.push_back(em[di++]);
                 zc(boc[i], i);
             }
-            if (i != L - 1) { tm.push_back(dm[di++]); zc(boc[i], i + 1); }
+            if (i != L - 1) { tm.push_back(em[di++]); zc(boc[i], i + 1); }
         }
         ctl.zero_mid = mk_linear(P + "controlnet_mid_block", boc[L - 1], boc[L - 1], true, true);
-        for (const char* m : {"mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1"}) tm.push_back({P + m, boc[L - 1], L - 1});
+        tm.insert(tm.end(), em.begin() + di, em.end());      // the mid block's three
         tm.push_back({P + "mid", boc[L - 1], L - 1});
-        ctl.aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
-        std::swap(temb_tab, ctl.temb_tab); std::swap(temb_total, ctl.temb_total);
-        building_control = false;
+        cnet.aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
         ctl.scale.assign((size_t)std::max(1, cfg.max_prompts), 0.f);
         size_t at = 0;
         while (at < trace_mods.size() && trace_mods[at].name != "mid_block.resnets.1") ++at;
@@ -760,26 +765,16 @@ struct rt_engine {
     }
 
     void build_plan() {
-        slots.clear(); slot_index.clear(); down.clear(); up.clear(); temb_tab.clear(); temb_total = 0; trace_mods.clear();
+        slots.clear(); slot_index.clear(); trace_mods.clear();
+        unet = NetP{}; cnet = NetP{}; cnet.prefix = "controlnet."; cnet.adapters = false;
+        nets.assign(1, &unet);
+        if (cfg.controlnet) nets.push_back(&cnet);
         const int L = cfg.n_levels;
         const int* boc = cfg.block_out_channels;
         temb_dim = boc[0] * 4;
         zero = (bf16_t*)sarena.alloc(256);
-        conv_in = mk_conv3("conv_in", cfg.in_channels, boc[0]);
-        trace_mods.push_back({"conv_in", boc[0], 0});
-        t1 = mk_linear("time_embedding.linear_1", boc[0], temb_dim, true);
-        t2 = mk_linear("time_embedding.linear_2", temb_dim, temb_dim, true);
-        if (cfg.addition_text_time) {
-            a1 = mk_linear("add_embedding.linear_1", cfg.projection_class_embeddings_input_dim, temb_dim, true);
-            a2 = mk_linear("add_embedding.linear_2", temb_dim, temb_dim, true);
-        }
-        mk_down_blocks("", down, trace_mods);
+        build_encoder(unet, trace_mods);
         int out_c = boc[L - 1];
-        mid_r0 = mk_resnet("mid_block.resnets.0", boc[L - 1], boc[L - 1]);
-        mid_t = mk_transformer("mid_block.attentions.0", boc[L - 1], cfg.heads[L - 1], cfg.transformer_layers[L - 1], L - 1);
-        mid_r1 = mk_resnet("mid_block.resnets.1", boc[L - 1], boc[L - 1]);
-        for (const char* m : {"mid_block.resnets.0", "mid_block.attentions.0", "mid_block.resnets.1"}) trace_mods.push_back({m, boc[L - 1], L - 1});
-        out_c = boc[L - 1];
         for (int i = 0; i < L; ++i) {
             UpP u; const int prev = out_c; out_c = boc[L - 1 - i];
             const int in_c = boc[L - 1 - std::min(i + 1, L - 1)];
@@ -789,22 +784,22 @@ struct rt_engine {
             for (int j = 0; j < nl; ++j) {
                 const int skip_c = j == nl - 1 ? in_c : out_c;
                 const int res_in = j == 0 ? prev : out_c;
-                u.res.push_back(mk_resnet(pre + ".resnets." + std::to_string(j), res_in + skip_c, out_c));
+                u.res.push_back(mk_resnet(unet, pre + ".resnets." + std::to_string(j), res_in + skip_c, out_c));
                 trace_mods.push_back({u.res.back().name, out_c, L - 1 - i});
                 if (u.has_attn) {
-                    u.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[L - 1 - i], cfg.transformer_layers[L - 1 - i], L - 1 - i));
+                    u.attn.push_back(mk_transformer(pre + ".attentions." + std::to_string(j), out_c, cfg.heads[L - 1 - i], cfg.transformer_layers[L - 1 - i], L - 1 - i, true));
                     trace_mods.push_back({u.attn.back().name, out_c, L - 1 - i});
                 }
             }
             if (u.has_up) { u.up = mk_conv3(pre + ".upsamplers.0.conv", out_c, out_c, true); trace_mods.push_back({pre + ".upsamplers.0.conv", out_c, L - 2 - i}); }
-            up.push_back(u);
+            unet.up.push_back(u);
         }
         norm_out = mk_norm("conv_norm_out", boc[0]);
         conv_out = mk_conv3("conv_out", boc[0], cfg.out_channels);
         trace_mods.push_back({"conv_out", cfg.out_channels, 0});
         // per-image sampler state
         const size_t HW = (size_t)cfg.latent_h * cfg.latent_w;
-        aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
+        unet.aug_emb = (float*)sarena.alloc((size_t)cfg.max_prompts * temb_dim * 4);
         wabs = (float*)sarena.alloc((size_t)2 * KP() * 4); wsgn = (float*)sarena.alloc((size_t)2 * KP() * 4);
         masks = (float*)sarena.alloc((size_t)RT_MAXB * 4 * HW * 4);
         lat = (float*)sarena.alloc(4 * HW * 4); lat_ref = (float*)sarena.alloc(4 * HW * 4); noise_pred = (float*)sarena.alloc(4 * HW * 4);
@@ -889,7 +884,8 @@ struct rt_engine {
 
     // ---------------------------------------------------------------------------- blocks
     // ResnetBlock2D.forward (models/resnet.py:591-645); x2 = skip tensor of the up path (virtual concat)
-    Tensor resnet(const ResnetP& r, const FwdIn& in, int HW, int Hh, int Ww, Tensor x1, const Tensor* x2, const float* emb,
+    // temb: the time_emb_proj table of the running forward (time_embed)
+    Tensor resnet(const ResnetP& r, const FwdIn& in, int HW, int Hh, int Ww, Tensor x1, const Tensor* x2, const float* temb,
                   bool inject_here) {
         const int B = in.B, M = B * HW;
         const int c1 = x1.C, c2 = x2 ? x2->C : 0;
@@ -901,7 +897,7 @@ struct rt_engine {
             bf16_t* h1 = ws.b16((size_t)M * r.cin);
             bf16_t* raw = r.has_sc ? ws.b16((size_t)M * r.cin) : nullptr;
             groupnorm(x1.p, x2 ? x2->p : nullptr, 2, c1, c2, B, HW, r.n1, cfg.norm_eps, true, h1, raw);
-            const float* tp = temb_all + (size_t)B * r.temb_first;        // computed for all resnets at the start of the forward
+            const float* tp = temb + (size_t)B * r.temb_first;            // computed for all resnets at the start of the forward
             // rich-text feature injection (resnet.py:639-643): out[b] = shortcut(x[b]) + hidden[res_src[b]].  The residual branch
             // (conv1 / norm2 / conv2) of an injected stream is never used, so the trailing run of injected streams is not computed
             // at all (the region streams of a rich-text step are the last ones): Bk streams keep their branch.
@@ -935,6 +931,234 @@ struct rt_engine {
         return Tensor{out, r.cout};
     }
 
+    // ---------------------------------------------------------------------------- transformer
+    // Regional LoRA (rt_set_lora_scales): the adapted streams of a forward - those whose prompt slot has a non-zero scale - get the low-rank
+    // term added behind each of the eight attention projections; every other stream is in none of these launches
+    struct LoraRows {
+        rt_engine& e;
+        int B, HW;
+        int rows[RT_MAXB]; float sc[RT_MAXB * 4];
+        bool any = false;
+        LoraRows(rt_engine& e_, const FwdIn& in, int HW_) : e(e_), B(in.B), HW(HW_) {
+            for (int b = 0; b < B; ++b) {
+                const bool on = !e.dry() && !in.control && e.lora_on(in.prompt[b]);
+                rows[b] = b * HW;
+                for (int l = 0; l < 4; ++l) sc[4 * b + l] = on ? e.lora_scale[(size_t)in.prompt[b] * 4 + l] : 0.f;
+                any = any || on;
+            }
+        }
+        bool on(int b) const { return sc[4 * b] != 0.f || sc[4 * b + 1] != 0.f || sc[4 * b + 2] != 0.f || sc[4 * b + 3] != 0.f; }
+        // run f(first stream, streams) over the maximal runs of adapted streams (the row-wise kernels take a run as one launch)
+        template <typename F> void runs(F f) const {
+            for (int b = 0; b < B;) {
+                if (!on(b)) { ++b; continue; }
+                int e_ = b; while (e_ < B && on(e_)) ++e_;
+                f(b, e_ - b); b = e_;
+            }
+        }
+        // the term of one projection for the first nb streams
+        void add(const LoraW& w, const bf16_t* X, int ldx, void* Y, int ldy, int form, int nb) const {
+            if (any) e.lora_add(w, X, ldx, Y, ldy, form, rows, sc, nb, HW);
+        }
+        // a folded LayerNorm is never materialised: the adapters' input is computed for the adapted rows only, into `n`
+        void norm(const NormW& ln, const f16_t* h, bf16_t* n) const {
+            runs([&](int b, int nb) { launch_layernorm(h + (size_t)b * HW * ln.C, 1, ln.g, ln.b, n + (size_t)b * HW * ln.C, nb * HW, ln.C, 1e-5f, e.stream); });
+        }
+    };
+    // The LayerNorms of one transformer() call, folded into their consumers (gemm16.hip, "LNF"; attention.py:150,168,181) wherever every
+    // consumer of the LayerNorm has the folded instantiation - a pure function of the layer's shape (width, tokens per stream), never of the
+    // batch.  The trunk's producers (proj_in, to_out, ff.net.2: fp16-trunk epilogues) then leave the per-row partial sums next to it; a
+    // producer without that form is followed by the stand-alone partials kernel.  Debug bit 22 restores the LayerNorm launches.
+    struct LnTrunk {
+        rt_engine& e;
+        const LoraRows& lora;
+        int M, C;
+        f16_t* hcur;                 // the trunk
+        float* part;                 // [M, 16]: up to 4 tile pairs x float4 per token
+        bf16_t* xb;                  // the trunk as bf16, written next to it by its producer
+        bool fold[3] = {false, false, false};                            // norm1 / norm2 / norm3
+        bool emit_pin = false, emit_out = false, emit_ff2 = false;       // the producers that leave the partials themselves
+        int ln_bn = 160, npair;      // column-tile width of the partials (a function of the class of the producers: of (C, tokens per stream))
+        LnFold em;
+        LnTrunk(rt_engine& e_, const LoraRows& l, const TransformerP& t, int M_, f16_t* h, float* p, bf16_t* x)
+            : e(e_), lora(l), M(M_), C(t.C), hcur(h), part(p), xb(x) {
+            const int HD = t.heads * t.DP;
+            if (gemm_lnfold_enabled() && ln_fold_width(C) && !t.blocks.empty() && t.blocks[0].qk1f.w) {
+                const TBlockP& k0 = t.blocks[0];
+                const int bn_pin = gemm_ln_emit_bn(e.dense_args(nullptr, C, t.pin, M, nullptr, C, EPI_F16));
+                const int bn_out = gemm_ln_emit_bn(e.dense_args(nullptr, HD, k0.out1, M, nullptr, C, EPI_F16));
+                const int bn_ff2 = gemm_ln_emit_bn(e.dense_args(nullptr, 4 * C, k0.ff2, M, nullptr, C, EPI_F16));
+                ln_bn = bn_out ? bn_out : (bn_ff2 ? bn_ff2 : (bn_pin ? bn_pin : 160));
+                emit_pin = bn_pin == ln_bn; emit_out = bn_out == ln_bn; emit_ff2 = bn_ff2 == ln_bn;     // (one class for all three: same N, same tokens per stream)
+                const int np = C / ln_bn / 2;
+                GemmArgs cq = e.dense_args(nullptr, C, k0.qk1f, M, nullptr, 2 * HD, EPI_BF16); cq.ln_npair = np;
+                GemmArgs cv = e.vt_args(k0.v1f, nullptr, C, M, nullptr, M); cv.ln_npair = np;
+                GemmArgs c2 = e.dense_args(nullptr, C, k0.q2f, M, nullptr, HD, EPI_BF16); c2.ln_npair = np;
+                GemmArgs c3 = e.dense_args(nullptr, C, k0.ff1f, M, nullptr, 4 * C, EPI_GEGLU); c3.ln_npair = np;
+                fold[0] = gemm_ln_fold_ok(cq) && gemm_ln_fold_ok(cv);
+                fold[1] = gemm_ln_fold_ok(c2);
+                fold[2] = gemm_ln_fold_ok(c3);
+            }
+            npair = C / ln_bn / 2;
+            em.emit = part; em.copy = xb;
+        }
+        // the consumer side of a folded launch: A / X is xb, W the folded copy, s its (row sum, c) pairs
+        LnFold reads(const float* s) const { LnFold l; l.part = part; l.npair = npair; l.ld = M; l.s = s; return l; }
+        // partials of the trunk as it stands, for the LayerNorm that follows
+        void partials() { if (!e.dry()) launch_ln_partials(hcur, xb, part, M, C, ln_bn, e.stream); }
+        // consume: out = epi(LayerNorm i of the trunk x W^T) - the folded GEMM on xb, or the LayerNorm into `n` and the plain GEMM
+        void consume(int i, const NormW& ln, bf16_t* n, const MatW& W, const MatW& Wf, const float* s, void* out, int ldo, int epi) {
+            if (fold[i]) { const LnFold l = reads(s); e.gemm(xb, C, Wf, M, out, ldo, epi, nullptr, 0, &l); }
+            else { e.layernorm(hcur, ln, n, M); e.gemm(n, C, W, M, out, ldo, epi); }
+        }
+        // produce into the trunk: hcur = A W^T (+ hcur with `residual`), then the adapters' term `lw` (the adapted rows are rounded to fp16 a
+        // second time: control_add_kernel's precedent).  folds: the LayerNorm that reads the trunk next is folded, so it needs the partials
+        // and xb - from the GEMM's epilogue where the producer `emits`, otherwise (if the trunk is `read_again` by a LayerNorm at all) from
+        // the stand-alone kernel; rows the adapters changed behind an emitting GEMM get theirs recomputed.
+        void produce(const bf16_t* A, int lda, const MatW& W, bool residual, bool folds, bool emits, bool read_again = true, const LoraW* lw = nullptr) {
+            e.gemm(A, lda, W, M, hcur, C, EPI_F16, residual ? hcur : nullptr, residual ? C : 0, folds && emits ? &em : nullptr);
+            if (lw) lora.add(*lw, A, lda, hcur, C, 2, lora.B);
+            if (folds && !emits && read_again) partials();
+            if (folds && emits && lw)
+                lora.runs([&](int b, int nb) { launch_ln_partials(hcur + (size_t)b * lora.HW * C, xb + (size_t)b * lora.HW * C, part + (size_t)b * lora.HW * 4, nb * lora.HW, C, ln_bn, e.stream, M); });
+        }
+    };
+    // What the blocks of one transformer() call share.  The per-stream tables depend on the forward, not on the block.
+    struct TCall {
+        TransformerP& t; const FwdIn& in;
+        int B, HW, M, C, HD;
+        LoraRows lora;
+        LnTrunk ln;
+        int nkeys[RT_MAXB], wset2[RT_MAXB];                                  // attn2: valid keys; multiplier set (-1: plain softmax, no tables)
+        int ip_slot[RT_MAXB], ip_cnt[RT_MAXB]; float ip_sc[RT_MAXB];         // image prompts (rt_set_image_prompts): slot -1 = no image
+        bool any_ip = false;
+        double keysum = 0, ip_keys = 0, nip = 0;
+        bf16_t *n = nullptr, *qk = nullptr, *vt = nullptr, *o = nullptr;     // scratch of the running block
+        float* store_stats = nullptr;                                        // softmax statistics of the token-map accumulation (attn_store.hip)
+        TCall(rt_engine& e, TransformerP& t_, const FwdIn& in_, int HW_, f16_t* hcur, float* part, bf16_t* xb)
+            : t(t_), in(in_), B(in_.B), HW(HW_), M(in_.B * HW_), C(t_.C), HD(t_.heads * t_.DP), lora(e, in_, HW_), ln(e, lora, t_, M, hcur, part, xb) {
+            for (int b = 0; b < B; ++b) {
+                const int p = in.prompt[b];
+                const bool on = e.cfg.ip_tokens > 0 && !in.control && e.ip_scale[p] != 0.f;
+                nkeys[b] = e.prompt_keys[p]; wset2[b] = in.fontsize[b] ? 1 : -1; keysum += nkeys[b];
+                ip_slot[b] = on ? p : -1; ip_cnt[b] = on ? e.ip_count[p] : 0; ip_sc[b] = on ? e.ip_scale[p] : 0.f;
+                if (on) { any_ip = true; ip_keys += ip_cnt[b]; nip += 1; }
+            }
+        }
+    };
+
+    // attn1 (self; attention_processor.py:476-545)
+    void attn1(TCall& c, TBlockP& k) {
+        TransformerP& t = c.t; const FwdIn& in = c.in; LnTrunk& ln = c.ln;
+        const int B = c.B, HW = c.HW, M = c.M, C = c.C, HD = c.HD;
+        // Q,K are only needed for streams that some stream attends with (injected region streams use the
+        // text_ref stream's Q,K: attention_processor.py:522-524 discards their own scores)
+        int nqk = 0;
+        for (int b = 0; b < B; ++b) nqk = std::max(nqk, in.qk_src[b] + 1);
+        if (ln.fold[0]) {
+            const LnFold lq = ln.reads(k.qk1s), lv = ln.reads(k.v1s);
+            gemm_qk_vt(ln.xb, C, k.qk1f, nqk * HW, c.qk, 2 * HD, k.v1f, M, c.vt, M, &lq, &lv);
+            c.lora.norm(k.ln1, ln.hcur, c.n);
+        } else {
+            layernorm(ln.hcur, k.ln1, c.n, M);
+            gemm_qk_vt(c.n, C, k.qk1, nqk * HW, c.qk, 2 * HD, k.v1, M, c.vt, M);
+        }
+        // (an injected region stream attends with text_ref's Q and K - rows >= nqk are not even computed -, so its own to_q /
+        // to_k adapters are moot; its to_v and to_out adapters act)
+        c.lora.add(k.lora[0], c.n, C, c.qk, 2 * HD, 0, nqk);
+        c.lora.add(k.lora[1], c.n, C, c.qk + HD, 2 * HD, 0, nqk);
+        c.lora.add(k.lora[2], c.n, C, c.vt, M, 1, B);
+        if (!dry()) {
+            // a layer whose map is recorded in this call: the attention launch leaves the softmax statistics of the recorded stream,
+            // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
+            const bool will_store = in.store_stream >= 0 && k.store_mode[0] && k.store_calls[0] + 1 > 10;      // n_maps[name] > 10 (rd.py:422, xl.py:988)
+            const bool stats_from_attn = will_store && store_handover_self(HW, t.DP, in.qk_src, in.store_stream);
+            const AttnArgs a = unet_self_attn_args(AttnIO{c.qk, 2 * HD, c.qk + HD, 2 * HD, c.vt, M, c.o, HD}, in.qk_src, B, t.heads, HW, t.DP,
+                                                   stats_from_attn ? c.store_stats : nullptr, in.store_stream);
+            prof_begin(RT_PROF_ATTN_SELF, 4.0 * B * t.heads * (double)HW * HW * t.d);
+            launch_attention(a, stream);
+            prof_end();
+            if (in.store_stream >= 0 && k.store_mode[0] && ++k.store_calls[0] > 10) {
+                RT_REQUIRE((size_t)HW * HW <= k.store_cap[0], "attention store: map larger than the enabled buffer");
+                prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * HW * t.d, 8.0 * HW * HW + 2.0 * 2.0 * HW * HD);
+                launch_attn_store(unet_store_args(a, in.store_stream, k.store[0], k.store_mode[0] == 2, c.store_stats, HW), stream);
+                prof_end();
+                k.store_rows[0] = HW; k.store_cols[0] = HW;
+            }
+        }
+        ln.produce(c.o, HD, k.out1, true, ln.fold[1], ln.emit_out, true, &k.lora[3]);
+    }
+
+    // attn2 (cross, K/V from the per-prompt cache; font-size softmax on flagged streams)
+    void attn2(TCall& c, TBlockP& k) {
+        TransformerP& t = c.t; const FwdIn& in = c.in; LnTrunk& ln = c.ln;
+        const int B = c.B, HW = c.HW, M = c.M, C = c.C, HD = c.HD;
+        // the route (cross_route): a layer with its map enabled counts as recorded whether or not this call is past the tenth
+        const bool capture2 = in.store_stream >= 0 && k.store_mode[1];
+        const int KPr = KP(), ldvt2 = cfg.max_prompts * KPr;
+        CrossRoute route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, c.nkeys, B, ln.fold[1], capture2);
+        // Image prompts: the image term is added into o behind the text attention, which the one-launch forms never write - a launch with an
+        // image takes the two-launch route of the same shape.  Regional LoRA likewise: to_q's term is added to a materialised Q, to_out's
+        // behind the GEMM.  (Only RT_PROBES builds with their debug switches on ever reach the one-launch kinds.  The dry planning forward
+        // of an engine that can hold images or adapters takes the two-launch route as well, so that the to_q GEMM such a launch runs has
+        // been planned: its split-K scratch is recorded like every other GEMM's.)
+        if ((c.any_ip || c.lora.any || (dry() && (cfg.ip_tokens > 0 || cfg.lora_rank > 0) && !in.control)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
+            route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, c.nkeys, B, ln.fold[1], capture2, false);
+        if (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED) {
+            layernorm(ln.hcur, k.ln2, c.n, M);      // (a folded norm2 never takes the one-launch forms)
+            if (route.kind == CrossRoute::XBLOCK) {
+                if (!dry()) {
+                    RT_REQUIRE(k.q2.K == C && k.out2.K == HD && HD == C, "xblock: packed projection widths");
+                    prof_begin(RT_PROF_XBLOCK, 4.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
+                    launch_xblock(unet_xblock_args(c.n, k.q2.w, k.out2.w, k.out2.b, k.kcache, k.vtcache, ldvt2, ln.hcur, ln.hcur, wabs, wsgn, in.prompt, c.wset2, B, HW, C, t.heads), stream);
+                    prof_end();
+                }
+                if (ln.fold[2]) ln.partials();
+                return;                              // to_out + residual were part of that launch
+            }
+            if (!dry()) {
+                prof_begin(RT_PROF_XATTN_FUSED, 2.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
+                launch_xattn_fused(unet_xattn_args(zero, c.n, k.q2.w, c.o, k.kcache, k.vtcache, ldvt2, wabs, wsgn, in.prompt, c.wset2, B, HW, C, t.heads), stream);
+                prof_end();
+            }
+        } else {
+            ln.consume(1, k.ln2, c.n, k.q2, k.q2f, k.q2s, c.qk, HD, EPI_BF16);
+            if (ln.fold[1]) c.lora.norm(k.ln2, ln.hcur, c.n);
+            c.lora.add(k.lora[4], c.n, C, c.qk, HD, 0, B);
+            if (!dry()) {
+                // (a recorded layer on cross77_kernel hands its statistics over as attn1 does, from the eleventh recorded call on)
+                const AttnArgs a = unet_cross_attn_args(AttnIO{c.qk, HD, k.kcache, HD, k.vtcache, ldvt2, c.o, HD}, in.prompt, c.wset2, c.nkeys, wabs, wsgn, B, t.heads, HW,
+                                                        KPr, t.DP, route.handover && k.store_calls[1] + 1 > 10 ? c.store_stats : nullptr, in.store_stream);
+                prof_begin(RT_PROF_ATTN_CROSS, 4.0 * t.heads * (double)HW * c.keysum * t.d);
+                launch_cross(a, route, stream);
+                prof_end();
+                if (capture2 && ++k.store_calls[1] > 10) {
+                    const int snk = c.nkeys[in.store_stream], srows = 96 * (snk / 77);
+                    RT_REQUIRE((size_t)HW * snk <= k.store_cap[1], "attention store: map larger than the enabled buffer");
+                    prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * snk * t.d, 8.0 * HW * snk + 2.0 * (HW + (double)srows) * HD);
+                    launch_attn_store(unet_store_args(a, in.store_stream, k.store[1], k.store_mode[1] == 2), stream);
+                    prof_end();
+                    k.store_rows[1] = HW; k.store_cols[1] = snk;
+                }
+                if (c.any_ip) {                                   // (the token-map store above recorded the text probabilities only)
+                    prof_begin(RT_PROF_IP_ATTN, 4.0 * t.heads * (double)HW * c.ip_keys * t.d, 3.0 * 2.0 * c.nip * HW * HD);
+                    launch_ip_attention(c.qk, HD, k.kipcache, HD, k.vtipcache, cfg.max_prompts * 16, c.o, HD, c.ip_slot, c.ip_cnt, c.ip_sc, B, t.heads, HW, t.DP, stream);
+                    prof_end();
+                }
+            }
+        }
+        ln.produce(c.o, HD, k.out2, true, ln.fold[2], ln.emit_out, true, &k.lora[7]);
+    }
+
+    // GEGLU feed-forward (attention.py:209-304)
+    void feed_forward(TCall& c, TBlockP& k, bool last) {
+        bf16_t* gg = ws.b16((size_t)c.M * 4 * c.C);
+        c.ln.consume(2, k.ln3, c.n, k.ff1, k.ff1f, k.ff1s, gg, 4 * c.C, EPI_GEGLU);
+        // the next block's norm1 reads what ff.net.2 leaves; behind the LAST block proj_out reads the trunk as bf16 - which is
+        // exactly the xb an emitting ff.net.2 writes (the cast launch in transformer() is then not needed)
+        c.ln.produce(gg, 4 * c.C, k.ff2, true, c.ln.fold[0], c.ln.emit_ff2, !last);
+    }
+
     // Transformer2DModel.forward (models/transformer_2d.py:270-310) + BasicTransformerBlock (attention.py:131-206)
     Tensor transformer(TransformerP& t, const FwdIn& in, int HW, Tensor x) {
         const int B = in.B, M = B * HW, C = t.C, HD = t.heads * t.DP;
@@ -945,209 +1169,27 @@ struct rt_engine {
         {
             Scope sc(ws);
             f16_t* hcur = ws.f16((size_t)M * C);
-            // LayerNorm folded into its consumers (gemm16.hip, "LNF"; attention.py:150,168,181) wherever every consumer of the LayerNorm has
-            // the folded instantiation - a pure function of the layer's shape (width, tokens per stream), never of the batch.  The trunk's
-            // producers (proj_in, to_out, ff.net.2: fp16-trunk epilogues) then leave the per-row partial sums next to it; a producer
-            // without that form is followed by the stand-alone partials kernel.  Debug bit 22 restores the LayerNorm launches.
-            float* part = ws.f32((size_t)M * 16);                    // up to 4 tile pairs x float4 per token
-            bf16_t* xb = ws.b16((size_t)M * C);                      // the trunk as bf16, written next to it by its producer
-            bool fold1 = false, fold2 = false, fold3 = false, emit_pin = false, emit_out = false, emit_ff2 = false;
-            int ln_bn = 160;                                         // column-tile width of the partials (a function of the class of the producers: of (C, tokens per stream))
-            if (gemm_lnfold_enabled() && ln_fold_width(C) && !t.blocks.empty() && t.blocks[0].qk1f.w) {
-                const TBlockP& k0 = t.blocks[0];
-                const int bn_pin = gemm_ln_emit_bn(dense_args(nullptr, C, t.pin, M, nullptr, C, EPI_F16));
-                const int bn_out = gemm_ln_emit_bn(dense_args(nullptr, HD, k0.out1, M, nullptr, C, EPI_F16));
-                const int bn_ff2 = gemm_ln_emit_bn(dense_args(nullptr, 4 * C, k0.ff2, M, nullptr, C, EPI_F16));
-                ln_bn = bn_out ? bn_out : (bn_ff2 ? bn_ff2 : (bn_pin ? bn_pin : 160));
-                emit_pin = bn_pin == ln_bn; emit_out = bn_out == ln_bn; emit_ff2 = bn_ff2 == ln_bn;     // (one class for all three: same N, same tokens per stream)
-                const int np = C / ln_bn / 2;
-                GemmArgs cq = dense_args(nullptr, C, k0.qk1f, M, nullptr, 2 * HD, EPI_BF16); cq.ln_npair = np;
-                GemmArgs cv = vt_args(k0.v1f, nullptr, C, M, nullptr, M); cv.ln_npair = np;
-                GemmArgs c2 = dense_args(nullptr, C, k0.q2f, M, nullptr, HD, EPI_BF16); c2.ln_npair = np;
-                GemmArgs c3 = dense_args(nullptr, C, k0.ff1f, M, nullptr, 4 * C, EPI_GEGLU); c3.ln_npair = np;
-                fold1 = gemm_ln_fold_ok(cq) && gemm_ln_fold_ok(cv);
-                fold2 = gemm_ln_fold_ok(c2);
-                fold3 = gemm_ln_fold_ok(c3);
-            }
-            const int npair = C / ln_bn / 2;
-            // partials of the trunk as it stands, for the LayerNorm that follows: from the producer's epilogue (`em` was passed to it) or here
-            auto partials_after = [&](bool emitted) { if (!emitted && !dry()) launch_ln_partials(hcur, xb, part, M, C, ln_bn, stream); };
-            LnFold em; em.emit = part; em.copy = xb;
-            // regional LoRA (rt_set_lora_scales): the adapted streams of this forward - those whose prompt slot has a non-zero scale - get the
-            // low-rank term added behind each of the eight attention projections; every other stream is in none of these launches
-            int l_rows[RT_MAXB]; float l_sc[RT_MAXB * 4];
-            bool any_lora = false;
-            for (int b = 0; b < B; ++b) {
-                const bool on = !dry() && !in.control && lora_on(in.prompt[b]);
-                l_rows[b] = b * HW;
-                for (int l = 0; l < 4; ++l) l_sc[4 * b + l] = on ? lora_scale[(size_t)in.prompt[b] * 4 + l] : 0.f;
-                any_lora = any_lora || on;
-            }
-            auto l_on = [&](int b) { return l_sc[4 * b] != 0.f || l_sc[4 * b + 1] != 0.f || l_sc[4 * b + 2] != 0.f || l_sc[4 * b + 3] != 0.f; };
-            // run f(first stream, streams) over the maximal runs of adapted streams (the row-wise kernels below take a run as one launch)
-            auto l_runs = [&](auto f) {
-                for (int b = 0; b < B;) {
-                    if (!l_on(b)) { ++b; continue; }
-                    int e = b; while (e < B && l_on(e)) ++e;
-                    f(b, e - b); b = e;
-                }
-            };
-            // a folded LayerNorm is never materialised: the adapters' input is computed for the adapted rows only, into `n`
-            auto l_norm = [&](const NormW& ln, bf16_t* n) {
-                l_runs([&](int b, int nb) { launch_layernorm(hcur + (size_t)b * HW * C, 1, ln.g, ln.b, n + (size_t)b * HW * C, nb * HW, C, 1e-5f, stream); });
-            };
-            // the adapted rows of the trunk changed behind a GEMM that emitted their LayerNorm partials and bf16 copy: recompute those rows'
-            auto l_partials = [&]() {
-                l_runs([&](int b, int nb) { launch_ln_partials(hcur + (size_t)b * HW * C, xb + (size_t)b * HW * C, part + (size_t)b * HW * 4, nb * HW, C, ln_bn, stream, M); });
-            };
+            float* part = ws.f32((size_t)M * 16);
+            bf16_t* xb = ws.b16((size_t)M * C);
+            TCall c(*this, t, in, HW, hcur, part, xb);
             {
                 Scope s2(ws);
                 bf16_t* g = ws.b16((size_t)M * C);
                 groupnorm(x.p, nullptr, 2, C, 0, B, HW, t.gn, 1e-6f, false, g, nullptr);
-                gemm(g, C, t.pin, M, hcur, C, EPI_F16, nullptr, 0, fold1 && emit_pin ? &em : nullptr);
-                if (fold1) partials_after(emit_pin);
+                c.ln.produce(g, C, t.pin, false, c.ln.fold[0], c.ln.emit_pin);
             }
             for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
-                TBlockP& k = t.blocks[bi];
-                const bool last = bi + 1 == t.blocks.size();
                 Scope s2(ws);
-                bf16_t* n = ws.b16((size_t)M * C);
-                // --- attn1 (self; attention_processor.py:476-545)
-                if (!fold1) layernorm(hcur, k.ln1, n, M);
-                bf16_t* qk = ws.b16((size_t)M * 2 * HD);
-                bf16_t* vt = ws.b16((size_t)HD * M);
-                bf16_t* o = ws.b16((size_t)M * HD);
-                float* store_stats = ws.f32((size_t)t.heads * HW * 2);      // softmax statistics of the token-map accumulation (attn_store.hip)
-                // Q,K are only needed for streams that some stream attends with (injected region streams use the
-                // text_ref stream's Q,K: attention_processor.py:522-524 discards their own scores)
-                int nqk = 0;
-                for (int b = 0; b < B; ++b) nqk = std::max(nqk, in.qk_src[b] + 1);
-                if (fold1) {
-                    LnFold lq; lq.part = part; lq.npair = npair; lq.ld = M; lq.s = k.qk1s;
-                    LnFold lv; lv.part = part; lv.npair = npair; lv.ld = M; lv.s = k.v1s;
-                    gemm_qk_vt(xb, C, k.qk1f, nqk * HW, qk, 2 * HD, k.v1f, M, vt, M, &lq, &lv);
-                } else gemm_qk_vt(n, C, k.qk1, nqk * HW, qk, 2 * HD, k.v1, M, vt, M);
-                if (any_lora) {
-                    // (an injected region stream attends with text_ref's Q and K - rows >= nqk are not even computed -, so its own to_q /
-                    // to_k adapters are moot; its to_v and to_out adapters act)
-                    if (fold1) l_norm(k.ln1, n);
-                    lora_add(k.lora[0], n, C, qk, 2 * HD, 0, l_rows, l_sc, nqk, HW);
-                    lora_add(k.lora[1], n, C, qk + HD, 2 * HD, 0, l_rows, l_sc, nqk, HW);
-                    lora_add(k.lora[2], n, C, vt, M, 1, l_rows, l_sc, B, HW);
-                }
-                if (!dry()) {
-                    // a layer whose map is recorded in this call: the attention launch leaves the softmax statistics of the recorded stream,
-                    // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
-                    const bool will_store = in.store_stream >= 0 && k.store_mode[0] && k.store_calls[0] + 1 > 10;      // n_maps[name] > 10 (rd.py:422, xl.py:988)
-                    const bool stats_from_attn = will_store && store_handover_self(HW, t.DP, in.qk_src, in.store_stream);
-                    const AttnArgs a = unet_self_attn_args(AttnIO{qk, 2 * HD, qk + HD, 2 * HD, vt, M, o, HD}, in.qk_src, B, t.heads, HW, t.DP,
-                                                           stats_from_attn ? store_stats : nullptr, in.store_stream);
-                    prof_begin(RT_PROF_ATTN_SELF, 4.0 * B * t.heads * (double)HW * HW * t.d);
-                    launch_attention(a, stream);
-                    prof_end();
-                    if (in.store_stream >= 0 && k.store_mode[0] && ++k.store_calls[0] > 10) {
-                        RT_REQUIRE((size_t)HW * HW <= k.store_cap[0], "attention store: map larger than the enabled buffer");
-                        prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * HW * t.d, 8.0 * HW * HW + 2.0 * 2.0 * HW * HD);
-                        launch_attn_store(unet_store_args(a, in.store_stream, k.store[0], k.store_mode[0] == 2, store_stats, HW), stream);
-                        prof_end();
-                        k.store_rows[0] = HW; k.store_cols[0] = HW;
-                    }
-                }
-                gemm(o, HD, k.out1, M, hcur, C, EPI_F16, hcur, C, fold2 && emit_out ? &em : nullptr);
-                if (any_lora) lora_add(k.lora[3], o, HD, hcur, C, 2, l_rows, l_sc, B, HW);      // a second fp16 rounding of the adapted rows (control_add_kernel's precedent)
-                if (fold2) partials_after(emit_out);
-                if (fold2 && emit_out && any_lora) l_partials();
-                // --- attn2 (cross, K/V from the per-prompt cache; font-size softmax on flagged streams)
-                if (!fold2) layernorm(hcur, k.ln2, n, M);
-                // the route (cross_route): a layer with its map enabled counts as recorded whether or not this call is past the tenth
-                const bool capture2 = in.store_stream >= 0 && k.store_mode[1];
-                const int KPr = KP(), ldvt2 = cfg.max_prompts * KPr;
-                int nkeys[RT_MAXB], wset2[RT_MAXB];
-                for (int b = 0; b < B; ++b) { nkeys[b] = prompt_keys[in.prompt[b]]; wset2[b] = in.fontsize[b] ? 1 : -1; }      // -1: plain softmax, no multiplier tables
-                CrossRoute route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2);
-                // image prompts (rt_set_image_prompts): the image term is added into o behind the text attention, which the one-launch forms
-                // never write - a launch with an image takes the two-launch route of the same shape
-                int ip_slot[RT_MAXB], ip_cnt[RT_MAXB]; float ip_sc[RT_MAXB];
-                bool any_ip = false;
-                double ip_keys = 0;
-                for (int b = 0; b < B; ++b) {
-                    const bool on = cfg.ip_tokens > 0 && !in.control && ip_scale[in.prompt[b]] != 0.f;
-                    ip_slot[b] = on ? in.prompt[b] : -1; ip_cnt[b] = on ? ip_count[in.prompt[b]] : 0; ip_sc[b] = on ? ip_scale[in.prompt[b]] : 0.f;
-                    if (on) { any_ip = true; ip_keys += ip_cnt[b]; }
-                }
-                // (Only RT_PROBES builds with their debug switches on ever reach the one-launch kinds.  The dry planning forward of an
-                // engine that can hold images takes the two-launch route as well, so that the to_q GEMM a launch with an image runs
-                // has been planned: its split-K scratch is recorded like every other GEMM's.)
-                // (regional LoRA likewise: to_q's term is added to a materialised Q, to_out's behind the GEMM)
-                if ((any_ip || any_lora || (dry() && (cfg.ip_tokens > 0 || cfg.lora_rank > 0) && !in.control)) && (route.kind == CrossRoute::XBLOCK || route.kind == CrossRoute::XATTN_FUSED))
-                    route = cross_route(C, t.heads, t.d, t.DP, HW, KPr, nkeys, B, fold2, capture2, false);
-                if (route.kind == CrossRoute::XBLOCK) {
-                    if (!dry()) {
-                        RT_REQUIRE(k.q2.K == C && k.out2.K == HD && HD == C, "xblock: packed projection widths");
-                        prof_begin(RT_PROF_XBLOCK, 4.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
-                        launch_xblock(unet_xblock_args(n, k.q2.w, k.out2.w, k.out2.b, k.kcache, k.vtcache, ldvt2, hcur, hcur, wabs, wsgn, in.prompt, wset2, B, HW, C, t.heads), stream);
-                        prof_end();
-                    }
-                } else if (route.kind == CrossRoute::XATTN_FUSED) {
-                    if (!dry()) {
-                        prof_begin(RT_PROF_XATTN_FUSED, 2.0 * M * HD * C + 4.0 * B * t.heads * (double)HW * 77 * t.d);
-                        launch_xattn_fused(unet_xattn_args(zero, n, k.q2.w, o, k.kcache, k.vtcache, ldvt2, wabs, wsgn, in.prompt, wset2, B, HW, C, t.heads), stream);
-                        prof_end();
-                    }
-                } else {
-                if (fold2) {
-                    LnFold l2; l2.part = part; l2.npair = npair; l2.ld = M; l2.s = k.q2s;
-                    gemm(xb, C, k.q2f, M, qk, HD, EPI_BF16, nullptr, 0, &l2);
-                } else gemm(n, C, k.q2, M, qk, HD, EPI_BF16);
-                if (any_lora) {
-                    if (fold2) l_norm(k.ln2, n);
-                    lora_add(k.lora[4], n, C, qk, HD, 0, l_rows, l_sc, B, HW);
-                }
-                if (!dry()) {
-                    // (a recorded layer on cross77_kernel hands its statistics over as attn1 does, from the eleventh recorded call on)
-                    const AttnArgs a = unet_cross_attn_args(AttnIO{qk, HD, k.kcache, HD, k.vtcache, ldvt2, o, HD}, in.prompt, wset2, nkeys, wabs, wsgn, B, t.heads, HW,
-                                                            KPr, t.DP, route.handover && k.store_calls[1] + 1 > 10 ? store_stats : nullptr, in.store_stream);
-                    double keysum = 0; for (int b = 0; b < B; ++b) keysum += nkeys[b];
-                    prof_begin(RT_PROF_ATTN_CROSS, 4.0 * t.heads * (double)HW * keysum * t.d);
-                    launch_cross(a, route, stream);
-                    prof_end();
-                    if (capture2 && ++k.store_calls[1] > 10) {
-                        const int snk = nkeys[in.store_stream], srows = 96 * (snk / 77);
-                        RT_REQUIRE((size_t)HW * snk <= k.store_cap[1], "attention store: map larger than the enabled buffer");
-                        prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * snk * t.d, 8.0 * HW * snk + 2.0 * (HW + (double)srows) * HD);
-                        launch_attn_store(unet_store_args(a, in.store_stream, k.store[1], k.store_mode[1] == 2), stream);
-                        prof_end();
-                        k.store_rows[1] = HW; k.store_cols[1] = snk;
-                    }
-                    if (any_ip) {                                     // (the token-map store above recorded the text probabilities only)
-                        double nip = 0; for (int b = 0; b < B; ++b) nip += ip_slot[b] >= 0;
-                        prof_begin(RT_PROF_IP_ATTN, 4.0 * t.heads * (double)HW * ip_keys * t.d, 3.0 * 2.0 * nip * HW * HD);
-                        launch_ip_attention(qk, HD, k.kipcache, HD, k.vtipcache, cfg.max_prompts * 16, o, HD, ip_slot, ip_cnt, ip_sc, B, t.heads, HW, t.DP, stream);
-                        prof_end();
-                    }
-                }
-                }
-                const bool out2_done = route.kind == CrossRoute::XBLOCK;      // to_out + residual were part of that launch
-                if (!out2_done) gemm(o, HD, k.out2, M, hcur, C, EPI_F16, hcur, C, fold3 && emit_out ? &em : nullptr);
-                if (any_lora) lora_add(k.lora[7], o, HD, hcur, C, 2, l_rows, l_sc, B, HW);      // (any_lora: never the one-launch block)
-                if (fold3) partials_after(!out2_done && emit_out);
-                if (fold3 && !out2_done && emit_out && any_lora) l_partials();
-                // --- GEGLU feed-forward (attention.py:209-304)
-                bf16_t* gg = ws.b16((size_t)M * 4 * C);
-                if (fold3) {
-                    LnFold l3; l3.part = part; l3.npair = npair; l3.ld = M; l3.s = k.ff1s;
-                    gemm(xb, C, k.ff1f, M, gg, 4 * C, EPI_GEGLU, nullptr, 0, &l3);
-                } else {
-                    layernorm(hcur, k.ln3, n, M);
-                    gemm(n, C, k.ff1, M, gg, 4 * C, EPI_GEGLU);
-                }
-                // the next block's norm1 reads what ff.net.2 leaves; behind the LAST block proj_out reads the trunk as bf16 - which is
-                // exactly the xb an emitting ff.net.2 writes (the cast launch below is then not needed)
-                const bool need1 = fold1 && !last, copy_last = last && fold1 && emit_ff2;
-                gemm(gg, 4 * C, k.ff2, M, hcur, C, EPI_F16, hcur, C, (need1 || copy_last) && emit_ff2 ? &em : nullptr);
-                if (need1) partials_after(emit_ff2);
+                c.n = ws.b16((size_t)M * C);
+                c.qk = ws.b16((size_t)M * 2 * HD);
+                c.vt = ws.b16((size_t)HD * M);
+                c.o = ws.b16((size_t)M * HD);
+                c.store_stats = ws.f32((size_t)t.heads * HW * 2);
+                attn1(c, t.blocks[bi]);
+                attn2(c, t.blocks[bi]);
+                feed_forward(c, t.blocks[bi], bi + 1 == t.blocks.size());
             }
-            const bool have_xb = fold1 && emit_ff2 && !t.blocks.empty();
+            const bool have_xb = c.ln.fold[0] && c.ln.emit_ff2 && !t.blocks.empty();
             bf16_t* hb = ws.b16((size_t)M * C);
             if (!dry() && !have_xb) launch_cast_f16_bf16(hcur, hb, (size_t)M * C, stream);
             gemm(have_xb ? xb : hb, C, t.pout, M, out, C, EPI_F16, x.p, C);
@@ -1193,21 +1235,99 @@ struct rt_engine {
         launch_control_add(dst.p, (size_t)HW * C, C, r, (size_t)HW * C, C, cs, csc, Bc, B, HW, C, stream);
         prof_end();
     }
+    // ---------------------------------------------------------------------------- the forward
+    // The time / addition embeddings of a forward of `net` (unet_2d_condition.py:784-877) and from them time_emb_proj(silu(emb)) of every
+    // resnet of its table (resnet.py:611-613) in one launch: [resnet][B][cout], allocated in the caller's scope - it lives as long as the
+    // forward - and handed to resnet() by the caller
+    const float* time_embed(const NetP& net, const FwdIn& in) {
+        const int B = in.B, C0 = cfg.block_out_channels[0];
+        float* emb = ws.f32((size_t)B * temb_dim);
+        {
+            Scope sc(ws);
+            float* tsin = ws.f32(C0);
+            float* e1 = ws.f32(temb_dim); float* e2 = ws.f32(temb_dim);
+            if (!dry()) {
+                launch_timestep_embed_scalar(in.t, C0, tsin, stream);
+                launch_small_linear(tsin, C0, net.t1.w, net.t1.K, net.t1.b, e1, temb_dim, 1, temb_dim, net.t1.K, 0, 0, stream);
+                launch_small_linear(e1, temb_dim, net.t2.w, net.t2.K, net.t2.b, e2, temb_dim, 1, temb_dim, temb_dim, 1, 0, stream);
+                launch_gather_add_rows(e2, net.aug_emb, in.prompt, emb, B, temb_dim, stream);
+            }
+        }
+        float* temb = ws.f32((size_t)B * net.temb_total);
+        {
+            Scope sc(ws);
+            float* semb = ws.f32((size_t)B * temb_dim);
+            if (!dry()) launch_temb_all(emb, temb_dim, semb, net.temb_tab_dev, (int)net.temb_tab.size(), net.temb_total, B, temb_dim, temb, stream);
+        }
+        return temb;
+    }
+    // The encoder of `net` on the streams of `in`: stem, down blocks, mid block; returns the mid block's output on the grid (ch, cw).
+    // stem(x8, x0): conv_in of the prepared latents x8 [B, HW0, 8] into x0.  skip(x, HW): every tensor the up path takes as a skip, in order.
+    template <typename Stem, typename Skip>
+    Tensor encode(NetP& net, const FwdIn& in, const float* temb, int& ch, int& cw, Stem stem, Skip skip) {
+        const int B = in.B, HW0 = in.h * in.w, C0 = cfg.block_out_channels[0];
+        Tensor x;
+        {
+            f16_t* x0 = ws.f16((size_t)B * HW0 * C0);
+            Scope sc(ws);
+            bf16_t* x8 = ws.b16((size_t)B * HW0 * 8);
+            if (!dry()) {
+                PrepArgs p{}; p.B = B; p.HW = HW0; p.dst = x8;
+                for (int b = 0; b < B; ++b) { p.src[b] = in.x[b]; p.scale[b] = in.scale[b]; }
+                launch_prep_latents(p, stream);
+            }
+            stem(x8, x0);
+            x = Tensor{x0, C0};
+        }
+        if (tracing()) trace_point(net.prefix + "conv_in", x, B, HW0);
+        skip(x, HW0);
+        ch = in.h; cw = in.w;
+        for (size_t i = 0; i < net.down.size(); ++i) {
+            DownP& d = net.down[i];
+            for (size_t j = 0; j < d.res.size(); ++j) {
+                x = resnet(d.res[j], in, ch * cw, ch, cw, x, nullptr, temb, false);
+                trace_point(d.res[j].name, x, B, ch * cw);
+                if (d.has_attn) { x = transformer(d.attn[j], in, ch * cw, x); trace_point(d.attn[j].name, x, B, ch * cw); }
+                skip(x, ch * cw);
+            }
+            if (d.has_down) {
+                const int nh = (ch + 1) / 2, nw = (cw + 1) / 2;
+                f16_t* y = ws.f16((size_t)B * nh * nw * d.C);
+                {
+                    Scope sc(ws);
+                    bf16_t* xb = ws.b16((size_t)B * ch * cw * d.C);
+                    if (!dry()) launch_cast_f16_bf16(x.p, xb, (size_t)B * ch * cw * d.C, stream);
+                    conv3(xb, A_CONV3_S2, d.down, B, ch, cw, d.C, y, EPI_F16);
+                }
+                ch = nh; cw = nw;
+                x = Tensor{y, d.C};
+                if (tracing()) trace_point(net.prefix + "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", x, B, ch * cw);
+                skip(x, ch * cw);
+            }
+        }
+        x = resnet(net.mid_r0, in, ch * cw, ch, cw, x, nullptr, temb, false);
+        trace_point(net.mid_r0.name, x, B, ch * cw);
+        x = transformer(net.mid_t, in, ch * cw, x);
+        trace_point(net.mid_t.name, x, B, ch * cw);
+        x = resnet(net.mid_r1, in, ch * cw, ch, cw, x, nullptr, temb, false);
+        trace_point(net.mid_r1.name, x, B, ch * cw);
+        return x;
+    }
+
     // ControlNetModel.forward for the controlled streams of `in`, behind the main UNet's mid block: adds scale x zero_conv(skip_k) into
     // skips[k] and scale x zero_conv(mid) into xmid, in place.  Everything it allocates is released when it returns.
-    void control_forward(const FwdIn& in, std::vector<Tensor>& skips, Tensor& xmid) {
+    void control_pass(const FwdIn& in, std::vector<Tensor>& skips, Tensor& xmid) {
         int cs[RT_MAXB]; float csc[RT_MAXB];
         const int Bc = control_streams(in, cs, csc), B = in.B, Hh = in.h, Ww = in.w, HW0 = Hh * Ww, C0 = cfg.block_out_channels[0];
-        const std::string P = "controlnet.";
-        auto trace_main = [&](const std::string& n, const Tensor& t, int HW) { if (tracing()) trace_point(P + n, t, B, HW); };
+        auto trace_main = [&](const std::string& n, const Tensor& t, int HW) { trace_point(cnet.prefix + n, t, B, HW); };      // (asked under tracing() only)
         if (tracing() && trace_name == "controlnet.hint_embedding") launch_trace_f16_nhwc_to_nchw(ctl.emb_f16, trace_out, 1, C0, HW0, stream);
         if (!Bc) {                        // nothing runs; the main-side trace points read the tensors as the up path will
             if (tracing()) {
                 int ch = Hh, cw = Ww; size_t k = 0;
                 trace_main("skip.0", skips[k++], ch * cw);
-                for (size_t i = 0; i < down.size(); ++i) {
-                    for (size_t j = 0; j < down[i].res.size(); ++j, ++k) trace_main("skip." + std::to_string(k), skips[k], ch * cw);
-                    if (down[i].has_down) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; trace_main("skip." + std::to_string(k), skips[k], ch * cw); ++k; }
+                for (const DownP& d : unet.down) {
+                    for (size_t j = 0; j < d.res.size(); ++j, ++k) trace_main("skip." + std::to_string(k), skips[k], ch * cw);
+                    if (d.has_down) { ch = (ch + 1) / 2; cw = (cw + 1) / 2; trace_main("skip." + std::to_string(k), skips[k], ch * cw); ++k; }
                 }
                 trace_main("mid", xmid, ch * cw);
             }
@@ -1219,84 +1339,25 @@ struct rt_engine {
             c.fontsize[i] = 0; c.qk_src[i] = i; c.res_src[i] = -1;
         }
         Scope sc(ws);
-        float* const main_temb = temb_all;
-        float* emb = ws.f32((size_t)Bc * temb_dim);
-        {
-            Scope s2(ws);
-            float* tsin = ws.f32(C0);
-            float* e1 = ws.f32(temb_dim); float* e2 = ws.f32(temb_dim);
-            if (!dry()) {
-                launch_timestep_embed_scalar(c.t, C0, tsin, stream);
-                launch_small_linear(tsin, C0, ctl.t1.w, ctl.t1.K, ctl.t1.b, e1, temb_dim, 1, temb_dim, ctl.t1.K, 0, 0, stream);
-                launch_small_linear(e1, temb_dim, ctl.t2.w, ctl.t2.K, ctl.t2.b, e2, temb_dim, 1, temb_dim, temb_dim, 1, 0, stream);
-                launch_gather_add_rows(e2, ctl.aug_emb, c.prompt, emb, Bc, temb_dim, stream);
-            }
-        }
-        temb_all = ws.f32((size_t)Bc * ctl.temb_total);      // resnet() reads the running forward's table: the control copy's while it runs
-        {
-            Scope s2(ws);
-            float* semb = ws.f32((size_t)Bc * temb_dim);
-            if (!dry()) launch_temb_all(emb, temb_dim, semb, ctl.temb_tab_dev, (int)ctl.temb_tab.size(), ctl.temb_total, Bc, temb_dim, temb_all, stream);
-        }
+        const float* temb = time_embed(cnet, c);
         size_t k = 0;
-        Tensor x;
-        {
-            f16_t* x0 = ws.f16((size_t)Bc * HW0 * C0);
-            Scope s2(ws);
-            bf16_t* x8 = ws.b16((size_t)Bc * HW0 * 8);
-            if (!dry()) {
-                PrepArgs p{}; p.B = Bc; p.HW = HW0; p.dst = x8;
-                for (int i = 0; i < Bc; ++i) { p.src[i] = c.x[i]; p.scale[i] = c.scale[i]; }
-                launch_prep_latents(p, stream);
-            }
+        int ch, cw;
+        Tensor x = encode(cnet, c, temb, ch, cw,
             // conv_in(x) + hint embedding: the embedding [HW0, C0] is the residual operand of the convolution's epilogue (fp32 sum, one
             // rounding to fp16) - one launch per controlled stream, each the launch of a stream that runs alone
-            for (int i = 0; i < Bc; ++i)
-                conv3(x8 + (size_t)i * HW0 * 8, A_CONV3, ctl.conv_in, 1, Hh, Ww, 8, x0 + (size_t)i * HW0 * C0, EPI_F16, ctl.emb_f16);
-            x = Tensor{x0, C0};
-        }
-        if (tracing()) trace_point(P + "conv_in", x, Bc, HW0);
-        auto residual = [&](int HW) {
-            RT_REQUIRE(k < skips.size() && k < ctl.zero.size(), "controlnet: more control skips than skips");
-            control_residual(ctl.zero[k], x, skips[k], cs, csc, Bc, B, HW);
-            trace_main("skip." + std::to_string(k), skips[k], HW);
-            ++k;
-        };
-        residual(HW0);
-        int ch = Hh, cw = Ww;
-        for (size_t i = 0; i < ctl.down.size(); ++i) {
-            DownP& d = ctl.down[i];
-            for (size_t j = 0; j < d.res.size(); ++j) {
-                x = resnet(d.res[j], c, ch * cw, ch, cw, x, nullptr, emb, false);
-                trace_point(d.res[j].name, x, Bc, ch * cw);
-                if (d.has_attn) { x = transformer(d.attn[j], c, ch * cw, x); trace_point(d.attn[j].name, x, Bc, ch * cw); }
-                residual(ch * cw);
-            }
-            if (d.has_down) {
-                const int nh = (ch + 1) / 2, nw = (cw + 1) / 2;
-                f16_t* y = ws.f16((size_t)Bc * nh * nw * d.C);
-                {
-                    Scope s2(ws);
-                    bf16_t* xb = ws.b16((size_t)Bc * ch * cw * d.C);
-                    if (!dry()) launch_cast_f16_bf16(x.p, xb, (size_t)Bc * ch * cw * d.C, stream);
-                    conv3(xb, A_CONV3_S2, d.down, Bc, ch, cw, d.C, y, EPI_F16);
-                }
-                ch = nh; cw = nw;
-                x = Tensor{y, d.C};
-                if (tracing()) trace_point(P + "down_blocks." + std::to_string(i) + ".downsamplers.0.conv", x, Bc, ch * cw);
-                residual(ch * cw);
-            }
-        }
+            [&](const bf16_t* x8, f16_t* x0) {
+                for (int i = 0; i < Bc; ++i) conv3(x8 + (size_t)i * HW0 * 8, A_CONV3, cnet.conv_in, 1, Hh, Ww, 8, x0 + (size_t)i * HW0 * C0, EPI_F16, ctl.emb_f16);
+            },
+            // one residual per skip of the control copy, and its main-side trace point
+            [&](const Tensor& xc, int HW) {
+                RT_REQUIRE(k < skips.size() && k < ctl.zero.size(), "controlnet: more control skips than skips");
+                control_residual(ctl.zero[k], xc, skips[k], cs, csc, Bc, B, HW);
+                if (tracing()) trace_main("skip." + std::to_string(k), skips[k], HW);
+                ++k;
+            });
         RT_REQUIRE(k == skips.size(), "controlnet: skip count");
-        x = resnet(ctl.mid_r0, c, ch * cw, ch, cw, x, nullptr, emb, false);
-        trace_point(ctl.mid_r0.name, x, Bc, ch * cw);
-        x = transformer(ctl.mid_t, c, ch * cw, x);
-        trace_point(ctl.mid_t.name, x, Bc, ch * cw);
-        x = resnet(ctl.mid_r1, c, ch * cw, ch, cw, x, nullptr, emb, false);
-        trace_point(ctl.mid_r1.name, x, Bc, ch * cw);
         control_residual(ctl.zero_mid, x, xmid, cs, csc, Bc, B, ch * cw);
-        trace_main("mid", xmid, ch * cw);
-        temb_all = main_temb;
+        if (tracing()) trace_main("mid", xmid, ch * cw);
     }
 
     // UNet2DConditionModel.forward (models/unet_2d_condition.py:703-983), batched over streams
@@ -1311,77 +1372,15 @@ struct rt_engine {
         if (cfg.controlnet && !dry()) control_check(in);
         if (!dry()) ensure_fold();       // (normally a no-op: rt_set_prompts derived the folded projections already)
         const size_t m0 = ws.mark();
-        // time / addition embeddings (unet_2d_condition.py:784-877)
-        float* emb = ws.f32((size_t)B * temb_dim);
-        {
-            Scope sc(ws);
-            float* tsin = ws.f32(cfg.block_out_channels[0]);
-            float* e1 = ws.f32(temb_dim); float* e2 = ws.f32(temb_dim);
-            if (!dry()) {
-                launch_timestep_embed_scalar(in.t, cfg.block_out_channels[0], tsin, stream);
-                launch_small_linear(tsin, cfg.block_out_channels[0], t1.w, t1.K, t1.b, e1, temb_dim, 1, temb_dim, t1.K, 0, 0, stream);
-                launch_small_linear(e1, temb_dim, t2.w, t2.K, t2.b, e2, temb_dim, 1, temb_dim, temb_dim, 1, 0, stream);
-                launch_gather_add_rows(e2, aug_emb, in.prompt, emb, B, temb_dim, stream);
-            }
-        }
-        // time_emb_proj(silu(emb)) of every resnet (resnet.py:611-613): one launch, buffer lives for the whole forward
-        temb_all = ws.f32((size_t)B * temb_total);
-        {
-            Scope sc(ws);
-            float* semb = ws.f32((size_t)B * temb_dim);
-            if (!dry()) {
-                launch_temb_all(emb, temb_dim, semb, temb_tab_dev, (int)temb_tab.size(), temb_total, B, temb_dim, temb_all, stream);
-            }
-        }
+        const float* temb = time_embed(unet, in);
         std::vector<Tensor> skips;
-        Tensor x;
-        {
-            f16_t* x0 = ws.f16((size_t)B * HW0 * cfg.block_out_channels[0]);
-            Scope sc(ws);
-            bf16_t* x8 = ws.b16((size_t)B * HW0 * 8);
-            if (!dry()) {
-                PrepArgs p{}; p.B = B; p.HW = HW0; p.dst = x8;
-                for (int b = 0; b < B; ++b) { p.src[b] = in.x[b]; p.scale[b] = in.scale[b]; }
-                launch_prep_latents(p, stream);
-            }
-            conv3(x8, A_CONV3, conv_in, B, Hh, Ww, 8, x0, EPI_F16);
-            x = Tensor{x0, cfg.block_out_channels[0]};
-        }
-        if (tracing()) trace_point("conv_in", x, B, HW0);
-        skips.push_back(x);
-        int ch = Hh, cw = Ww;
-        for (size_t i = 0; i < down.size(); ++i) {
-            DownP& d = down[i];
-            for (size_t j = 0; j < d.res.size(); ++j) {
-                x = resnet(d.res[j], in, ch * cw, ch, cw, x, nullptr, emb, false);
-                trace_point(d.res[j].name, x, B, ch * cw);
-                if (d.has_attn) { x = transformer(d.attn[j], in, ch * cw, x); trace_point(d.attn[j].name, x, B, ch * cw); }
-                skips.push_back(x);
-            }
-            if (d.has_down) {
-                const int nh = (ch + 1) / 2, nw = (cw + 1) / 2;
-                f16_t* y = ws.f16((size_t)B * nh * nw * d.C);
-                {
-                    Scope sc(ws);
-                    bf16_t* xb = ws.b16((size_t)B * ch * cw * d.C);
-                    if (!dry()) launch_cast_f16_bf16(x.p, xb, (size_t)B * ch * cw * d.C, stream);
-                    conv3(xb, A_CONV3_S2, d.down, B, ch, cw, d.C, y, EPI_F16);
-                }
-                ch = nh; cw = nw;
-                x = Tensor{y, d.C};
-                if (tracing()) trace_point("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", x, B, ch * cw);
-                skips.push_back(x);
-            }
-        }
-        x = resnet(mid_r0, in, ch * cw, ch, cw, x, nullptr, emb, false);
-        trace_point(mid_r0.name, x, B, ch * cw);
-        x = transformer(mid_t, in, ch * cw, x);
-        trace_point(mid_t.name, x, B, ch * cw);
-        x = resnet(mid_r1, in, ch * cw, ch, cw, x, nullptr, emb, false);
-        trace_point(mid_r1.name, x, B, ch * cw);
-        if (cfg.controlnet) control_forward(in, skips, x);
-        for (size_t i = 0; i < up.size(); ++i) {
-            UpP& u = up[i];
+        int ch, cw;
+        Tensor x = encode(unet, in, temb, ch, cw,
+            [&](const bf16_t* x8, f16_t* x0) { conv3(x8, A_CONV3, unet.conv_in, B, Hh, Ww, 8, x0, EPI_F16); },
+            [&](const Tensor& s, int) { skips.push_back(s); });
+        if (cfg.controlnet) control_pass(in, skips, x);
+        for (size_t i = 0; i < unet.up.size(); ++i) {
+            UpP& u = unet.up[i];
             for (size_t j = 0; j < u.res.size(); ++j) {
                 Tensor sk = skips.back(); skips.pop_back();
                 const bool inject_here = (i == 1 && j == 1);        // 'up_blocks.1.resnets.1' (rd.py:350, xl.py:1101)
@@ -1393,7 +1392,7 @@ struct rt_engine {
                     launch_freeu(x.p, x.C, sk.p, sk.C, B, ch, cw, fu_b[i], fu_s[i], stream);
                     prof_end();
                 }
-                x = resnet(u.res[j], in, ch * cw, ch, cw, x, &sk, emb, inject_here);
+                x = resnet(u.res[j], in, ch * cw, ch, cw, x, &sk, temb, inject_here);
                 trace_point(u.res[j].name, x, B, ch * cw);
                 if (u.has_attn) { x = transformer(u.attn[j], in, ch * cw, x); trace_point(u.attn[j].name, x, B, ch * cw); }
             }
@@ -1440,26 +1439,15 @@ struct rt_engine {
         // rows past a prompt's own keys are zeros: their K / V^T rows are finite, and masked by every attention kernel
         for (int p_ = 0; p_ < P; ++p_)
             launch_pad_ctx(pe + (size_t)p_ * L * D, ctx + (size_t)p_ * KPr * D, counts ? counts[p_] : L, KPr, D, stream);
-        auto build = [&](TransformerP& t) {
-            const int HD = t.heads * t.DP;
-            for (TBlockP& k : t.blocks) {
-                gemm(ctx, D, k.k2, P * KPr, k.kcache, HD, EPI_BF16);
-                gemm_vt(k.v2, ctx, D, P * KPr, k.vtcache, cfg.max_prompts * KPr);
-            }
-        };
         // one prompt = one "stream" of 96 rows: the tile class / split-K rule of these GEMMs is keyed on that, so a prompt's cached
         // K / V bits do not depend on how many other prompts share the set
         cur_hw = 96;
-        for (auto& d : down) for (auto& t : d.attn) build(t);
-        build(mid_t);
-        for (auto& u : up) for (auto& t : u.attn) build(t);
-        if (cfg.controlnet) {
-            for (auto& d : ctl.down) for (auto& t : d.attn) build(t);
-            build(ctl.mid_t);
-        }
+        for (NetP* net : nets) net->for_each_tblock([&](TransformerP& t, TBlockP& k) {
+            gemm(ctx, D, k.k2, P * KPr, k.kcache, t.heads * t.DP, EPI_BF16);
+            gemm_vt(k.v2, ctx, D, P * KPr, k.vtcache, cfg.max_prompts * KPr);
+        });
         cur_hw = 0;
-        HIP_CHECK(hipMemsetAsync(aug_emb, 0, (size_t)cfg.max_prompts * temb_dim * 4, stream));
-        if (cfg.controlnet) HIP_CHECK(hipMemsetAsync(ctl.aug_emb, 0, (size_t)cfg.max_prompts * temb_dim * 4, stream));
+        for (NetP* net : nets) HIP_CHECK(hipMemsetAsync(net->aug_emb, 0, (size_t)cfg.max_prompts * temb_dim * 4, stream));
         if (cfg.addition_text_time) {
             RT_REQUIRE(pooled && time_ids, "set_prompts: SDXL needs pooled embeds and time_ids");
             const int td = cfg.addition_time_embed_dim, Kin = cfg.projection_class_embeddings_input_dim;
@@ -1472,11 +1460,9 @@ struct rt_engine {
                 HIP_CHECK(hipMemcpyAsync(add + (size_t)p_ * Kin, pooled + (size_t)p_ * pooled_dim, (size_t)pooled_dim * 4, hipMemcpyDeviceToDevice, stream));
                 HIP_CHECK(hipMemcpyAsync(add + (size_t)p_ * Kin + pooled_dim, tsin, (size_t)6 * td * 4, hipMemcpyDeviceToDevice, stream));
             }
-            launch_small_linear(add, Kin, a1.w, a1.K, a1.b, hmid, temb_dim, P, temb_dim, Kin, 0, 0, stream);
-            launch_small_linear(hmid, temb_dim, a2.w, a2.K, a2.b, aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
-            if (cfg.controlnet) {      // the control copy's own add_embedding of the same (pooled | time ids) rows
-                launch_small_linear(add, Kin, ctl.a1.w, ctl.a1.K, ctl.a1.b, hmid, temb_dim, P, temb_dim, Kin, 0, 0, stream);
-                launch_small_linear(hmid, temb_dim, ctl.a2.w, ctl.a2.K, ctl.a2.b, ctl.aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
+            for (NetP* net : nets) {      // every network's own add_embedding of the same (pooled | time ids) rows
+                launch_small_linear(add, Kin, net->a1.w, net->a1.K, net->a1.b, hmid, temb_dim, P, temb_dim, Kin, 0, 0, stream);
+                launch_small_linear(hmid, temb_dim, net->a2.w, net->a2.K, net->a2.b, net->aug_emb, temb_dim, P, temb_dim, temb_dim, 1, 0, stream);
             }
         }
         n_prompts = P;
@@ -1650,17 +1636,6 @@ struct rt_engine {
         HIP_CHECK(hipStreamSynchronize(stream));
     }
 
-    template <typename F> void for_each_tblock(F f) {
-        for (auto& d : down) for (auto& t : d.attn) for (auto& k : t.blocks) f(t, k);
-        for (auto& k : mid_t.blocks) f(mid_t, k);
-        for (auto& u : up) for (auto& t : u.attn) for (auto& k : t.blocks) f(t, k);
-    }
-    // ... and the ControlNet's copy behind them (the token-map store and the image prompts are the UNet's alone: they keep for_each_tblock)
-    template <typename F> void for_each_tblock_all(F f) {
-        for_each_tblock(f);
-        for (auto& d : ctl.down) for (auto& t : d.attn) for (auto& k : t.blocks) f(t, k);
-        for (auto& k : ctl.mid_t.blocks) f(ctl.mid_t, k);
-    }
     bool any_store() { bool any = false; for_each_tblock([&](TransformerP&, TBlockP& k) { any |= k.store_mode[0] || k.store_mode[1]; }); return any; }
     void attn_store_enable(const std::string& name, int mode) {
         bool found = false;
@@ -1780,7 +1755,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
             {   // the K / V^T cache GEMMs of rt_set_prompts (one prompt = one 96-row stream) at the largest prompt count
                 const int D = cfg->cross_attention_dim, P96 = cfg->max_prompts * e->KP();
                 e->cur_hw = 96;
-                e->for_each_tblock_all([&](TransformerP& t, TBlockP& k) {
+                for (NetP* net : e->nets) net->for_each_tblock([&](TransformerP& t, TBlockP& k) {
                     e->gemm(nullptr, D, k.k2, P96, nullptr, t.heads * t.DP, EPI_BF16);
                     e->gemm_vt(k.v2, nullptr, D, P96, nullptr, P96);
                     if (cfg->ip_tokens > 0 && k.kip.w) {      // ... and those of rt_set_image_prompts (one slot = one 16-row stream)
@@ -1816,13 +1791,10 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
                 HIP_CHECK(hipMalloc((void**)&e->splitk_buf, e->splitk_need * 4));
                 e->splitk_floats = e->splitk_need;
             }
-            if (!e->temb_tab.empty()) {      // the time_emb_proj table of temb_all_kernel: batch-independent, uploaded once
-                HIP_CHECK(hipMalloc((void**)&e->temb_tab_dev, e->temb_tab.size() * sizeof(TembEntry)));
-                HIP_CHECK(hipMemcpy(e->temb_tab_dev, e->temb_tab.data(), e->temb_tab.size() * sizeof(TembEntry), hipMemcpyHostToDevice));
-            }
-            if (!e->ctl.temb_tab.empty()) {
-                HIP_CHECK(hipMalloc((void**)&e->ctl.temb_tab_dev, e->ctl.temb_tab.size() * sizeof(TembEntry)));
-                HIP_CHECK(hipMemcpy(e->ctl.temb_tab_dev, e->ctl.temb_tab.data(), e->ctl.temb_tab.size() * sizeof(TembEntry), hipMemcpyHostToDevice));
+            for (NetP* net : e->nets) {      // the time_emb_proj table of temb_all_kernel: batch-independent, uploaded once
+                if (net->temb_tab.empty()) continue;
+                HIP_CHECK(hipMalloc((void**)&net->temb_tab_dev, net->temb_tab.size() * sizeof(TembEntry)));
+                HIP_CHECK(hipMemcpy(net->temb_tab_dev, net->temb_tab.data(), net->temb_tab.size() * sizeof(TembEntry), hipMemcpyHostToDevice));
             }
         }
         e->set_fontsize(nullptr, nullptr, 0);      // multiplier set 0/1 = plain softmax until rt_set_fontsize is called
@@ -1840,8 +1812,9 @@ int rt_destroy(rt_engine* e) {
     if (e->arena_base) {
         (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->stream);
         for (auto& r : e->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->temb_tab_dev); (void)hipFree(e->splitk_buf); (void)hipFree(e->src_buf);
-        (void)hipFree(e->ctl.temb_tab_dev); (void)hipFree(e->ctl.emb_f32); (void)hipFree(e->ctl.emb_f16);
+        (void)hipFree(e->arena_base); (void)hipFree(e->sarena_base); (void)hipFree(e->farena_base); (void)hipFree(e->ws.base); (void)hipFree(e->splitk_buf); (void)hipFree(e->src_buf);
+        for (NetP* net : e->nets) (void)hipFree(net->temb_tab_dev);
+        (void)hipFree(e->ctl.emb_f32); (void)hipFree(e->ctl.emb_f16);
         (void)hipStreamDestroy(e->own_stream);
     }
     delete e;
