@@ -170,6 +170,35 @@ int rt_set_lora_columns(rt_engine* e, const int* col_adapter_host, int R);
  * rt_set_lora_scales adapts. */
 int rt_attn_cache_info(rt_engine* e, int idx, void** kcache, void** vtcache, long long* bytes_each);
 int rt_set_lora_scales(rt_engine* e, const float* scales_host /* [n_prompts][4] */, int n_prompts);
+/* Perturbed-attention guidance, scaled per prompt slot (no counterpart in the reference; [memory] diffusers' enable_pag / pag_scale /
+ * pag_applied_layers with PAGCFGIdentitySelfAttnProcessor2_0 - parity with it is unpinned; csrc/pag.hip).  A slot with sigma != 0 gets a
+ * TWIN of the conditional stream that runs it: one more stream of the step's one batched forward, behind all existing streams, with its
+ * partner's latents, input scale, prompt slot, font-size flag, Q / K source, ResNet-feature source, image-prompt term, LoRA scales and
+ * ControlNet treatment.  At every APPLIED attn1 module the twin's attention output is O = V = to_v(norm1(x)), head for head - no Q, no
+ * K, no softmax; to_out.0 and the residual follow as usual - and at every other module it is an ordinary stream (the twin of an injected
+ * region stream still attends with text_ref's Q / K there and takes its ResNet feature).  With T_r the prediction of the stream of slot
+ * r, P_r its twin's and m_r its mask:
+ *   eps = u + g (sum_r m_r T_r - u) + sum_r m_r sigma_r (T_r - P_r)
+ * computed as ONE launch ahead of the step's epilogue, eps[s] <- fmaf(sigma / g, eps[s] - eps[twin], eps[s]) (sigma / g formed in fp32 on
+ * the host), after which the unchanged two-term guidance is the three-term formula; v-prediction composes (everything is linear).  The
+ * stepped reference pair gets the plain pass's treatment with the base slot's sigma: u_ref + g (T_ref - u_ref) + sigma_base (T_ref - P_ref).
+ * rt_set_pag_layers: ';'-joined attn1 module names as rt_attn_module_info lists them (NULL / "": none).  Needs no device; survives every
+ *   other call.  An unknown name, an attn2 name, or an empty set while a slot has sigma != 0 is RT_E_INVALID naming the offender.
+ * rt_set_pag_scales: one finite sigma per prompt slot of rt_set_prompts (slots n_prompts .. are 0), the calling pattern of
+ *   rt_set_control_scales: slot 0 is the negative prompt - it has no twin, a non-zero value is refused -, the rich pass runs region r on
+ *   slot r + 1 and the base prompt (base stream, and text_ref while the pair is stepped) on the last slot, the plain pass its text on slot
+ *   1.  rt_set_prompts / rt_set_prompts_keys reset every sigma to 0.  A bad argument leaves the state alone.
+ * Stream order of a rich step: [uncond, base, uncond_ref, text_ref, regions ..., twin of base, twin of text_ref (only while the pair is
+ * stepped), twins of the regions with sigma != 0]; of a plain step: [uncond, text, twin of text].  rt_region_step_part's plan_info[0]
+ * counts the twins; the split keeps text_ref, the regions and every twin in the last range while the injection is on, and the plain twin
+ * rides with the text stream's part.  More streams than rt_config.max_streams is RT_E_INVALID naming both numbers.  Refused before any
+ * launch, the engine staying usable: guidance_scale == 0 and guidance_rescale > 0 with a sigma != 0 (the rescale needs the unfolded text
+ * prediction; rt_plain_step_part takes no guidance scale, so in the split plain step it refuses the rescale and guidance_scale == 0 is
+ * refused by rt_plain_step_finish, ahead of its own launches), and a forward whose applied module has a token count that is no multiple of 8 (RT_E_UNSUPPORTED).
+ * All sigma 0: no twin exists, no new kernel is launched, every stream keeps its bits; a non-twin stream's bits never depend on whether
+ * twins are present.  Nothing is allocated in a step, the entry lists travel in the kernel arguments, a step stays capturable. */
+int rt_set_pag_layers(rt_engine* e, const char* names);
+int rt_set_pag_scales(rt_engine* e, const float* scales_host, int n_prompts);
 /* region masks (model.masks, rd.py:97,119-128 / xl.py:775,810-821): [R,4,h,w] f32 */
 int rt_set_masks(rt_engine* e, const float* masks, int n_regions, int h, int w);
 /* font-size control (text_format_dict['word_pos'|'font_size'], richtext_utils.py:188-209): HOST arrays; n = 0 disables.
@@ -263,6 +292,9 @@ int rt_plain_step(rt_engine* e, int step_index, float guidance_scale);
  * (CFG + scheduler step).  Bit-identical with rt_plain_step on one GPU. */
 int rt_plain_step_part(rt_engine* e, int step_index, int part, int nparts, int* first_stream, int* n_streams);
 int rt_plain_step_finish(rt_engine* e, int step_index, float guidance_scale);
+/* host-only: the streams of a plain step as the state stands - 2, or 3 with a perturbed twin of the text stream (rt_set_pag_scales), which
+ * rides with the text stream's part: ranges (0, 1), (1, n - 1), (n, 0) ... */
+int rt_plain_streams(rt_engine* e, int* n_streams);
 
 /* token-map attention store (hooks rd.py:397-443, xl.py:959-1016): head-averaged softmax(QK^T) of the
  * CONDITIONAL stream of rt_plain_step, recorded for the named attention modules (reference module names such as
@@ -289,7 +321,9 @@ enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_
        RT_PROF_CONTROL_ADD = 8 /* the ControlNet residual add (control.hip; rt_set_control_scales), priced in bytes: the fp32 residual read once, the
                                 * fp16 skip read and written once, for the controlled streams */,
        RT_PROF_LORA = 9 /* the regional LoRA term of one projection (lora.hip; rt_set_lora_scales), for the adapted streams of the launch:
-                         * FLOPs = 2 * rows * R * (K + N), bytes = X read once + Y read and written once */ };
+                         * FLOPs = 2 * rows * R * (K + N), bytes = X read once + Y read and written once */,
+       RT_PROF_PAG = 10 /* perturbed-attention guidance (pag.hip; rt_set_pag_scales), priced in bytes: the identity attention of the twins at an
+                         * applied module (V^T read, O written once) and the fold of a step (partner read and written, twin read) */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
 int rt_profile_read(rt_engine* e, int kernel_class, int* count, double* total_ms, double* total_flops);
 /* as rt_profile_read, plus the ALGORITHMIC HBM bytes of the launches (attention store: the fp32 accumulator read + written once and the
@@ -317,6 +351,11 @@ int rt_unet_forward(rt_engine* e, const float* x, int B, int h, int w, float tim
 int rt_unet_forward_trace(rt_engine* e, const float* x, int B, int h, int w, float timestep, const float* in_scale_host,
                           const int* prompt_idx_host, const int* fontsize_host, const int* qk_src_host, const int* res_src_host,
                           float* out, const char* module_name, float* trace_out_dev, long long trace_cap_floats);
+/* rt_unet_forward_trace's arguments plus perturb_host: per stream 1 = the stream is perturbed at the applied modules of rt_set_pag_layers
+ * (its attention output there is its V); the perturbed streams trail the list.  module_name == NULL: no trace.  perturb_host == NULL: none. */
+int rt_unet_forward_perturbed(rt_engine* e, const float* x, int B, int h, int w, float timestep, const float* in_scale_host,
+                              const int* prompt_idx_host, const int* fontsize_host, const int* qk_src_host, const int* res_src_host,
+                              float* out, const char* module_name, float* trace_out_dev, long long trace_cap_floats, const int* perturb_host);
 int rt_trace_module_count(rt_engine* e);
 int rt_trace_module_info(rt_engine* e, int idx, char* name, int name_cap, int* channels, int* downshift);
 
@@ -366,6 +405,14 @@ int rt_op_ip_attention(const void* Q, int ldq, const void* Kip, int ldk, const v
  * element whose term is exactly 0 (rows of `up` that are zero: head padding) keeps its bits.  Each row is a function of itself alone:
  * deterministic and batch invariant.  The packed weights carry whatever the base projection's pack carries (head padding, to_q's
  * d^-1/2 log2 e): the kernel knows nothing of heads. */
+/* The identity attention of perturbed-attention guidance alone (csrc/pag.hip), in rt_op_attention's layouts: O[b N + n, c] = VT[c, b N + n]
+ * for c < H DP and the n batch entries entry_host names (each once, < B); VT [H DP, ldvt] bf16 (row h DP + d, column = token; the pad rows
+ * d .. DP are copied like the rest), O [B N, ldo] bf16 (head h at column h DP).  N % 8 == 0, DP as rt_op_ip_attention accepts, leading
+ * dimensions multiples of 8, 16-byte aligned pointers.  Entries that are not named keep their bytes.  Bit-exact: a transpose. */
+int rt_op_identity_attention(const void* VT, int ldvt, void* O, int ldo, const int* entry_host, int n, int B, int H, int N, int DP, void* stream);
+/* The fold of a step alone: eps [n_streams][h w][4] fp32 (rt_eps_info's layout); pair i: eps[stream_host[i]] <- fmaf(ratio_host[i],
+ * eps[stream_host[i]] - eps[twin_host[i]], eps[stream_host[i]]).  A stream is named once; a twin's slot is read only. */
+int rt_op_pag_fold(float* eps, int n_streams, int h, int w, const int* stream_host, const int* twin_host, const float* ratio_host, int n, void* stream);
 int rt_op_lora_add(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank,
                    const int* col_adapter, void* Y, int ldy, int form, const int* row_host, const float* scale_host, int B, int rows, int K,
                    int N, int R, int* launched, void* stream);

@@ -369,6 +369,10 @@ void launch_freeu(f16_t* hidden, int C1, f16_t* skip, int C2, int B, int H, int 
 // control.hip (ControlNet): the residual add of a step, the hint embedder's fp32 convolution and the hint's layout change
 void launch_control_add(f16_t* skip, size_t skip_stride, int lds, const float* r, size_t r_stride, int ldr, const int* /*host*/ stream,
                         const float* /*host*/ scale, int n, int B, int HW, int C, hipStream_t st);
+// pag.hip (perturbed-attention guidance): O[b N + n, c] = VT[c, b N + n] for the n named batch entries (a bf16 transpose in rt_op_attention's
+// layouts; N % 8 == 0, leading dimensions multiples of 8), and the fold of a step: eps[s[i]] <- fmaf(rho[i], eps[s[i]] - eps[twin[i]], eps[s[i]])
+void launch_identity_attention(const bf16_t* VT, int ldvt, bf16_t* O, int ldo, const int* /*host*/ entry, int n, int B, int H, int N, int DP, hipStream_t st);
+void launch_pag_fold(float* eps, int F, int HW, const int* /*host*/ s, const int* /*host*/ twin, const float* /*host*/ rho, int n, hipStream_t st);
 void launch_control_conv3(const float* in, const float* w, const float* bias, float* out, f16_t* out16, int Hin, int Win, int CinP, int Cout,
                           int stride, int silu, hipStream_t st);      // fp32 3x3 convolution (pad 1) of one NHWC image, optional SiLU, optional fp16 copy
 void launch_control_hint(const float* hint, float* out, int Ch, int CP, size_t HW, hipStream_t st);            // [Ch, HW] f32 -> [HW, CP] f32, pad channels zero

@@ -100,6 +100,7 @@ struct TBlockP {
     int store_calls[2] = {0, 0};
     int store_rows[2] = {0, 0}, store_cols[2] = {0, 0};
     size_t store_cap[2] = {0, 0};
+    bool pag = false;                      // attn1 of this block is an applied module of rt_set_pag_layers
 };
 struct TransformerP {
     std::string name;
@@ -177,6 +178,8 @@ struct FwdIn {
     float* eps_out = nullptr;    // [B, HW, 4] fp32
     int store_stream = -1;       // stream whose head-averaged attention maps are recorded (plain pass: the conditional one)
     bool control = false;        // the forward of the ControlNet's encoder copy (control_pass): no image-prompt term, no adapters
+    int perturb[RT_MAXB] = {};   // perturbed-attention guidance: 1 = a twin, whose attention output at the applied attn1 modules (rt_set_pag_layers)
+                                 // is its V (pag.hip); the twins trail the list.  Never set on the control copy.
 };
 
 extern int g_store_own_stats;
@@ -450,6 +453,12 @@ struct rt_engine {
     // rt_set_freeu: (s1, s2, b1, b2) of the first two up blocks; all 1 = off, under which a forward launches nothing new.  Survives everything but rt_set_freeu.
     float fu_s[2] = {1.f, 1.f}, fu_b[2] = {1.f, 1.f};
     bool freeu_on() const { return fu_s[0] != 1.f || fu_s[1] != 1.f || fu_b[0] != 1.f || fu_b[1] != 1.f; }
+    // Perturbed-attention guidance (rt_set_pag_layers / rt_set_pag_scales; pag.hip): sigma per prompt slot (all 0 = off: no twin stream, no
+    // new launch) and the number of applied attn1 modules (their blocks carry TBlockP::pag).  The scales are reset by rt_set_prompts, the
+    // layers survive everything but rt_set_pag_layers.  No weight, no persistent buffer.
+    std::vector<float> pag_scale;
+    int pag_layers = 0;
+    bool pag_on() const { for (float v : pag_scale) if (v != 0.f) return true; return false; }
     unsigned long long noise_seed = 0;              // stochastic samplers: key of the per-step noise field (rt_set_noise_seed); survives rt_set_schedule / rt_set_latents
 
     // optional per-launch HIP-event profiling of the MFMA kernels (bench.py roofline leg)
@@ -1053,8 +1062,12 @@ struct rt_engine {
         const int B = c.B, HW = c.HW, M = c.M, C = c.C, HD = c.HD;
         // Q,K are only needed for streams that some stream attends with (injected region streams use the
         // text_ref stream's Q,K: attention_processor.py:522-524 discards their own scores)
-        int nqk = 0;
-        for (int b = 0; b < B; ++b) nqk = std::max(nqk, in.qk_src[b] + 1);
+        // Perturbed-attention guidance: at an applied module the trailing twins do not attend - their attention output is their V (below) -,
+        // so the launch covers the leading natt entries and a twin's Q / K rows are projected only where an attending stream reads them
+        int natt = B;
+        if (k.pag) { natt = 0; while (natt < B && !in.perturb[natt]) ++natt; }
+        int nqk = natt ? 0 : 1;                 // (a launch of twins alone keeps one stream's rows: the projection pair has no V-only form)
+        for (int b = 0; b < natt; ++b) nqk = std::max(nqk, in.qk_src[b] + 1);
         if (ln.fold[0]) {
             const LnFold lq = ln.reads(k.qk1s), lv = ln.reads(k.v1s);
             gemm_qk_vt(ln.xb, C, k.qk1f, nqk * HW, c.qk, 2 * HD, k.v1f, M, c.vt, M, &lq, &lv);
@@ -1073,11 +1086,20 @@ struct rt_engine {
             // so the store runs its apply kernel only (debug bit 17: the store computes them itself, round 4's two launches)
             const bool will_store = in.store_stream >= 0 && k.store_mode[0] && k.store_calls[0] + 1 > 10;      // n_maps[name] > 10 (rd.py:422, xl.py:988)
             const bool stats_from_attn = will_store && store_handover_self(HW, t.DP, in.qk_src, in.store_stream);
-            const AttnArgs a = unet_self_attn_args(AttnIO{c.qk, 2 * HD, c.qk + HD, 2 * HD, c.vt, M, c.o, HD}, in.qk_src, B, t.heads, HW, t.DP,
+            const AttnArgs a = unet_self_attn_args(AttnIO{c.qk, 2 * HD, c.qk + HD, 2 * HD, c.vt, M, c.o, HD}, in.qk_src, natt, t.heads, HW, t.DP,
                                                    stats_from_attn ? c.store_stats : nullptr, in.store_stream);
-            prof_begin(RT_PROF_ATTN_SELF, 4.0 * B * t.heads * (double)HW * HW * t.d);
-            launch_attention(a, stream);
-            prof_end();
+            if (natt) {
+                prof_begin(RT_PROF_ATTN_SELF, 4.0 * natt * t.heads * (double)HW * HW * t.d);
+                launch_attention(a, stream);
+                prof_end();
+            }
+            if (natt < B) {                     // the twins' rows of o: O = V, head for head (pag.hip)
+                int twins[RT_MAXB];
+                for (int b = natt; b < B; ++b) twins[b - natt] = b;
+                prof_begin(RT_PROF_PAG, 0.0, 2.0 * 2.0 * (B - natt) * (double)HW * HD);      // priced in bytes: V^T read once, O written once
+                launch_identity_attention(c.vt, M, c.o, HD, twins, B - natt, B, t.heads, HW, t.DP, stream);
+                prof_end();
+            }
             if (in.store_stream >= 0 && k.store_mode[0] && ++k.store_calls[0] > 10) {
                 RT_REQUIRE((size_t)HW * HW <= k.store_cap[0], "attention store: map larger than the enabled buffer");
                 prof_begin(RT_PROF_ATTN_STORE, 2.0 * 2.0 * t.heads * (double)HW * HW * t.d, 8.0 * HW * HW + 2.0 * 2.0 * HW * HD);
@@ -1360,6 +1382,26 @@ struct rt_engine {
         if (tracing()) trace_main("mid", xmid, ch * cw);
     }
 
+    // Perturbed-attention guidance: what a forward with twins needs, refused before anything is launched - the twins trail the list, the
+    // recorded stream is none of them, and every applied module's grid holds a multiple of 8 tokens (the identity kernel's 16-byte accesses)
+    void pag_check(const FwdIn& in) {
+        bool any = false;
+        for (int b = 0; b < in.B; ++b) {
+            if (in.perturb[b]) any = true;
+            else RT_REQUIRE(!any, "forward: the perturbed streams must trail the stream list");
+        }
+        if (!any) return;
+        RT_REQUIRE(!in.control, "forward: the ControlNet copy is never perturbed");
+        RT_REQUIRE(in.store_stream < 0 || !in.perturb[in.store_stream], "forward: the token-map store never records a perturbed stream");
+        if (pag_layers == 0) throw rt_error(RT_E_INVALID, "forward: a perturbed stream but no applied layer (rt_set_pag_layers: the applied set is empty)");
+        for_each_tblock([&](TransformerP& t, TBlockP& k) {
+            if (!k.pag) return;
+            const int tokens = (in.h >> t.level) * (in.w >> t.level);
+            if (tokens % 8 != 0)
+                throw rt_error(RT_E_UNSUPPORTED, "forward: perturbed attention at " + k.mod_name[0] + " needs a multiple of 8 tokens, the grid has " + std::to_string(tokens));
+        });
+    }
+
     // UNet2DConditionModel.forward (models/unet_2d_condition.py:703-983), batched over streams
     void unet_forward(const FwdIn& in) {
         const int B = in.B, Hh = in.h, Ww = in.w, HW0 = Hh * Ww;
@@ -1369,6 +1411,7 @@ struct rt_engine {
         // FreeU (rt_set_freeu): the skip filter scales the bins {-1, 0} of both axes, which a side of 1 does not have - refused before any launch
         if (!dry() && freeu_on() && ((Hh >> (cfg.n_levels - 1)) < 2 || (Ww >> (cfg.n_levels - 1)) < 2))
             throw rt_error(RT_E_UNSUPPORTED, "forward: FreeU needs a deepest grid of at least 2 x 2 (latents of " + std::to_string(2 << (cfg.n_levels - 1)) + " or more per side)");
+        if (!dry()) pag_check(in);
         if (cfg.controlnet && !dry()) control_check(in);
         if (!dry()) ensure_fold();       // (normally a no-op: rt_set_prompts derived the folded projections already)
         const size_t m0 = ws.mark();
@@ -1470,6 +1513,7 @@ struct rt_engine {
         std::fill(ip_scale.begin(), ip_scale.end(), 0.f);              // the slots change meaning: no prompt has an image until rt_set_image_prompts
         std::fill(ctl.scale.begin(), ctl.scale.end(), 0.f);            // ... and none is controlled until rt_set_control_scales (the hint stays)
         std::fill(lora_scale.begin(), lora_scale.end(), 0.f);          // ... and none is adapted until rt_set_lora_scales (the caches above carry no term)
+        std::fill(pag_scale.begin(), pag_scale.end(), 0.f);            // ... and none has a perturbed twin until rt_set_pag_scales (the applied layers stay)
         lora_cache_dirty = false;
         HIP_CHECK(hipStreamSynchronize(stream));   // host buffers (time_ids) may go away
     }
@@ -1613,6 +1657,71 @@ struct rt_engine {
         for (int p_ = 0; p_ < cfg.max_prompts; ++p_) ctl.scale[p_] = p_ < P ? scales[p_] : 0.f;
     }
 
+    // Perturbed-attention guidance.  names: ';'-joined attn1 module names as rt_attn_module_info lists them (empty / NULL: none applied).
+    // Everything is checked before the state changes.
+    void set_pag_layers(const char* names) {
+        std::vector<std::string> want;
+        const std::string all = names ? names : "";
+        for (size_t at = 0; at <= all.size();) {
+            const size_t end = std::min(all.find(';', at), all.size());
+            if (end > at) want.push_back(all.substr(at, end - at));
+            at = end + 1;
+        }
+        for (const std::string& w : want) {
+            int found = 0;      // 1: an attn1 module, 2: an attn2 module
+            for_each_tblock([&](TransformerP&, TBlockP& k) { if (k.mod_name[0] == w) found = 1; else if (k.mod_name[1] == w) found = 2; });
+            if (found == 2) throw rt_error(RT_E_INVALID, "set_pag_layers: " + w + " is a cross-attention module; perturbed attention applies to attn1 modules only");
+            if (found == 0) throw rt_error(RT_E_INVALID, "set_pag_layers: unknown attention module " + w);
+        }
+        if (want.empty() && pag_on()) throw rt_error(RT_E_INVALID, "set_pag_layers: an empty applied set while a slot has a non-zero scale (rt_set_pag_scales)");
+        pag_layers = 0;
+        for_each_tblock([&](TransformerP&, TBlockP& k) {
+            k.pag = std::find(want.begin(), want.end(), k.mod_name[0]) != want.end();
+            if (k.pag) ++pag_layers;
+        });
+    }
+    // One finite scale per prompt slot of rt_set_prompts, the calling pattern of rt_set_control_scales: slot 0 is the negative prompt, which
+    // has no twin; the rich pass runs region r on slot r + 1 and the base prompt on the last slot, the plain pass its text on slot 1.
+    void set_pag_scales(const float* scales, int P) {
+        RT_REQUIRE(scales, "set_pag_scales: scales");
+        RT_REQUIRE(P >= 1 && P <= n_prompts, "set_pag_scales: more slots than prompts set (rt_set_prompts first)");
+        bool any = false;
+        for (int p_ = 0; p_ < P; ++p_) {
+            if (!std::isfinite(scales[p_])) throw rt_error(RT_E_INVALID, "set_pag_scales: the scale of slot " + std::to_string(p_) + " is not finite");
+            any |= scales[p_] != 0.f;
+        }
+        if (scales[0] != 0.f) throw rt_error(RT_E_INVALID, "set_pag_scales: slot 0 is the negative prompt, which has no perturbed twin: its scale must be 0");
+        if (any && pag_layers == 0) throw rt_error(RT_E_INVALID, "set_pag_scales: a non-zero scale but the applied set is empty (rt_set_pag_layers first)");
+        for (int p_ = 0; p_ < cfg.max_prompts; ++p_) pag_scale[p_] = p_ < P ? scales[p_] : 0.f;
+    }
+    // Before any launch of a step with PAG on: the two combinations that are out of scope
+    void pag_step_check(float g) const {
+        if (!pag_on()) return;
+        if (g == 0.f) throw rt_error(RT_E_INVALID, "perturbed-attention guidance needs classifier-free guidance: guidance_scale is 0 (the fold divides by it)");
+        if (guidance_rescale > 0.f)
+            throw rt_error(RT_E_INVALID, "perturbed-attention guidance together with guidance_rescale > 0 is not supported (the rescale needs the unfolded text prediction)");
+    }
+    // The twin of stream s, behind all streams planned so far
+    int pag_twin(FwdIn& in, int& F, int s, const char* who) {
+        if (F >= cfg.max_streams)
+            throw rt_error(RT_E_INVALID, std::string(who) + ": perturbed-attention guidance needs more streams (" + std::to_string(F + 1) +
+                                             " or more) than the engine was built for (max_streams " + std::to_string(cfg.max_streams) + ")");
+        in.x[F] = in.x[s]; in.scale[F] = in.scale[s]; in.prompt[F] = in.prompt[s]; in.fontsize[F] = in.fontsize[s];
+        in.qk_src[F] = in.qk_src[s] == s ? F : in.qk_src[s]; in.res_src[F] = in.res_src[s]; in.perturb[F] = 1;
+        return F++;
+    }
+    // The fold of a step (pag.hip), ahead of everything in finish_step: eps[s] <- fmaf(sigma / g, eps[s] - eps[twin], eps[s])
+    struct PagPairs { int n = 0, F = 0; int s[RT_MAXB], twin[RT_MAXB]; float rho[RT_MAXB]; };
+    PagPairs pag_pairs;          // of the step being planned: region_plan / plain_finish set it, finish_step consumes it
+    void pag_fold() {
+        if (!pag_pairs.n) return;
+        const PagPairs& p = pag_pairs;
+        const int F = p.F;
+        prof_begin(RT_PROF_PAG, 0.0, 3.0 * p.n * 16.0 * lat_h * lat_w);      // partner read + written, twin read
+        launch_pag_fold(eps, F, lat_h * lat_w, p.s, p.twin, p.rho, p.n, stream);
+        prof_end();
+    }
+
     void set_fontsize(const int64_t* word_pos, const float* font_size, int n) {
         // set 0: plain softmax; set 1: font-size softmax (attention_processor.py:386-396).  wabs = 0 on padded keys.
         // One table row per key POSITION of the longest prompt the engine holds (KP = 96 rows per chunk, keys first): chunk c of a prompt
@@ -1688,6 +1797,7 @@ struct rt_engine {
     int src_h = 0, src_w = 0;
     void plain_step(int i, float g);
     void plain_forward(int i, int first, int count);
+    int plain_streams();
     void plain_finish(int i, float g);
     void plain_step_part(int i, int part, int nparts, int* first, int* count);
 };
@@ -1718,6 +1828,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
         e->lora_scale.assign((size_t)std::max(1, cfg->max_prompts) * 4, 0.f);
+        e->pag_scale.assign((size_t)std::max(1, cfg->max_prompts), 0.f);
         e->ip_count.assign((size_t)std::max(1, cfg->max_prompts), 0); e->ip_scale.assign((size_t)std::max(1, cfg->max_prompts), 0.f);
         if (e->cfg.max_keys == 0) e->cfg.max_keys = 77;
         e->prompt_keys.assign((size_t)std::max(1, e->cfg.max_prompts), 77);
@@ -1883,6 +1994,8 @@ int rt_set_image_prompts(rt_engine* e, const float* tokens, const int* counts, c
 }
 int rt_set_control_hint(rt_engine* e, const float* hint, int h, int w) { RT_TRY(e, { need_device(e); e->set_control_hint(hint, h, w); }) }
 int rt_set_control_scales(rt_engine* e, const float* scales, int P) { RT_TRY(e, { need_device(e); e->set_control_scales(scales, P); }) }
+int rt_set_pag_layers(rt_engine* e, const char* names) { RT_TRY(e, { e->set_pag_layers(names); }) }
+int rt_set_pag_scales(rt_engine* e, const float* scales, int P) { RT_TRY(e, { need_device(e); e->set_pag_scales(scales, P); }) }
 int rt_attn_cache_info(rt_engine* e, int idx, void** kcache, void** vtcache, long long* bytes_each) {
     RT_TRY(e, {
         need_device(e);
@@ -2033,11 +2146,13 @@ int rt_plain_step(rt_engine* e, int i, float g) { RT_TRY(e, { need_device(e); e-
 int rt_plain_step_part(rt_engine* e, int i, int part, int nparts, int* first, int* count) {
     RT_TRY(e, { need_device(e); RT_REQUIRE(first && count, "rt_plain_step_part: null outputs"); e->plain_step_part(i, part, nparts, first, count); })
 }
+int rt_plain_streams(rt_engine* e, int* n_streams) { RT_TRY(e, { RT_REQUIRE(n_streams, "rt_plain_streams: null argument"); *n_streams = e->plain_streams(); }) }
 int rt_plain_step_finish(rt_engine* e, int i, float g) { RT_TRY(e, { need_device(e); e->plain_finish(i, g); }) }
 
 // rt_unet_forward and rt_unet_forward_trace: one body.  module == nullptr: no trace.  The request is validated before anything is launched.
 static void unet_forward_entry(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt, const int* fontsize,
-                               const int* qk_src, const int* res_src, float* out, const char* module, float* trace_out, long long trace_cap) {
+                               const int* qk_src, const int* res_src, float* out, const char* module, float* trace_out, long long trace_cap,
+                               const int* perturb = nullptr) {
     {
         need_device(e); e->require_bound();
         RT_REQUIRE(B >= 1 && B <= e->cfg.max_streams, "rt_unet_forward: batch");
@@ -2065,6 +2180,7 @@ static void unet_forward_entry(rt_engine* e, const float* x, int B, int h, int w
             in.x[b] = x + (size_t)b * 4 * h * w; in.scale[b] = in_scale ? in_scale[b] : 1.f;
             in.prompt[b] = prompt ? prompt[b] : 0; in.fontsize[b] = fontsize ? fontsize[b] : 0;
             in.qk_src[b] = qk_src ? qk_src[b] : b; in.res_src[b] = res_src ? res_src[b] : -1;
+            in.perturb[b] = perturb && perturb[b] ? 1 : 0;
             RT_REQUIRE(in.prompt[b] >= 0 && in.prompt[b] < e->n_prompts, "rt_unet_forward: prompt index");
             RT_REQUIRE(in.qk_src[b] >= 0 && in.qk_src[b] < B && in.res_src[b] < B, "rt_unet_forward: source stream index");
         }
@@ -2083,6 +2199,11 @@ int rt_unet_forward_trace(rt_engine* e, const float* x, int B, int h, int w, flo
         RT_REQUIRE(module_name, "rt_unet_forward_trace: module_name is NULL");
         unet_forward_entry(e, x, B, h, w, t, in_scale, prompt, fontsize, qk_src, res_src, out, module_name, trace_out_dev, trace_cap_floats);
     })
+}
+int rt_unet_forward_perturbed(rt_engine* e, const float* x, int B, int h, int w, float t, const float* in_scale, const int* prompt, const int* fontsize,
+                              const int* qk_src, const int* res_src, float* out, const char* module_name, float* trace_out_dev, long long trace_cap_floats,
+                              const int* perturb_host) {
+    RT_TRY(e, { unet_forward_entry(e, x, B, h, w, t, in_scale, prompt, fontsize, qk_src, res_src, out, module_name, trace_out_dev, trace_cap_floats, perturb_host); })
 }
 int rt_trace_module_count(rt_engine* e) { return (int)e->trace_mods.size(); }
 int rt_trace_module_info(rt_engine* e, int idx, char* name, int cap, int* channels, int* downshift) {
@@ -2698,6 +2819,15 @@ int rt_op_freeu(void* hidden_f16, int C1, void* skip_f16, int C2, int B, int H, 
     OP_TRY({
         RT_REQUIRE(std::isfinite(b) && b > 0.f && std::isfinite(s) && s > 0.f, "rt_op_freeu: b and s must be finite and > 0");
         launch_freeu((f16_t*)hidden_f16, C1, (f16_t*)skip_f16, C2, B, H, W, b, s, (hipStream_t)stream);
+    })
+}
+int rt_op_identity_attention(const void* VT, int ldvt, void* O, int ldo, const int* entry_host, int n, int B, int H, int N, int DP, void* stream) {
+    OP_TRY({ launch_identity_attention((const bf16_t*)VT, ldvt, (bf16_t*)O, ldo, entry_host, n, B, H, N, DP, (hipStream_t)stream); })
+}
+int rt_op_pag_fold(float* eps, int n_streams, int h, int w, const int* stream_host, const int* twin_host, const float* ratio_host, int n, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(h >= 1 && w >= 1, "rt_op_pag_fold: grid");
+        launch_pag_fold(eps, n_streams, h * w, stream_host, twin_host, ratio_host, n, (hipStream_t)stream);
     })
 }
 int rt_op_control_add(void* skip_f16, long long skip_stride, int lds, const float* r, long long r_stride, int ldr, const int* stream_host,

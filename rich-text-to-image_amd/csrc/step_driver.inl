@@ -117,6 +117,7 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
     RT_REQUIRE(mask_hw == lat_h * lat_w && lat_h > 0, "region_step: masks/latents shape mismatch");
     RT_REQUIRE(rt_sched_is_dpm(sched_kind) || rt_sched_is_euler(sched_kind) == xl,
                "region_step: SD uses PNDM or DPM-Solver++, SDXL uses Euler or DPM-Solver++");
+    pag_step_check(g);
     const float t = timesteps[i];
     const bool use_ref = isa > 0 || ibg > 0;
     // `t > (1-inject_selfattn)*1000`: torch compares a float32 / int64 tensor element with a Python float in float32
@@ -155,7 +156,21 @@ void rt_engine::region_plan(int i, float g, double isa, double ibg, bool xl, boo
         if (feat && run_ref) { in.qk_src[s] = a.s_tref; in.res_src[s] = a.s_tref; }
         a.s_region[r] = s;
     }
-    in.B = F;
+    // Perturbed-attention guidance: the twins behind all existing streams - of base, of text_ref while the pair is stepped (the plain pass's
+    // treatment, with the base slot's sigma), of the region streams whose slot has sigma != 0 - and the pairs of the step's fold
+    pag_pairs = PagPairs{};
+    if (pag_on()) {
+        auto pair = [&](int s, float sigma) {
+            PagPairs& p = pag_pairs;
+            p.s[p.n] = s; p.twin[p.n] = pag_twin(in, F, s, "region_step"); p.rho[p.n] = sigma / g; ++p.n;
+        };
+        if (pag_scale[R] != 0.f) {
+            pair(a.s_base, pag_scale[R]);
+            if (step_ref) pair(a.s_tref, pag_scale[R]);
+        }
+        for (int r = 0; r < R - 1; ++r) if (pag_scale[r + 1] != 0.f) pair(a.s_region[r], pag_scale[r + 1]);
+    }
+    in.B = F; pag_pairs.F = F;
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = R; a.g = g; a.plain = 0;
     a.noise_pred = noise_pred;
     a.step_ref = step_ref ? 1 : 0; a.blend = (blend && !defer_blend) ? 1 : 0;
@@ -193,6 +208,7 @@ void rt_engine::guided_prepass(int i, StepArgs& a) {
 
 // The epilogue of step i on the planned arguments: the guided pre-pass when the prediction needs it, then the solver of sched_kind
 void rt_engine::finish_step(int i, StepArgs& a) {
+    pag_fold();      // perturbed-attention guidance: after it the two-term guidance below is the three-term one
     if (prediction_type != RT_PRED_EPSILON || guidance_rescale > 0.f) guided_prepass(i, a);
     SolverArgs d{};
     solver_coeffs(this, i, d);
@@ -249,7 +265,7 @@ void rt_engine::region_step_part(int i, float g, double isa, double ibg, bool xl
     sub.eps_out = eps + (size_t)*first * lat_h * lat_w * 4;          // the range is contiguous: its predictions land in their own slots
     for (int b = 0; b < *count; ++b) {
         const int s = *first + b;
-        sub.x[b] = in.x[s]; sub.scale[b] = in.scale[s]; sub.prompt[b] = in.prompt[s]; sub.fontsize[b] = in.fontsize[s];
+        sub.x[b] = in.x[s]; sub.scale[b] = in.scale[s]; sub.prompt[b] = in.prompt[s]; sub.fontsize[b] = in.fontsize[s]; sub.perturb[b] = in.perturb[s];
         RT_REQUIRE(in.qk_src[s] >= *first && in.qk_src[s] < *first + *count, "split: a stream's Q / K source lies outside its part");
         sub.qk_src[b] = in.qk_src[s] - *first;
         sub.res_src[b] = in.res_src[s] < 0 ? -1 : in.res_src[s] - *first;
@@ -265,38 +281,60 @@ void rt_engine::region_step_finish(int i, float g, double isa, double ibg, bool 
 
 // The plain-text step (rd.py:200-214 / xl.py:880-905) in the same three pieces as the rich-text step: the forwards of a contiguous range of
 // its two streams [uncond, text], and the epilogue on both.  `first < 0`: both streams (the one-GPU step).
+// Perturbed-attention guidance (the text slot's sigma != 0) appends the twin of the text stream: [uncond, text, twin].
+int rt_engine::plain_streams() {
+    if (!pag_on()) return 2;
+    RT_REQUIRE(n_prompts >= 2, "plain_step: need [negative, text] prompts");
+    if (pag_scale[1] == 0.f) return 2;
+    if (cfg.max_streams < 3)
+        throw rt_error(RT_E_INVALID, "plain_step: perturbed-attention guidance needs more streams (3) than the engine was built for (max_streams " +
+                                         std::to_string(cfg.max_streams) + ")");
+    return 3;
+}
 void rt_engine::plain_forward(int i, int first, int count) {
     require_bound();
     const int n = (int)timesteps.size();
     RT_REQUIRE(i >= 0 && i < n, "plain_step: step index out of range");
     RT_REQUIRE(n_prompts >= 2, "plain_step: need [negative, text] prompts");
-    RT_REQUIRE(first >= 0 && count >= 1 && first + count <= 2, "plain_step: stream range");
+    RT_REQUIRE(first >= 0 && count >= 1 && first + count <= plain_streams(), "plain_step: stream range");
+    // perturbed-attention guidance: what can be refused without g is refused here, before any launch of the split form too (rt_plain_step_part
+    // has no g: g == 0 is caught by rt_plain_step_finish, ahead of its own launches; rt_plain_step checks both first)
+    pag_step_check(1.f);
     const bool xl = rt_sched_is_euler(sched_kind);
     FwdIn in{}; in.h = lat_h; in.w = lat_w; in.t = timesteps[i]; in.B = count;
     in.eps_out = eps + (size_t)first * lat_h * lat_w * 4;            // a stream's prediction lands in its own slot of the eps buffer
     const float scale = xl ? 1.f / std::sqrt(table[i] * table[i] + 1.f) : 1.f;
-    for (int b = 0; b < count; ++b) { in.x[b] = lat; in.scale[b] = scale; in.prompt[b] = first + b; in.fontsize[b] = 0; in.qk_src[b] = b; in.res_src[b] = -1; }
+    for (int b = 0; b < count; ++b) {
+        const int s = first + b;                                        // stream 2: the twin of the text stream
+        in.x[b] = lat; in.scale[b] = scale; in.prompt[b] = s < 2 ? s : 1; in.fontsize[b] = 0; in.qk_src[b] = b; in.res_src[b] = -1; in.perturb[b] = s == 2;
+    }
     // hooks keep the conditional half: out[1][0][1:2] (rd.py:417,425 / xl.py:980,991) - recorded by the rank that runs the text stream
     if (any_store() && first <= 1 && first + count > 1) in.store_stream = 1 - first;
     unet_forward(in);
 }
 void rt_engine::plain_finish(int i, float g) {
     RT_REQUIRE(i >= 0 && i < (int)timesteps.size(), "plain_step: step index out of range");     // PNDM / Euler index their tables with it
+    pag_step_check(g);
+    pag_pairs = PagPairs{};
+    if (plain_streams() == 3) { pag_pairs.n = 1; pag_pairs.F = 3; pag_pairs.s[0] = 1; pag_pairs.twin[0] = 2; pag_pairs.rho[0] = pag_scale[1] / g; }
     StepArgs a{};
     a.eps = eps; a.masks = masks; a.lat = lat; a.lat_ref = lat_ref; a.HW = lat_h * lat_w; a.R = 0; a.g = g; a.plain = 1;
     a.s_uncond = 0; a.s_base = 1; a.s_uref = a.s_tref = -1; a.step_ref = 0; a.blend = 0;
     finish_step(i, a);
 }
 void rt_engine::plain_step(int i, float g) {
-    plain_forward(i, 0, 2);
+    pag_step_check(g);
+    plain_forward(i, 0, plain_streams());
     plain_finish(i, g);
 }
 // Intra-image split of the plain pass (round 6): part 0 runs the unconditional stream, part 1 the text stream (and records the token maps),
 // further parts run nothing; one exchange of the two noise predictions, then rt_plain_step_finish on every rank.
 void rt_engine::plain_step_part(int i, int part, int nparts, int* first, int* count) {
     RT_REQUIRE(nparts >= 1 && part >= 0 && part < nparts, "plain_step_part: part index");
-    if (nparts == 1) { *first = 0; *count = 2; }
-    else { *first = part < 2 ? part : 2; *count = part < 2 ? 1 : 0; }
+    // (with perturbed-attention guidance the twin rides with the text stream's part)
+    const int F = plain_streams();
+    if (nparts == 1) { *first = 0; *count = F; }
+    else { *first = part < 2 ? part : F; *count = part == 0 ? 1 : part == 1 ? F - 1 : 0; }
     if (*count > 0) plain_forward(i, *first, *count);
     else { require_bound(); RT_REQUIRE(i >= 0 && i < (int)timesteps.size(), "plain_step: step index out of range"); }
 }

@@ -99,6 +99,7 @@ _SYMBOLS = [
     "rt_op_latent_attention",
     "rt_set_control_hint", "rt_control_embedding_read", "rt_set_control_scales", "rt_op_control_add",
     "rt_op_lora_add", "rt_set_lora_columns", "rt_set_lora_scales", "rt_attn_cache_info",
+    "rt_set_pag_layers", "rt_set_pag_scales", "rt_plain_streams", "rt_unet_forward_perturbed", "rt_op_identity_attention", "rt_op_pag_fold",
 ]
 
 
@@ -356,6 +357,25 @@ class Engine:
         sc = [float(v) for v in scales]
         self._chk(self.lib.rt_set_control_scales(self.h, (C.c_float * max(1, len(sc)))(*sc), len(sc)))
 
+    # ---- perturbed-attention guidance (include/rtdiff.h: rt_set_pag_layers / rt_set_pag_scales)
+    def set_pag_layers(self, names):
+        """The applied attn1 modules, full names as attn_modules() lists them (pag.resolve_layers turns specs such as "mid" into names).
+        Survives set_prompts."""
+        self._chk(self.lib.rt_set_pag_layers(self.h, ";".join(names).encode()))
+
+    def set_pag_scales(self, scales):
+        """One finite sigma per prompt slot of the last set_prompts (slot 0, the negative prompt, must be 0); a slot with sigma != 0 gets a
+        perturbed twin stream in every step.  set_prompts resets every sigma to 0."""
+        sc = [float(v) for v in scales]
+        self._chk(self.lib.rt_set_pag_scales(self.h, (C.c_float * max(1, len(sc)))(*sc) if sc else None, len(sc)))
+
+    PROF_PAG = 10           # pag.hip (identity attention of the twins, the fold of a step): priced in algorithmic HBM bytes
+
+    def profile_read_pag(self):
+        n, ms, fl, by = C.c_int(), C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.rt_profile_read2(self.h, self.PROF_PAG, C.byref(n), C.byref(ms), C.byref(fl), C.byref(by)))
+        return dict(launches=n.value, total_ms=ms.value, total_flops=fl.value, total_bytes=by.value)
+
     # ---- regional LoRA (include/rtdiff.h: rt_set_lora_columns / rt_set_lora_scales; engines built with lora_rank > 0)
     def bind_regional_loras(self, adapters):
         """adapters: {name: modules} of regional_lora.parse_adapter, in load order (an empty dict: zero factors everywhere).  Binds the
@@ -607,6 +627,12 @@ class Engine:
         self._chk(self.lib.rt_plain_step_part(self.h, i, part, nparts, C.byref(first), C.byref(count)))
         return first.value, count.value
 
+    def plain_streams(self):
+        """The streams of a plain step as the state stands: 2, or 3 with a perturbed twin of the text stream (set_pag_scales)."""
+        n = C.c_int(0)
+        self._chk(self.lib.rt_plain_streams(self.h, C.byref(n)))
+        return n.value
+
     def plain_step_finish(self, i, guidance_scale):
         self._chk(self.lib.rt_plain_step_finish(self.h, i, C.c_float(guidance_scale)))
 
@@ -622,8 +648,9 @@ class Engine:
             out.append((name.value.decode(), ch.value, sh.value))
         return out
 
-    def unet_forward(self, x, timestep, prompt_idx, in_scale=None, fontsize=None, qk_src=None, res_src=None, trace=None):
-        """trace = a module name of trace_modules(): returns (out, the trunk tensor that module leaves as fp32 [B, C, h', w']) - the same
+    def unet_forward(self, x, timestep, prompt_idx, in_scale=None, fontsize=None, qk_src=None, res_src=None, trace=None, perturb=None):
+        """perturb = per stream 1 / 0: the stream is perturbed at the applied modules of set_pag_layers (rt_unet_forward_perturbed; the
+        perturbed streams trail the list).  trace = a module name of trace_modules(): returns (out, the trunk tensor that module leaves as fp32 [B, C, h', w']) - the same
         forward, `out` bit for bit (rt_unet_forward_trace: test infrastructure)."""
         import torch
         x = x.contiguous().float()
@@ -641,10 +668,20 @@ class Engine:
             tr = torch.empty(B, ch, h >> sh, w >> sh, device=x.device)
             if trace.startswith("controlnet."):      # the control copy's own modules leave the CONTROLLED streams only, the hint embedding one entry: the rest stays NaN
                 tr.fill_(float("nan"))
-            self._chk(self.lib.rt_unet_forward_trace(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
-                                                     iarr(qk_src), iarr(res_src), _ptr(out), trace.encode(), _ptr(tr), C.c_longlong(tr.numel())))
+            if perturb is not None:
+                self._chk(self.lib.rt_unet_forward_perturbed(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
+                                                             iarr(qk_src), iarr(res_src), _ptr(out), trace.encode(), _ptr(tr), C.c_longlong(tr.numel()),
+                                                             iarr(perturb)))
+            else:
+                self._chk(self.lib.rt_unet_forward_trace(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
+                                                         iarr(qk_src), iarr(res_src), _ptr(out), trace.encode(), _ptr(tr), C.c_longlong(tr.numel())))
             self.synchronize()
             return out, tr
+        if perturb is not None:
+            self._chk(self.lib.rt_unet_forward_perturbed(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx), iarr(fontsize),
+                                                         iarr(qk_src), iarr(res_src), _ptr(out), None, None, C.c_longlong(0), iarr(perturb)))
+            self.synchronize()
+            return out
         self._chk(self.lib.rt_unet_forward(self.h, _ptr(x), B, h, w, C.c_float(float(timestep)), sc, iarr(prompt_idx),
                                            iarr(fontsize), iarr(qk_src), iarr(res_src), _ptr(out)))
         self.synchronize()
@@ -689,6 +726,43 @@ def ip_attention(Q, Kip, VTip, O, slots, counts, scales, H, N, DP):
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()
     return O
+
+
+def identity_attention(VT, O, entries, H, N, DP):
+    """The identity attention of perturbed-attention guidance alone (rt_op_identity_attention), on the caller's bf16 2-D tensors (views with
+    a row stride are fine: the stride is the leading dimension): O[b N + n, c] = VT[c, b N + n] for c < H DP and the batch entries named;
+    VT [H DP, >= B N], O [B N, >= H DP].  Returns O."""
+    import torch
+    lib = load_library()
+    for t in (VT, O):
+        assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.device == O.device, "identity_attention: bf16 [rows, ld] tensors on one device"
+    assert VT.shape[0] >= H * DP and O.shape[1] >= H * DP and N >= 1 and O.shape[0] % N == 0 and VT.shape[1] >= O.shape[0], "identity_attention: shapes"
+    n = len(entries)
+    with torch.cuda.device(O.device):
+        rc = lib.rt_op_identity_attention(_ptr(VT), int(VT.stride(0)), _ptr(O), int(O.stride(0)), (C.c_int * max(1, n))(*[int(v) for v in entries]), n,
+                                          int(O.shape[0] // N), int(H), int(N), int(DP), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return O
+
+
+def pag_fold(eps, h, w, streams, twins, ratios):
+    """The fold of a step alone (rt_op_pag_fold), IN PLACE on eps [F, h w, 4] fp32 (contiguous, the engine's eps layout):
+    eps[streams[i]] <- fmaf(ratios[i], eps[streams[i]] - eps[twins[i]], eps[streams[i]]).  Returns eps."""
+    import torch
+    lib = load_library()
+    assert eps.dtype == torch.float32 and eps.is_contiguous() and eps.dim() == 3 and eps.shape[1] == h * w and eps.shape[2] == 4, "pag_fold: fp32 [F, h w, 4]"
+    n = len(streams)
+    assert len(twins) == n and len(ratios) == n
+    with torch.cuda.device(eps.device):
+        rc = lib.rt_op_pag_fold(_ptr(eps), int(eps.shape[0]), int(h), int(w), (C.c_int * max(1, n))(*[int(v) for v in streams]),
+                                (C.c_int * max(1, n))(*[int(v) for v in twins]), (C.c_float * max(1, n))(*[float(v) for v in ratios]), n,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return eps
 
 
 LORA_FORMS = {"bf16": 0, "bf16_t": 1, "f16": 2}

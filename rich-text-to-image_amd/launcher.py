@@ -320,17 +320,27 @@ def plain_capture_rank():
     return 1 if dist.is_initialized() and dist.get_world_size() > 1 else 0
 
 
+def plain_ranges(n_streams, world):
+    """The (first, count) of every rank for a plain step of n_streams streams [uncond, text(, twin of text)] - the rule of
+    csrc/step_driver.inl::plain_step_part: rank 0 the unconditional stream, rank 1 the text stream and, with perturbed-attention guidance,
+    its twin; further ranks none.  One rank runs them all."""
+    if world == 1:
+        return [(0, n_streams)]
+    return [(0, 1) if r == 0 else (1, n_streams - 1) if r == 1 else (n_streams, 0) for r in range(world)]
+
+
 def split_plain_step(engine, i, guidance_scale):
     """ONE plain-text step (rd.py:200-214 / xl.py:880-905) of ONE image on all ranks: rank 0 runs the unconditional forward, rank 1 the
-    text forward (and records the token maps: plain_capture_rank), further ranks none; two broadcasts of one noise prediction each
-    (256 KB at SDXL), then CFG + scheduler step on every rank.  Bit-identical with engine.plain_step on one GPU."""
+    text forward (and records the token maps: plain_capture_rank; with perturbed-attention guidance also the text stream's twin), further
+    ranks none; two broadcasts of one or two noise predictions each (256 KB per prediction at SDXL), then CFG + scheduler step on every rank.  Bit-identical with engine.plain_step on one GPU."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
+    n = engine.plain_streams() if hasattr(engine, "plain_streams") else 2
     if world == 1:
         engine.plain_step(i, guidance_scale)
-        return [(0, 2)]
+        return plain_ranges(n, 1)
     first, count = engine.plain_step_part(i, rank, world)
-    ranges = [(r, 1) if r < 2 else (2, 0) for r in range(world)]     # the rule of csrc/step_driver.inl::plain_step_part
+    ranges = plain_ranges(n, world)
     assert ranges[rank] == (first, count), (ranges[rank], first, count)
     engine.synchronize()
     eps, per = eps_tensor(engine) if not hasattr(engine, "eps_as_tensor") else engine.eps_as_tensor()

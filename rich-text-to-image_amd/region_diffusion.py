@@ -6,13 +6,14 @@ from . import denoise_loop, img2img
 from .engine import SD15_CONFIG
 from .freeu import FreeUMixin
 from .controlnet import ControlNetMixin
+from .pag import PagMixin, twin_count
 from .regional_lora import RegionalLoraMixin
 from .ip_adapter import IPAdapterMixin
 from .schedulers import DPMSolverTables, PNDMTables, engine_prediction
 from .unet import HipUNet2DConditionModel
 
 
-class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraMixin):
+class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraMixin, PagMixin):
     def __init__(self, device=0, unet_state_dict=None, config=None, vae=None, tokenizer=None, text_encoder=None, load_path=None,
                  latent_hw=None, vae_dir=None, vae_encoder=None, scheduler=None, max_prompt_chunks=1, guidance_rescale=0.0,
                  prediction_type=None):
@@ -143,7 +144,8 @@ class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraM
         ip_slots = self.image_prompt_slots(n_prompts, True)               # (a region index beyond the request's regions raises here, before any launch)
         cn_scales = self.control_scales(n_prompts, True)                  # (likewise)
         lora_scales = self.lora_slot_scales(n_prompts, True)              # (likewise)
-        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
+        pag_scales = self.pag_slot_scales(n_prompts, True, guidance_scale, engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale)[1])      # (likewise, and the refused combinations)
+        eng = self.unet.engine(h, w, streams=n_prompts + 2 + twin_count(pag_scales, True), prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
         self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
         keep = None
         if image is not None:
@@ -153,6 +155,7 @@ class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraM
         self.apply_image_prompts(eng, ip_slots, n_prompts)
         self.apply_control(eng, cn_scales, h, w)
         self.apply_lora_scales(eng, lora_scales)
+        self.apply_pag(eng, pag_scales)
         eng.set_masks([m.to(self.device) for m in self.masks])
         tfd = text_format_dict or {}
         eng.set_fontsize(tfd.get("word_pos"), tfd.get("font_size"))
@@ -205,7 +208,8 @@ class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraM
         ip_slots = self.image_prompt_slots(n_prompts, False)
         cn_scales = self.control_scales(n_prompts, False)
         lora_scales = self.lora_slot_scales(n_prompts, False)
-        eng = self.unet.engine(h, w, streams=n_prompts + 2, prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
+        pag_scales = self.pag_slot_scales(n_prompts, False, guidance_scale, engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale)[1])
+        eng = self.unet.engine(h, w, streams=n_prompts + 2 + twin_count(pag_scales, False), prompts=n_prompts, keys=max(key_counts) if key_counts else text_embeddings.shape[1])
         self.scheduler.set_timesteps(num_inference_steps, strength if image is not None else 1.0)
         if image is not None:
             img2img.check_tokenmap_iterations(getattr(self, "_tokenmap_hooks", False), len(self.scheduler.timesteps))
@@ -213,6 +217,7 @@ class RegionDiffusion(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraM
         self.apply_image_prompts(eng, ip_slots, n_prompts)
         self.apply_control(eng, cn_scales, h, w)
         self.apply_lora_scales(eng, lora_scales)
+        self.apply_pag(eng, pag_scales)
         eng.set_schedule(self._schedule_kind(), self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*engine_prediction(self.scheduler, guidance_scale, guidance_rescale, self.guidance_rescale))

@@ -8,6 +8,7 @@ from . import denoise_loop, img2img
 from .engine import SDXL_CONFIG
 from .freeu import FreeUMixin
 from .controlnet import ControlNetMixin
+from .pag import PagMixin, twin_count
 from .regional_lora import RegionalLoraMixin
 from .ip_adapter import IPAdapterMixin
 from .schedulers import DPMSolverTables, EulerAncestralTables, EulerTables, engine_prediction
@@ -20,7 +21,7 @@ class StableDiffusionXLPipelineOutput(dict):
         self.images = images
 
 
-class RegionDiffusionXL(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraMixin):
+class RegionDiffusionXL(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLoraMixin, PagMixin):
     def __init__(self, load_path=None, device=0, unet_state_dict=None, config=None, vae=None, text_encoders=None,
                  vae_scaling_factor=0.13025, tokenizer=None, latent_hw=None, scheduler=None, vae_dir=None, vae_encoder=None,
                  max_prompt_chunks=1, guidance_rescale=0.0, prediction_type=None):
@@ -174,12 +175,14 @@ class RegionDiffusionXL(FreeUMixin, IPAdapterMixin, ControlNetMixin, RegionalLor
         ip_slots = self.image_prompt_slots(embeds.shape[0], run_rich_text)     # (a region index beyond the request's regions raises here, before any launch)
         cn_scales = self.control_scales(embeds.shape[0], run_rich_text)        # (likewise)
         lora_scales = self.lora_slot_scales(embeds.shape[0], run_rich_text)    # (likewise)
-        eng = self.unet.engine(h, w, streams=embeds.shape[0] + 2 if run_rich_text else 2, prompts=embeds.shape[0],
+        pag_scales = self.pag_slot_scales(embeds.shape[0], run_rich_text, guidance_scale, prediction[1])      # (likewise, and the refused combinations)
+        eng = self.unet.engine(h, w, streams=(embeds.shape[0] + 2 if run_rich_text else 2) + twin_count(pag_scales, run_rich_text), prompts=embeds.shape[0],
                                keys=max(key_counts) if key_counts else embeds.shape[1])
         eng.set_prompts(embeds, pooled, add_time_ids, key_counts=key_counts)
         self.apply_image_prompts(eng, ip_slots, embeds.shape[0])
         self.apply_control(eng, cn_scales, h, w)
         self.apply_lora_scales(eng, lora_scales)
+        self.apply_pag(eng, pag_scales)
         eng.set_schedule(self.scheduler.kind, self.scheduler.timesteps.tolist(), self.scheduler.table(), num_inference_steps)
         eng.set_noise_seed(noise_seed)
         eng.set_prediction(*prediction)

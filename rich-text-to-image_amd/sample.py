@@ -47,9 +47,20 @@ def generate(model, param, model_type='SD', run_dir=None, color_guidance_weight=
     scales of THIS request on a pipeline with adapters loaded - set for the call, restored after it; absent / None: the pipeline as it is.
     `param['control']` (optional; set_control's keyword arguments, controlnet.control_from_request / check_control_args' result: image=
     a file, scale=, regions=, negative=, start=, end=): the ControlNet hint and scales of THIS request on a pipeline with a ControlNet
-    loaded - set for the call, restored after it; the hint is resized to the request's height x width; absent / None: the pipeline as it is."""
+    loaded - set for the call, restored after it; the hint is resized to the request's height x width; absent / None: the pipeline as it is.
+    `param['pag']` (optional; set_pag's keyword arguments, pag.pag_from_request / check_pag_args' result: scale=, regions=, base=,
+    layers=): perturbed-attention guidance of THIS request in both passes - set for the call, restored after it; absent / None: the
+    pipeline as it is."""
     args = (model_type, run_dir, color_guidance_weight, inject_selfattn, segment_threshold, num_segments, inject_background, latents,
             init_image, strength, keep_source)
+    pg = param.get('pag')
+    if pg is not None:
+        keep_pg = getattr(model, 'pag', None)
+        model.set_pag(**pg)
+        try:
+            return generate(model, {k: v for k, v in param.items() if k != 'pag'}, *args)
+        finally:
+            model.pag = keep_pg
     rl = param.get('region_loras')
     if rl is not None:
         if not getattr(model, 'regional_loras', None):
@@ -316,6 +327,52 @@ def check_control_args(a):
     return flag
 
 
+def check_pag_args(a):
+    """--pag_scale / --pag_layers and the "pag" keys of a --requests file, checked before any rank starts: every scale and layer spec
+    parses, and the two refused combinations - no classifier-free guidance (--guidance_weight 0), --guidance_rescale > 0 - end the run
+    (SystemExit).  Returns the flags' request (set_pag's keyword arguments) or None."""
+    from .pag import DEFAULT_LAYERS, check_guidance, check_layer_forms, pag_from_request, parse_scale_args
+
+    def checked(kw, who):
+        try:
+            check_layer_forms(kw["layers"])                         # the forms alone: the modules are the UNet's, known once it is loaded
+            on = [kw["scale"]] + list(kw["regions"].values()) + ([] if kw["base"] is None else [kw["base"]])
+            check_guidance(on, getattr(a, "guidance_weight", 1.0), getattr(a, "guidance_rescale", None) or 0.0, who)
+        except ValueError as e:
+            raise SystemExit(f"sample: {e}")
+        return kw
+    flag = None
+    if getattr(a, "pag_scale", None):
+        try:
+            kw = parse_scale_args(a.pag_scale)
+        except ValueError as e:
+            raise SystemExit(f"sample: {e}")
+        kw["layers"] = tuple(getattr(a, "pag_layers", None) or DEFAULT_LAYERS)
+        flag = checked(kw, "--pag_scale")
+    elif getattr(a, "pag_layers", None):
+        raise SystemExit("sample: --pag_layers needs --pag_scale")
+    if getattr(a, "requests", None):
+        with open(a.requests) as f:
+            for n, line in enumerate(f, 1):
+                if line.strip() and json.loads(line).get("pag") is not None:
+                    try:
+                        checked(pag_from_request(json.loads(line)["pag"], f"--requests line {n}: pag"), f"--requests line {n}: pag")
+                    except ValueError as e:
+                        raise SystemExit(f"sample: {e}")
+    return flag
+
+
+def _request_pag(a, r):
+    """A --requests line's "pag" (S | [S, "TARGET:S", ...] | {"scale": ..., "layers": [...]}), else the flags'."""
+    if r.get("pag") is None:
+        return getattr(a, "pag", None)
+    from .pag import pag_from_request
+    try:
+        return pag_from_request(r["pag"], "--requests: pag")
+    except ValueError as e:
+        raise SystemExit(f"sample: {e}")
+
+
 def check_region_lora_args(a):
     """--region_lora and the "region_loras" keys of a --requests file, checked before any rank starts: every file exists, every spec
     parses, at most four adapters in all.  Bad values end the run (SystemExit).  Sets a.region_lora_files = {name: path} of every adapter
@@ -386,7 +443,7 @@ def build_requests(a):
     several --seeds = independent requests (BASELINE configs 4 / 5: "batch of 8 independent rich-text JSON/seeds"): JSONs and seeds
     pair up one to one when both lists have the same length, otherwise every JSON is sampled with every seed.  `--requests FILE`:
     one JSON object per line, {"rich_text_json": {...} | "<path>", "seed": 3, "negative_prompt": "...", "scheduler": "euler-ancestral"}
-    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); "control": {"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b} = the ControlNet hint and scales of that request alone (--controlnet); "region_loras": ["PATH[:TARGET[:SCALE]]", ...] = the regional LoRA scales of that request alone (every PATH is loaded at start-up, at most four in all); a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
+    (missing keys: the flags; "freeu": [s1, s2, b1, b2] = FreeU for that request alone; "image_prompts": ["FILE[:TARGET[:SCALE]]", ...] = the image prompts of that request alone (--ip_adapter); "control": {"image": FILE, "scale": S | [S, "TARGET:S", ...], "start": a, "end": b} = the ControlNet hint and scales of that request alone (--controlnet); "region_loras": ["PATH[:TARGET[:SCALE]]", ...] = the regional LoRA scales of that request alone (every PATH is loaded at start-up, at most four in all); "pag": S | [S, "TARGET:S", ...] | {"scale": ..., "layers": [SPEC, ...]} = perturbed-attention guidance for that request alone; a line's scheduler is one of --scheduler's names other than default and takes --solver_order where that applies)."""
     reqs = []
     if a.requests:
         with open(a.requests) as f:
@@ -400,13 +457,15 @@ def build_requests(a):
                                  negative_prompt=r.get("negative_prompt", a.negative_prompt), scheduler=_request_scheduler(a, r.get("scheduler")),
                                  max_prompt_chunks=check_max_prompt_chunks(int(r.get("max_prompt_chunks", getattr(a, "max_prompt_chunks", 1)))),
                                  freeu=check_freeu_arg(r.get("freeu", getattr(a, "freeu", None)), "--requests: freeu"),
-                                 image_prompts=_request_image_prompts(a, r), control=_request_control(a, r), region_loras=_request_region_loras(a, r)))
+                                 image_prompts=_request_image_prompts(a, r), control=_request_control(a, r), region_loras=_request_region_loras(a, r),
+                                 pag=_request_pag(a, r)))
     jsons = [_load_json_arg(v) for v in (a.rich_text_json or [])]
     seeds = list(a.seeds) if a.seeds else [a.seed]
     if jsons:
         pairs = list(zip(jsons, seeds)) if len(jsons) == len(seeds) else [(j, sd) for j in jsons for sd in seeds]
         reqs += [dict(text_input=j, seed=int(sd), negative_prompt=a.negative_prompt, max_prompt_chunks=getattr(a, "max_prompt_chunks", 1),
-                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None), control=getattr(a, "control", None), region_loras=getattr(a, "region_loras", None)) for j, sd in pairs]
+                      freeu=check_freeu_arg(getattr(a, "freeu", None), "--freeu"), image_prompts=getattr(a, "image_prompts", None), control=getattr(a, "control", None), region_loras=getattr(a, "region_loras", None),
+                      pag=getattr(a, "pag", None)) for j, sd in pairs]
     if not reqs:
         raise SystemExit("sample: no request (pass --rich_text_json JSON [JSON ...] and / or --requests FILE)")
     for i, r in enumerate(reqs):
@@ -605,6 +664,13 @@ def build_parser():
                         'in all; the same file may be named with several targets.  (load_components(lora_path=) merges ONE adapter into the weights instead)')
     p.add_argument('--region_lora_attention_only', action='store_true',
                    help='with --region_lora: drop a checkpoint\'s tensors on other modules (feed-forward, proj_in / proj_out, resnets) instead of refusing it')
+    p.add_argument('--pag_scale', type=str, nargs='+', default=None, metavar='S|TARGET:S',
+                   help='perturbed-attention guidance in both passes: a bare S is the scale of the base prompt and of every rich-text region, '
+                        'TARGET is base or a region number.  A prompt with scale 0 gets no perturbed stream.  Needs classifier-free guidance; '
+                        'not together with --guidance_rescale')
+    p.add_argument('--pag_layers', type=str, nargs='+', default=None, metavar='SPEC',
+                   help='with --pag_scale: the self-attention modules that are perturbed - mid (default), down, up, down_blocks.N, up_blocks.N, '
+                        '...attentions.M or full attn1 module names')
     p.add_argument('--control_start', type=float, default=0.0, help='with --control_image: the fraction of the executed schedule at which control begins (control_guidance_start)')
     p.add_argument('--control_end', type=float, default=1.0, help='... and at which it ends (control_guidance_end)')
     p.add_argument('--prediction_type', type=str, default=None, choices=['epsilon', 'v_prediction'],
@@ -654,6 +720,7 @@ def main(argv=None):
     a.image_prompts = check_ip_args(a)                 # ... and a missing adapter / embedding file or a malformed FILE[:TARGET[:SCALE]]
     a.control = check_control_args(a)                  # ... and a missing ControlNet / hint image or a malformed --control_scale
     a.region_loras = check_region_lora_args(a)         # ... and a missing adapter file or a malformed PATH[:TARGET[:SCALE]]
+    a.pag = check_pag_args(a)                          # ... and a malformed --pag_scale / --pag_layers or one of PAG's two refused combinations
     if a.init_image is None and a.keep_source != 'none':
         raise SystemExit("sample: --keep_source needs --init_image")
     if a.init_image is not None and a.keep_source != 'none' and a.split_image:
@@ -691,7 +758,7 @@ def main(argv=None):
         param = {'text_input': r['text_input'], 'height': a.height or res, 'width': a.width or res, 'guidance_weight': a.guidance_weight,
                  'steps': a.sample_steps, 'noise_index': r['seed'], 'negative_prompt': r['negative_prompt'],
                  'max_prompt_chunks': r.get('max_prompt_chunks', 1), 'guidance_rescale': a.guidance_rescale, 'freeu': r.get('freeu'), 'image_prompts': r.get('image_prompts'),
-                 'control': r.get('control'), 'region_loras': r.get('region_loras')}
+                 'control': r.get('control'), 'region_loras': r.get('region_loras'), 'pag': r.get('pag')}
         plain, rich, t = generate(model, param, 'SD' if a.model == 'SD' else 'SDXL', a.run_dir, a.color_guidance_weight, a.inject_selfattn,
                                   a.segment_threshold, a.num_segments, a.inject_background, init_image=init_image, strength=a.strength,
                                   keep_source=None if a.keep_source == 'none' else a.keep_source)

@@ -6,11 +6,12 @@ import torch
 
 from .engine import Engine
 from .controlnet import ControlNetMixin
+from .pag import PagMixin
 from .ip_adapter import IPAdapterMixin
 from .regional_lora import RegionalLoraMixin, rank_layout
 
 
-class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin):
+class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin, PagMixin):
     """Holds the engine(s) for one set of weights; engines are created lazily per latent size.  With an IP-Adapter installed
     (load_ip_adapter) every engine is built with its image tokens per prompt and carries its to_k_ip / to_v_ip weights; with a ControlNet installed
     (load_controlnet) every engine is built with it and carries its weights under "controlnet.".  With regional LoRA adapters installed
