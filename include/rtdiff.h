@@ -81,6 +81,11 @@ typedef struct rt_config {
                                          * registers lora.<module>.down.weight [R, K], lora.<module>.up.weight [N, R] and
                                          * lora.<module>.alpha_over_rank [R] in the same arena, packed like the base weight they sit beside, and the
                                          * engine keeps the padded bf16 prompt embeddings (max_prompts * 96 * max_keys / 77 rows) for the attn2 caches */
+    int lora_targets;                   /* the modules regional LoRA adapts (lora_rank > 0): 0 = the eight attention projections, the weight table
+                                         * above, bit for bit; 1 = also ff.net.0.proj [8C, C] (its `up` [8C, R] packed in the base weight's GEGLU row
+                                         * order, per 64 rows [32 value | 32 gate]), ff.net.2 [C, 4C] of every transformer block and proj_in /
+                                         * proj_out [C, C] of every Transformer2DModel of the main UNet (linear or 1x1 convolution: the factors are
+                                         * registered 2-D), each with the same three lora.<module>.* slots, packed plainly */
 } rt_config;
 
 typedef struct rt_engine rt_engine;
@@ -161,6 +166,10 @@ int rt_set_control_scales(rt_engine* e, const float* scales_host, int n_prompts)
  *   second rounding of the adapted rows, like the ControlNet add).  attn2 to_k / to_v cost nothing in a step: rt_set_lora_scales rebuilds
  *   the K / V^T caches of the main UNet with the GEMMs of rt_set_prompts (same bits) and adds the term to the 96-row blocks of the slots
  *   with a non-zero scale; all scales back to 0 leaves the bits rt_set_prompts left.
+ * With rt_config.lora_targets = 1 the term is added in place behind proj_in, ff.net.2 (both into the fp16 trunk) and proj_out as well, and
+ *   ff.net.0.proj of an adapted stream runs unfused and once: LayerNorm 3 of its rows, the plain weight into fp32 scratch (one stream's
+ *   pre-activations at a time, planned by the dry forward), then rt_op_lora_geglu's kernel into the stream's rows of the GEGLU output; the
+ *   other streams of that forward keep the fused GEGLU launch, over the maximal runs of un-adapted streams, and its bits.
  * A stream whose slot has all-zero scales is in no new launch and keeps its bits; an adapted stream's bits do not depend on its
  * neighbours; with every scale 0 no new kernel is launched.  The ControlNet copy runs without adapters.  Nothing is allocated in a step,
  * which stays capturable. */
@@ -321,7 +330,8 @@ enum { RT_PROF_GEMM_DENSE = 0, RT_PROF_GEMM_CONV = 1, RT_PROF_ATTN_SELF = 2, RT_
        RT_PROF_CONTROL_ADD = 8 /* the ControlNet residual add (control.hip; rt_set_control_scales), priced in bytes: the fp32 residual read once, the
                                 * fp16 skip read and written once, for the controlled streams */,
        RT_PROF_LORA = 9 /* the regional LoRA term of one projection (lora.hip; rt_set_lora_scales), for the adapted streams of the launch:
-                         * FLOPs = 2 * rows * R * (K + N), bytes = X read once + Y read and written once */,
+                         * FLOPs = 2 * rows * R * (K + N), bytes = X read once + Y read and written once (ff.net.0.proj's kernel: X and the
+                         * fp32 pre-activations read once, the GEGLU output written once) */,
        RT_PROF_PAG = 10 /* perturbed-attention guidance (pag.hip; rt_set_pag_scales), priced in bytes: the identity attention of the twins at an
                          * applied module (V^T read, O written once) and the fold of a step (partner read and written, twin read) */ };
 int rt_profile_enable(rt_engine* e, int on);     /* on: start recording (clears old records); off: stop */
@@ -416,6 +426,17 @@ int rt_op_pag_fold(float* eps, int n_streams, int h, int w, const int* stream_ho
 int rt_op_lora_add(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank,
                    const int* col_adapter, void* Y, int ldy, int form, const int* row_host, const float* scale_host, int B, int rows, int K,
                    int N, int R, int* launched, void* stream);
+/* ff.net.0.proj of adapted streams from the base projection's fp32 pre-activations (csrc/lora.hip, lora_geglu_kernel), in rt_op_lora_add's
+ * argument style.  Z [*, ldz] fp32: row (row_b + m) holds the N = 8C pre-activations (bias in) in the packed column order of the GEGLU
+ * GEMM, per 64 columns [32 value | 32 gate]; `up` [N, ldu] has its rows in the same order.  With T, Ts as in rt_op_lora_add and D = Ts up^T:
+ *   out[row_b + m, 32 blk + c] = bf16( (Z[.., 64 blk + c] + D[.., 64 blk + c]) * gelu(Z[.., 64 blk + 32 + c] + D[.., 64 blk + 32 + c]) )
+ * ONE rounding; gelu = the polynomial erf form of the fused GEGLU epilogue.  out [*, ldo] bf16, N / 2 columns.  rows % 8 == 0, K % 8 == 0,
+ * N % 64 == 0, R % 16 == 0 in 16 .. 128, ldx / ldd / ldu / ldo % 8 == 0, ldz % 4 == 0, 16-byte aligned pointers, B <= 16; a refusal returns an
+ * error and launches nothing.  An entry whose four scales are all 0 is not in the grid and its rows of out are not written; with no
+ * entry left nothing is launched.  Each row is a function of itself alone: deterministic and batch invariant. */
+int rt_op_lora_geglu(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank,
+                     const int* col_adapter, const float* Z, int ldz, void* out, int ldo, const int* row_host, const float* scale_host, int B,
+                     int rows, int K, int N, int R, int* launched, void* stream);
 /* Host-only (no GPU): the partition of a self-attention launch into shared-probability units (round 6; csrc/attention.hip).  Streams that
  * attend with the same (q_src, k_src) - text_ref and the region streams that take its probabilities, attention_processor.py:522-524 - are dealt
  * G at a time into units that compute softmax(QK^T) once; mode 0 = the shape rule (tokens >= 2048: units of four in their own launch, else

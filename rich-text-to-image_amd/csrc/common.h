@@ -309,6 +309,10 @@ void launch_ip_attention(const bf16_t* Q, int ldq, const bf16_t* Kip, int ldk, c
 // 2 fp16 row-major); row / scale [B][4] are host arrays; a stream whose scales are all 0 is not launched; returns the streams in the grid
 int launch_lora_add(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const bf16_t* up, int ldu, const float* aor, const int* adapter, void* Y,
                     int ldy, int form, const int* row, const float* scale, int B, int rows, int K, int N, int R, hipStream_t st);
+// ... and ff.net.0.proj of the adapted streams from the base GEMM's fp32 pre-activations Z [*, ldz] (bias in; N packed columns, per 64-block
+// [32 value | 32 gate], `up` [N, ldu] in the same row order): out[*, ldo] (N / 2 columns) = bf16((Zv + Dv) gelu(Zg + Dg)), D = bf16(f_b (X down^T)) up^T
+int launch_lora_geglu(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const bf16_t* up, int ldu, const float* aor, const int* adapter, const float* Z,
+                      int ldz, bf16_t* out, int ldo, const int* row, const float* scale, int B, int rows, int K, int N, int R, hipStream_t st);
 bool gemm_cross77_enabled();      // debug bit 19 clear
 int attention_units_plan_host(const int* q_src, const int* k_src, int B, int N, int DP, int mode, int* launch_of, int* unit_of, int* members_of);   // host-only: the partition launch_attention would take
 void gemm16_set_tall(int on);        // (A/B) rt_op_gemm_debug bit 27

@@ -93,6 +93,7 @@ struct TBlockP {
     // regional LoRA (rt_config.lora_rank > 0, main UNet only; lora.hip): the factors of the eight attention projections, packed like the
     // base weight they sit beside - index 4 a + {0 to_q, 1 to_k, 2 to_v, 3 to_out.0} of attn(a + 1)
     LoraW lora[8];
+    LoraW lora_ff1, lora_ff2;    // rt_config.lora_targets = 1: ff.net.0.proj (`up` rows in ff1's GEGLU order) and ff.net.2; null otherwise
     // token-map attention store: index 0 = attn1, 1 = attn2
     std::string mod_name[2];
     float* store[2] = {nullptr, nullptr};
@@ -107,6 +108,7 @@ struct TransformerP {
     int C = 0, heads = 0, d = 0, DP = 0, level = 0;
     NormW gn;
     MatW pin, pout;
+    LoraW lora_pin, lora_pout;   // rt_config.lora_targets = 1: proj_in / proj_out, plain; null otherwise
     std::vector<TBlockP> blocks;
 };
 struct DownP { std::vector<ResnetP> res; std::vector<TransformerP> attn; bool has_attn = false, has_down = false; MatW down; int C = 0; };
@@ -604,6 +606,21 @@ struct rt_engine {
         const float qscale = (float)(std::pow((double)t.d, -0.5) * 1.4426950408889634);   // d^-1/2 * log2(e)
         t.gn = mk_norm(name + ".norm", C);
         t.pin = mk_linear(name + ".proj_in", C, C, true, !cfg.use_linear_projection);
+        // rt_config.lora_targets = 1: the factors of a further module [N, K], packed like the base weight (up_rows: the row order of `up`)
+        const bool lora_wide = cfg.lora_rank > 0 && cfg.lora_targets == 1 && adapters;
+        auto mk_lora = [&](const std::string& module, int K, int N, int up_rows) {
+            const int R = cfg.lora_rank;
+            LoraW w; w.K = K; w.N = N;
+            w.down = (bf16_t*)arena.alloc((size_t)R * K * 2);
+            w.up = (bf16_t*)arena.alloc((size_t)N * R * 2);
+            w.aor = (float*)arena.alloc((size_t)R * 4);
+            add_slot("lora." + module + ".down.weight", {R, K}, pk_matrix(w.down, R, K, K, K));
+            PackArgs p = pk_matrix(w.up, N, R, R, R); p.row_map = up_rows;
+            add_slot("lora." + module + ".up.weight", {N, R}, p);
+            add_slot("lora." + module + ".alpha_over_rank", {R}, pk_vec(w.aor, R));
+            return w;
+        };
+        if (lora_wide) t.lora_pin = mk_lora(name + ".proj_in", C, C, PACK_ROWS_ID);
         for (int li = 0; li < nlayers; ++li) {
             const std::string b = name + ".transformer_blocks." + std::to_string(li);
             TBlockP k;
@@ -679,9 +696,14 @@ struct rt_engine {
                         add_slot(m + ".alpha_over_rank", {R}, pk_vec(w.aor, R));
                     }
             }
+            if (lora_wide) {
+                k.lora_ff1 = mk_lora(b + ".ff.net.0.proj", C, 8 * C, PACK_ROWS_GEGLU);
+                k.lora_ff2 = mk_lora(b + ".ff.net.2", 4 * C, C, PACK_ROWS_ID);
+            }
             t.blocks.push_back(k);
         }
         t.pout = mk_linear(name + ".proj_out", C, C, true, !cfg.use_linear_projection);
+        if (lora_wide) t.lora_pout = mk_lora(name + ".proj_out", C, C, PACK_ROWS_ID);
         return t;
     }
 
@@ -942,7 +964,8 @@ struct rt_engine {
 
     // ---------------------------------------------------------------------------- transformer
     // Regional LoRA (rt_set_lora_scales): the adapted streams of a forward - those whose prompt slot has a non-zero scale - get the low-rank
-    // term added behind each of the eight attention projections; every other stream is in none of these launches
+    // term added behind each of the eight attention projections - with rt_config.lora_targets = 1 behind proj_in, ff.net.2 and proj_out as
+    // well, and their ff.net.0.proj runs unfused (feed_forward) -; every other stream is in none of these launches
     struct LoraRows {
         rt_engine& e;
         int B, HW;
@@ -957,17 +980,18 @@ struct rt_engine {
             }
         }
         bool on(int b) const { return sc[4 * b] != 0.f || sc[4 * b + 1] != 0.f || sc[4 * b + 2] != 0.f || sc[4 * b + 3] != 0.f; }
-        // run f(first stream, streams) over the maximal runs of adapted streams (the row-wise kernels take a run as one launch)
-        template <typename F> void runs(F f) const {
+        // run f(first stream, streams) over the maximal runs of adapted streams (the row-wise kernels take a run as one launch) - or,
+        // adapted = false, of the streams the adapters leave alone
+        template <typename F> void runs(F f, bool adapted = true) const {
             for (int b = 0; b < B;) {
-                if (!on(b)) { ++b; continue; }
-                int e_ = b; while (e_ < B && on(e_)) ++e_;
+                if (on(b) != adapted) { ++b; continue; }
+                int e_ = b; while (e_ < B && on(e_) == adapted) ++e_;
                 f(b, e_ - b); b = e_;
             }
         }
-        // the term of one projection for the first nb streams
+        // the term of one projection for the first nb streams (a module without factors - rt_config.lora_targets = 0 - has none)
         void add(const LoraW& w, const bf16_t* X, int ldx, void* Y, int ldy, int form, int nb) const {
-            if (any) e.lora_add(w, X, ldx, Y, ldy, form, rows, sc, nb, HW);
+            if (any && w.down) e.lora_add(w, X, ldx, Y, ldy, form, rows, sc, nb, HW);
         }
         // a folded LayerNorm is never materialised: the adapters' input is computed for the adapted rows only, into `n`
         void norm(const NormW& ln, const f16_t* h, bf16_t* n) const {
@@ -1016,9 +1040,14 @@ struct rt_engine {
         // partials of the trunk as it stands, for the LayerNorm that follows
         void partials() { if (!e.dry()) launch_ln_partials(hcur, xb, part, M, C, ln_bn, e.stream); }
         // consume: out = epi(LayerNorm i of the trunk x W^T) - the folded GEMM on xb, or the LayerNorm into `n` and the plain GEMM
-        void consume(int i, const NormW& ln, bf16_t* n, const MatW& W, const MatW& Wf, const float* s, void* out, int ldo, int epi) {
-            if (fold[i]) { const LnFold l = reads(s); e.gemm(xb, C, Wf, M, out, ldo, epi, nullptr, 0, &l); }
-            else { e.layernorm(hcur, ln, n, M); e.gemm(n, C, W, M, out, ldo, epi); }
+        void consume(int i, const NormW& ln, bf16_t* n, const MatW& W, const MatW& Wf, const float* s, bf16_t* out, int ldo, int epi) {
+            consume_rows(i, ln, n, W, Wf, s, out, ldo, epi, 0, M);
+        }
+        // ... of `rows` rows from row0 on (a run of streams): the same launches over fewer rows, whose bits do not depend on the run
+        void consume_rows(int i, const NormW& ln, bf16_t* n, const MatW& W, const MatW& Wf, const float* s, bf16_t* out, int ldo, int epi, int row0, int rows) {
+            const size_t r0 = (size_t)row0;
+            if (fold[i]) { LnFold l = reads(s); l.part = part + r0 * 4; e.gemm(xb + r0 * C, C, Wf, rows, out + r0 * ldo, ldo, epi, nullptr, 0, &l); }
+            else { e.layernorm(hcur + r0 * C, ln, n + r0 * C, rows); e.gemm(n + r0 * C, C, W, rows, out + r0 * ldo, ldo, epi); }
         }
         // produce into the trunk: hcur = A W^T (+ hcur with `residual`), then the adapters' term `lw` (the adapted rows are rounded to fp16 a
         // second time: control_add_kernel's precedent).  folds: the LayerNorm that reads the trunk next is folded, so it needs the partials
@@ -1026,6 +1055,7 @@ struct rt_engine {
         // the stand-alone kernel; rows the adapters changed behind an emitting GEMM get theirs recomputed.
         void produce(const bf16_t* A, int lda, const MatW& W, bool residual, bool folds, bool emits, bool read_again = true, const LoraW* lw = nullptr) {
             e.gemm(A, lda, W, M, hcur, C, EPI_F16, residual ? hcur : nullptr, residual ? C : 0, folds && emits ? &em : nullptr);
+            if (lw && !lw->down) lw = nullptr;
             if (lw) lora.add(*lw, A, lda, hcur, C, 2, lora.B);
             if (folds && !emits && read_again) partials();
             if (folds && emits && lw)
@@ -1174,11 +1204,35 @@ struct rt_engine {
 
     // GEGLU feed-forward (attention.py:209-304)
     void feed_forward(TCall& c, TBlockP& k, bool last) {
-        bf16_t* gg = ws.b16((size_t)c.M * 4 * c.C);
-        c.ln.consume(2, k.ln3, c.n, k.ff1, k.ff1f, k.ff1s, gg, 4 * c.C, EPI_GEGLU);
+        const int HW = c.HW, C = c.C;
+        bf16_t* gg = ws.b16((size_t)c.M * 4 * C);
+        // ff.net.0.proj's adapter (rt_config.lora_targets = 1): the GEGLU epilogue cannot take an add behind the GEMM, so an adapted stream
+        // runs unfused and once - LayerNorm 3 of its rows, the plain weight into fp32 scratch z (ONE stream's at a time), lora_geglu_kernel
+        // into its rows of gg - while the maximal runs of the other streams keep the fused launch and its bits.  The dry planning forward
+        // plans both: the whole fused launch and one stream's fp32 GEMM with its scratch.
+        const bool wide = k.lora_ff1.down && (c.lora.any || dry());
+        if (!wide) {
+            c.ln.consume(2, k.ln3, c.n, k.ff1, k.ff1f, k.ff1s, gg, 4 * C, EPI_GEGLU);
+        } else {
+            float* z = ws.f32((size_t)HW * 8 * C);
+            if (dry()) {
+                c.ln.consume(2, k.ln3, c.n, k.ff1, k.ff1f, k.ff1s, gg, 4 * C, EPI_GEGLU);
+                gemm(c.n, C, k.ff1, HW, z, 8 * C, EPI_F32);
+            } else {
+                c.lora.runs([&](int b, int nb) { c.ln.consume_rows(2, k.ln3, c.n, k.ff1, k.ff1f, k.ff1s, gg, 4 * C, EPI_GEGLU, b * HW, nb * HW); }, false);
+                for (int b = 0; b < c.B; ++b) {
+                    if (!c.lora.on(b)) continue;
+                    bf16_t* nb_ = c.n + (size_t)b * HW * C;
+                    layernorm(c.ln.hcur + (size_t)b * HW * C, k.ln3, nb_, HW);
+                    gemm(nb_, C, k.ff1, HW, z, 8 * C, EPI_F32);
+                    lora_geglu(k.lora_ff1, nb_, z, gg + (size_t)b * HW * 4 * C, c.lora.sc + 4 * b, HW);
+                }
+            }
+        }
         // the next block's norm1 reads what ff.net.2 leaves; behind the LAST block proj_out reads the trunk as bf16 - which is
-        // exactly the xb an emitting ff.net.2 writes (the cast launch in transformer() is then not needed)
-        c.ln.produce(gg, 4 * c.C, k.ff2, true, c.ln.fold[0], c.ln.emit_ff2, !last);
+        // exactly the xb an emitting ff.net.2 writes (the cast launch in transformer() is then not needed; the rows ff.net.2's adapter
+        // changed are refreshed in xb by produce, together with their partials)
+        c.ln.produce(gg, 4 * C, k.ff2, true, c.ln.fold[0], c.ln.emit_ff2, !last, &k.lora_ff2);
     }
 
     // Transformer2DModel.forward (models/transformer_2d.py:270-310) + BasicTransformerBlock (attention.py:131-206)
@@ -1198,7 +1252,7 @@ struct rt_engine {
                 Scope s2(ws);
                 bf16_t* g = ws.b16((size_t)M * C);
                 groupnorm(x.p, nullptr, 2, C, 0, B, HW, t.gn, 1e-6f, false, g, nullptr);
-                c.ln.produce(g, C, t.pin, false, c.ln.fold[0], c.ln.emit_pin);
+                c.ln.produce(g, C, t.pin, false, c.ln.fold[0], c.ln.emit_pin, true, &t.lora_pin);
             }
             for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
                 Scope s2(ws);
@@ -1215,6 +1269,7 @@ struct rt_engine {
             bf16_t* hb = ws.b16((size_t)M * C);
             if (!dry() && !have_xb) launch_cast_f16_bf16(hcur, hb, (size_t)M * C, stream);
             gemm(have_xb ? xb : hb, C, t.pout, M, out, C, EPI_F16, x.p, C);
+            c.lora.add(t.lora_pout, have_xb ? xb : hb, C, out, C, 2, B);
         }
         return Tensor{out, C};
     }
@@ -1528,6 +1583,13 @@ struct rt_engine {
         launch_lora_add(X, ldx, w.down, w.K, w.up, R, w.aor, lora_col, Y, ldy, form, rows_at, sc4, B, rows, w.K, w.N, R, stream);
         prof_end();
     }
+    // ff.net.0.proj of ONE adapted stream from its fp32 pre-activations (lora_geglu_kernel): Z read, X read, out written once
+    void lora_geglu(const LoraW& w, const bf16_t* X, const float* Z, bf16_t* out, const float* sc4, int rows) {
+        const int R = cfg.lora_rank, row0 = 0;
+        prof_begin(RT_PROF_LORA, 2.0 * rows * R * ((double)w.K + w.N), (double)rows * (4.0 * w.N + 2.0 * w.K + w.N));
+        launch_lora_geglu(X, w.K, w.down, w.K, w.up, R, w.aor, lora_col, Z, w.N, out, w.N / 2, &row0, sc4, 1, rows, w.K, w.N, R, stream);
+        prof_end();
+    }
     void set_lora_columns(const int* col, int R) {
         RT_REQUIRE(cfg.lora_rank > 0, "set_lora_columns: the engine was built without regional LoRA (rt_config.lora_rank == 0)");
         RT_REQUIRE(col && R == cfg.lora_rank, "set_lora_columns: one adapter index per rank column (rt_config.lora_rank of them)");
@@ -1825,6 +1887,7 @@ int rt_create(const rt_config* cfg, int device, rt_engine** out) {
         RT_REQUIRE(cfg->ip_tokens >= 0 && cfg->ip_tokens <= 16, "rt_create: ip_tokens must be 0 (no image prompts) or 1 .. 16");
         RT_REQUIRE(cfg->controlnet == 0 || cfg->controlnet == 1, "rt_create: controlnet must be 0 or 1");
         RT_REQUIRE(cfg->lora_rank >= 0 && cfg->lora_rank <= 128 && cfg->lora_rank % 16 == 0, "rt_create: lora_rank must be 0 (no regional LoRA) or a multiple of 16 up to 128");
+        RT_REQUIRE(cfg->lora_targets == 0 || (cfg->lora_targets == 1 && cfg->lora_rank > 0), "rt_create: lora_targets must be 0 (the attention projections) or, with lora_rank > 0, 1 (feed-forward, proj_in and proj_out as well)");
         e = new rt_engine();
         e->cfg = *cfg; e->device = device;
         e->lora_scale.assign((size_t)std::max(1, cfg->max_prompts) * 4, 0.f);
@@ -2844,6 +2907,16 @@ int rt_op_lora_add(const void* X, int ldx, const void* down, int ldd, const void
         RT_REQUIRE(X && down && up && alpha_over_rank && col_adapter && Y && row_host && scale_host, "rt_op_lora_add: null argument");
         const int n = launch_lora_add((const bf16_t*)X, ldx, (const bf16_t*)down, ldd, (const bf16_t*)up, ldu, alpha_over_rank, col_adapter, Y, ldy, form,
                                       row_host, scale_host, B, rows, K, N, R, (hipStream_t)stream);
+        if (launched) *launched = n;
+    })
+}
+int rt_op_lora_geglu(const void* X, int ldx, const void* down, int ldd, const void* up, int ldu, const float* alpha_over_rank, const int* col_adapter,
+                     const float* Z, int ldz, void* out, int ldo, const int* row_host, const float* scale_host, int B, int rows, int K, int N, int R,
+                     int* launched, void* stream) {
+    OP_TRY({
+        RT_REQUIRE(X && down && up && alpha_over_rank && col_adapter && Z && out && row_host && scale_host, "rt_op_lora_geglu: null argument");
+        const int n = launch_lora_geglu((const bf16_t*)X, ldx, (const bf16_t*)down, ldd, (const bf16_t*)up, ldu, alpha_over_rank, col_adapter, Z, ldz,
+                                        (bf16_t*)out, ldo, row_host, scale_host, B, rows, K, N, R, (hipStream_t)stream);
         if (launched) *launched = n;
     })
 }

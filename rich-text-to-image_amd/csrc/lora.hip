@@ -17,6 +17,9 @@
 // consecutive m of its n).  Every global access is 16 bytes.  No atomics, no workgroup waits on another, a row's arithmetic depends on
 // neither the grid nor the other streams.  An element whose term is exactly 0 - the head-pad columns, whose rows of B are zero -
 // keeps its bits.
+//
+// lora_geglu_kernel (further down) is the same wave structure for ff.net.0.proj, whose GEGLU epilogue an add behind the GEMM cannot
+// reach: the first product and its rounding are shared (lora_ts), the second meets the base GEMM's fp32 pre-activations.
 #include "xb_common.h"
 #include <cmath>
 
@@ -30,30 +33,21 @@ struct LoraArgs {
     const float* aor;              // [R] alpha / rank per rank column
     const int* adapter;            // [R] adapter (0 .. 3) per rank column
     void* Y; int ldy;              // row-major forms: [*, ldy] row (row[i] + m), N columns; transposed: [N, ldy] column (row[i] + m)
+    const float* Z; int ldz;       // lora_geglu_kernel only: [*, ldz] row (row[i] + m), the N packed pre-activations; Y then has N / 2 columns
     int nact, rows, K, N, R, ntile;      // streams in the grid, rows per stream, 64-row tiles per stream
     int row[RT_MAXB];
     float scale[RT_MAXB][4];
 };
 
-template <int NKS, int FORM>                                          // R <= 32 NKS
-__global__ __launch_bounds__(128) void lora_add_kernel(LoraArgs p) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int l15 = lane & 15, q4 = lane >> 4;
-    const int i = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    const int m0 = tile * 64 + wave * 32;
-    if (m0 >= p.rows) return;                                         // wave-uniform; the kernel has no barrier
-    const size_t row0 = (size_t)p.row[i];
+// The first product and its one rounding, shared by both kernels: T^T = A X^T of the wave's rows mrow[2] of stream i, then Ts = bf16(f T).
+// Tile (mt, 2 ks + h): lane (l15, q4) reg e <- row mrow[mt] (of lane l15), rank column 32 ks + 8 q4 + 4 h + e; the fragment ts[mt][ks] of
+// contraction step ks holds rank columns 32 ks + 8 q4 .. + 7 of the lane's row.
+template <int NKS>                                                    // R <= 32 NKS
+static __device__ __forceinline__ void lora_ts(const LoraArgs& p, int i, size_t row0, const int (&mrow)[2], int pi, int q4, bf16x8 (&ts)[2][NKS]) {
     const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int pi = 8 * (l15 >> 2) + (l15 & 3);                        // + 4 h: the pi order of a pair of 16-row tiles
-    // ---- T^T = A X^T: tile (mt, 2 ks + h); lane (l15, q4) reg e <- row mrow[mt] (of lane l15), rank column 32 ks + 8 q4 + 4 h + e
-    int mrow[2];
     const bf16_t* xp[2];
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        mrow[mt] = m0 + (FORM == LORA_BF16_T ? pi + 4 * mt : 16 * mt + l15);
-        xp[mt] = p.X + (row0 + (mrow[mt] < p.rows ? mrow[mt] : 0)) * p.ldx + 8 * q4;
-    }
+    for (int mt = 0; mt < 2; ++mt) xp[mt] = p.X + (row0 + (mrow[mt] < p.rows ? mrow[mt] : 0)) * p.ldx + 8 * q4;
     const bf16_t* ap[2 * NKS];
     bool aok[2 * NKS];
 #pragma unroll
@@ -79,27 +73,41 @@ __global__ __launch_bounds__(128) void lora_add_kernel(LoraArgs p) {
             acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, xf[1], acc[1][t], 0, 0, 0);
         }
     }
-    // ---- Ts = bf16(f T): the fragment of contraction step ks holds rank columns 32 ks + 8 q4 .. + 7 of the lane's row
-    bf16x8 ts[2][NKS];
-    {
-        const float s0 = p.scale[i][0], s1 = p.scale[i][1], s2 = p.scale[i][2], s3 = p.scale[i][3];
+    const float s0 = p.scale[i][0], s1 = p.scale[i][1], s2 = p.scale[i][2], s3 = p.scale[i][3];
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            f32x4 f[2];
+    for (int ks = 0; ks < NKS; ++ks) {
+        f32x4 f[2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = 32 * ks + 8 * q4 + 4 * h;
-                const bool ok = j < p.R;                              // R % 4 == 0
-                const f32x4 ar = ok ? *(const f32x4*)(p.aor + j) : (f32x4){0.f, 0.f, 0.f, 0.f};
-                const int4 ad = ok ? *(const int4*)(p.adapter + j) : make_int4(0, 0, 0, 0);
-                const int adv[4] = {ad.x, ad.y, ad.z, ad.w};
+        for (int h = 0; h < 2; ++h) {
+            const int j = 32 * ks + 8 * q4 + 4 * h;
+            const bool ok = j < p.R;                                  // R % 4 == 0
+            const f32x4 ar = ok ? *(const f32x4*)(p.aor + j) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            const int4 ad = ok ? *(const int4*)(p.adapter + j) : make_int4(0, 0, 0, 0);
+            const int adv[4] = {ad.x, ad.y, ad.z, ad.w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) f[h][e] = ar[e] * (adv[e] == 0 ? s0 : adv[e] == 1 ? s1 : adv[e] == 2 ? s2 : s3);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) ts[mt][ks] = xb_pack8(acc[mt][2 * ks] * f[0], acc[mt][2 * ks + 1] * f[1]);
+            for (int e = 0; e < 4; ++e) f[h][e] = ar[e] * (adv[e] == 0 ? s0 : adv[e] == 1 ? s1 : adv[e] == 2 ? s2 : s3);
         }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) ts[mt][ks] = xb_pack8(acc[mt][2 * ks] * f[0], acc[mt][2 * ks + 1] * f[1]);
     }
+}
+
+template <int NKS, int FORM>                                          // R <= 32 NKS
+__global__ __launch_bounds__(128) void lora_add_kernel(LoraArgs p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l15 = lane & 15, q4 = lane >> 4;
+    const int i = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int m0 = tile * 64 + wave * 32;
+    if (m0 >= p.rows) return;                                         // wave-uniform; the kernel has no barrier
+    const size_t row0 = (size_t)p.row[i];
+    const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int pi = 8 * (l15 >> 2) + (l15 & 3);                        // + 4 h: the pi order of a pair of 16-row tiles
+    int mrow[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) mrow[mt] = m0 + (FORM == LORA_BF16_T ? pi + 4 * mt : 16 * mt + l15);
+    bf16x8 ts[2][NKS];
+    lora_ts<NKS>(p, i, row0, mrow, pi, q4, ts);
     // ---- Y += Ts B^T
     if (FORM != LORA_BF16_T) {
         // 32 columns per step: tile h, row i <- n = n0 + pi + 4 h; lane (l15, q4) reg e of tile h = row mrow[mt], n = n0 + 8 q4 + 4 h + e
@@ -179,12 +187,78 @@ __global__ __launch_bounds__(128) void lora_add_kernel(LoraArgs p) {
     }
 }
 
+// lora_geglu_kernel: ff.net.0.proj of an adapted stream.  The GEGLU epilogue of the base GEMM is not reachable by an add behind it, so
+// the base GEMM of such a stream leaves its fp32 pre-activations Z (bias in; packed column order, per 64-block [32 value | 32 gate]) and
+// this kernel finishes the projection:
+//   out[m, c] = bf16( (Zv + Dv) * gelu(Zg + Dg) ),   D = Ts B^T                     ONE rounding; gelu = gelu_erf_x2 (common.h), EPI_GEGLU's
+// with Ts as above and B [N, R] in the packed row order of the base weight.  One step takes a packed 64-block: the value tiles and the
+// gate tiles are the h tiles of two row-major steps 32 columns apart, so lane (l15, q4) ends with the value AND the gate of output
+// columns 32 blk + 8 q4 .. + 7 of its row: four float4 of Z in, one 16-byte piece of out.
+template <int NKS>
+__global__ __launch_bounds__(128) void lora_geglu_kernel(LoraArgs p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l15 = lane & 15, q4 = lane >> 4;
+    const int i = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int m0 = tile * 64 + wave * 32;
+    if (m0 >= p.rows) return;                                         // wave-uniform; the kernel has no barrier
+    const size_t row0 = (size_t)p.row[i];
+    const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int pi = 8 * (l15 >> 2) + (l15 & 3);
+    const int mrow[2] = {m0 + l15, m0 + 16 + l15};
+    bf16x8 ts[2][NKS];
+    lora_ts<NKS>(p, i, row0, mrow, pi, q4, ts);
+    // tile (g, h), g = 0 value / 1 gate: row i <- n = n0 + 32 g + pi + 4 h; lane (l15, q4) reg e = row mrow[mt], n = n0 + 32 g + 8 q4 + 4 h + e
+    for (int n0 = 0; n0 < p.N; n0 += 64) {                            // N % 64 == 0
+        f32x4 d[2][2][2];
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                d[0][g][h] = (f32x4){0.f, 0.f, 0.f, 0.f}; d[1][g][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                const bf16_t* bp = p.B + (size_t)(n0 + 32 * g + pi + 4 * h) * p.ldb + 8 * q4;
+#pragma unroll
+                for (int ks = 0; ks < NKS; ++ks) {
+                    const bf16x8 bf = 32 * ks + 8 * q4 < p.R ? *(const bf16x8*)(bp + 32 * ks) : zero8;      // R % 8 == 0
+                    d[0][g][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, ts[0][ks], d[0][g][h], 0, 0, 0);
+                    d[1][g][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, ts[1][ks], d[1][g][h], 0, 0, 0);
+                }
+            }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            if (mrow[mt] >= p.rows) continue;
+            const float* zp = p.Z + (row0 + mrow[mt]) * p.ldz + n0 + 8 * q4;
+            f32x4 o[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x4 v = *(const f32x4*)(zp + 4 * h) + d[mt][0][h], gt = *(const f32x4*)(zp + 32 + 4 * h) + d[mt][1][h];
+                const f32x2 a0 = gelu_erf_x2((f32x2){gt[0], gt[1]}), a1 = gelu_erf_x2((f32x2){gt[2], gt[3]});
+                o[h] = v * (f32x4){a0.x, a0.y, a1.x, a1.y};
+            }
+            *(bf16x8*)((bf16_t*)p.Y + (row0 + mrow[mt]) * p.ldy + (n0 >> 1) + 8 * q4) = xb_pack8(o[0], o[1]);
+        }
+    }
+}
+
 template <int NKS>
 static void lora_launch_form(const LoraArgs& a, int form, dim3 grid, hipStream_t st) {
     switch (form) {
         case LORA_BF16: hipLaunchKernelGGL((lora_add_kernel<NKS, LORA_BF16>), grid, dim3(128), 0, st, a); break;
         case LORA_BF16_T: hipLaunchKernelGGL((lora_add_kernel<NKS, LORA_BF16_T>), grid, dim3(128), 0, st, a); break;
         default: hipLaunchKernelGGL((lora_add_kernel<NKS, LORA_F16>), grid, dim3(128), 0, st, a); break;
+    }
+}
+
+// The streams of a launch: one whose four scales are all 0 is not in the grid
+static void lora_streams(LoraArgs& a, const int* row, const float* scale /* [B][4] */, int B) {
+    for (int b = 0; b < B; ++b) {
+        bool on = false;
+        for (int l = 0; l < 4; ++l) { RT_REQUIRE(std::isfinite(scale[4 * b + l]), "lora: scale"); on |= scale[4 * b + l] != 0.f; }
+        if (!on) continue;
+        RT_REQUIRE(row[b] >= 0 && row[b] % 8 == 0, "lora: a stream's row offset (a multiple of 8)");
+        a.row[a.nact] = row[b];
+        for (int l = 0; l < 4; ++l) a.scale[a.nact][l] = scale[4 * b + l];
+        ++a.nact;
     }
 }
 
@@ -201,16 +275,8 @@ int launch_lora_add(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const
     RT_REQUIRE(((uintptr_t)X | (uintptr_t)down | (uintptr_t)up | (uintptr_t)Y | (uintptr_t)aor | (uintptr_t)adapter) % 16 == 0, "lora_add: 16-byte alignment");
     LoraArgs a{}; a.X = X; a.ldx = ldx; a.A = down; a.lda = ldd; a.B = up; a.ldb = ldu; a.aor = aor; a.adapter = adapter; a.Y = Y; a.ldy = ldy;
     a.rows = rows; a.K = K; a.N = N; a.R = R; a.ntile = cdiv(rows, 64);
-    for (int b = 0; b < B; ++b) {
-        bool on = false;
-        for (int l = 0; l < 4; ++l) { RT_REQUIRE(std::isfinite(scale[4 * b + l]), "lora_add: scale"); on |= scale[4 * b + l] != 0.f; }
-        if (!on) continue;
-        RT_REQUIRE(row[b] >= 0 && row[b] % 8 == 0, "lora_add: a stream's row offset (a multiple of 8)");
-        RT_REQUIRE(form != LORA_BF16_T || (long)row[b] + rows <= ldy, "lora_add: stream beyond the transposed row");
-        a.row[a.nact] = row[b];
-        for (int l = 0; l < 4; ++l) a.scale[a.nact][l] = scale[4 * b + l];
-        ++a.nact;
-    }
+    lora_streams(a, row, scale, B);
+    for (int i = 0; i < a.nact; ++i) RT_REQUIRE(form != LORA_BF16_T || (long)a.row[i] + rows <= ldy, "lora_add: stream beyond the transposed row");
     if (a.nact == 0) return 0;
     const dim3 grid(a.ntile * a.nact);
     switch (cdiv(R, 32)) {
@@ -218,6 +284,31 @@ int launch_lora_add(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const
         case 2: lora_launch_form<2>(a, form, grid, st); break;
         case 3: lora_launch_form<3>(a, form, grid, st); break;
         default: lora_launch_form<4>(a, form, grid, st); break;
+    }
+    HIP_CHECK(hipGetLastError());
+    return a.nact;
+}
+
+// ff.net.0.proj of the adapted streams from the base GEMM's fp32 pre-activations (lora_geglu_kernel): N packed columns in, N / 2 out.
+// The same streams rule as launch_lora_add; returns the number of streams launched.
+int launch_lora_geglu(const bf16_t* X, int ldx, const bf16_t* down, int ldd, const bf16_t* up, int ldu, const float* aor, const int* adapter, const float* Z,
+                      int ldz, bf16_t* out, int ldo, const int* row, const float* scale /* [B][4] */, int B, int rows, int K, int N, int R, hipStream_t st) {
+    RT_REQUIRE(B >= 1 && B <= RT_MAXB && rows >= 8 && rows % 8 == 0, "lora_geglu: batch / rows per stream (rows % 8 == 0)");
+    RT_REQUIRE(K >= 8 && K % 8 == 0 && N >= 64 && N % 64 == 0, "lora_geglu: K must be a multiple of 8, N (packed value | gate columns) of 64");
+    RT_REQUIRE(R >= 16 && R <= 128 && R % 16 == 0, "lora_geglu: 16 <= R <= 128 rank columns, a multiple of 16");
+    RT_REQUIRE(ldx % 8 == 0 && ldd % 8 == 0 && ldu % 8 == 0 && ldo % 8 == 0 && ldz % 4 == 0, "lora_geglu: leading dimensions");
+    RT_REQUIRE(ldx >= K && ldd >= K && ldu >= R && ldz >= N && ldo >= N / 2, "lora_geglu: a row holds its columns");
+    RT_REQUIRE(((uintptr_t)X | (uintptr_t)down | (uintptr_t)up | (uintptr_t)Z | (uintptr_t)out | (uintptr_t)aor | (uintptr_t)adapter) % 16 == 0, "lora_geglu: 16-byte alignment");
+    LoraArgs a{}; a.X = X; a.ldx = ldx; a.A = down; a.lda = ldd; a.B = up; a.ldb = ldu; a.aor = aor; a.adapter = adapter; a.Y = out; a.ldy = ldo;
+    a.Z = Z; a.ldz = ldz; a.rows = rows; a.K = K; a.N = N; a.R = R; a.ntile = cdiv(rows, 64);
+    lora_streams(a, row, scale, B);
+    if (a.nact == 0) return 0;
+    const dim3 grid(a.ntile * a.nact);
+    switch (cdiv(R, 32)) {
+        case 1: hipLaunchKernelGGL(lora_geglu_kernel<1>, grid, dim3(128), 0, st, a); break;
+        case 2: hipLaunchKernelGGL(lora_geglu_kernel<2>, grid, dim3(128), 0, st, a); break;
+        case 3: hipLaunchKernelGGL(lora_geglu_kernel<3>, grid, dim3(128), 0, st, a); break;
+        default: hipLaunchKernelGGL(lora_geglu_kernel<4>, grid, dim3(128), 0, st, a); break;
     }
     HIP_CHECK(hipGetLastError());
     return a.nact;

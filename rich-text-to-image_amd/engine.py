@@ -59,6 +59,7 @@ class RtConfig(C.Structure):
         ("control_hint_channels", C.c_int),
         ("control_embed_channels", C.c_int * 4),
         ("lora_rank", C.c_int),
+        ("lora_targets", C.c_int),
     ]
 
 
@@ -98,7 +99,7 @@ _SYMBOLS = [
     "rt_op_patchify", "rt_op_vit_embed", "rt_op_bidir_attention",
     "rt_op_latent_attention",
     "rt_set_control_hint", "rt_control_embedding_read", "rt_set_control_scales", "rt_op_control_add",
-    "rt_op_lora_add", "rt_set_lora_columns", "rt_set_lora_scales", "rt_attn_cache_info",
+    "rt_op_lora_add", "rt_set_lora_columns", "rt_set_lora_scales", "rt_attn_cache_info", "rt_op_lora_geglu",
     "rt_set_pag_layers", "rt_set_pag_scales", "rt_plain_streams", "rt_unet_forward_perturbed", "rt_op_identity_attention", "rt_op_pag_fold",
 ]
 
@@ -143,9 +144,11 @@ def _tup(v, n):
 CONTROL_EMBED_CHANNELS = (16, 32, 96, 256)      # diffusers' ControlNetModel default `conditioning_embedding_out_channels`
 
 
-def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None, lora_rank=0):
+def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None, lora_rank=0,
+                     lora_targets=0):
     """UNet2DConditionModel kwargs (reference config.json) -> rt_config.  max_keys: keys of the longest prompt (77 per CLIP window).
     lora_rank: rank columns of the regional LoRA adapters (a multiple of 16 up to 128); 0 = none: the weight table is the reference's.
+    lora_targets: 0 = the adapters sit on the eight attention projections; 1 = on ff.net.0.proj, ff.net.2, proj_in and proj_out as well.
     ip_tokens: image tokens per prompt slot of an IP-Adapter (1 .. 16); 0 = none: the weight table is the reference's state_dict layout.
     controlnet: None = no ControlNet (likewise), or dict(embed_channels=(16, 32, 96, 256), hint_channels=3) - either key optional."""
     c = RtConfig()
@@ -176,6 +179,7 @@ def config_from_dict(cfg, latent_h, latent_w, max_streams=8, max_prompts=8, max_
     c.max_keys = max_keys
     c.ip_tokens = int(ip_tokens)
     c.lora_rank = int(lora_rank)
+    c.lora_targets = int(lora_targets)
     if controlnet is not None:
         unknown = set(controlnet) - {"embed_channels", "hint_channels"}
         if unknown:
@@ -198,11 +202,11 @@ class Engine:
     """One engine = one GPU.  Mirrors the C ABI one to one; see include/rtdiff.h for semantics."""
 
     def __init__(self, cfg_dict, latent_h, latent_w, device=0, max_streams=8, max_prompts=8, max_keys=77, ip_tokens=0, controlnet=None,
-                 lora_rank=0):
+                 lora_rank=0, lora_targets=0):
         self.lib = load_library()
         self.cfg_dict = dict(cfg_dict)
-        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens, controlnet, lora_rank)
-        self.lora_rank = int(lora_rank)
+        self.cfg = config_from_dict(cfg_dict, latent_h, latent_w, max_streams, max_prompts, max_keys, ip_tokens, controlnet, lora_rank, lora_targets)
+        self.lora_rank, self.lora_targets = int(lora_rank), int(lora_targets)
         self.controlnet = dict(controlnet) if controlnet is not None else None
         self.max_keys = max_keys
         self.ip_tokens = int(ip_tokens)
@@ -394,6 +398,11 @@ class Engine:
                 raise ValueError(f"the adapters' padded ranks {dict(zip(layout[0], layout[1]))} add up to {layout[3]} rank columns; this engine was built for {R}")
         col = [0] * R
         table = dict(self.weight_table())
+        # an adapter must run whole: a module this engine has no slot for (ff / proj_in / proj_out on an engine built with lora_targets=0) is refused
+        absent = sorted({p for m in (adapters or {}).values() for p in m if f"lora.{p}.down.weight" not in table})
+        if absent:
+            raise ValueError(f"bind_regional_loras: this engine (lora_targets={self.lora_targets}) has no slots for the adapted modules {absent}; "
+                             "build it with lora_targets=1, or parse the adapters with attention_only=True")
         for name, shape in table.items():
             if not name.startswith("lora.") or not name.endswith(".down.weight"):
                 continue
@@ -794,6 +803,37 @@ def lora_add(X, down, up, alpha_over_rank, col_adapter, Y, form, rows_at, scales
         rc = lib.rt_op_lora_add(_ptr(X), int(X.stride(0)), _ptr(down), int(down.stride(0)), _ptr(up), int(up.stride(0)), _ptr(alpha_over_rank),
                                 _ptr(col_adapter), _ptr(Y), int(Y.stride(0)), f, (C.c_int * B)(*[int(v) for v in rows_at]), (C.c_float * (4 * B))(*sc),
                                 B, int(rows), int(K), int(N), int(R), C.byref(n), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc != 0:
+            raise RtError(rc, lib.rt_op_last_error().decode())
+        torch.cuda.synchronize()
+    return n.value
+
+
+def lora_geglu(X, down, up, alpha_over_rank, col_adapter, Z, out, rows_at, scales, rows):
+    """ff.net.0.proj of adapted streams from the base projection's fp32 pre-activations (rt_op_lora_geglu): per batch entry b with its `rows`
+    rows at rows_at[b] and the adapter scales scales[b], out = bf16((Zv + Dv) gelu(Zg + Dg)) with D = bf16(f_b (X down^T)) up^T.  X [*, >= K],
+    down [R, >= K], up [N, >= R] (rows in the packed GEGLU order) bf16, Z [*, >= N] fp32 (packed columns, per 64 [32 value | 32 gate]),
+    out [*, >= N / 2] bf16; 2-D tensors whose row stride is the leading dimension.  An entry whose scales are all 0 is skipped and its rows
+    of out are not written.  Returns the number of entries launched."""
+    import torch
+    lib = load_library()
+    B = len(rows_at)
+    R, K = down.shape
+    N = up.shape[0]
+    for t in (X, down, up, Z, out):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.device == out.device, "lora_geglu: [rows, ld] tensors on one device"
+    assert X.dtype == down.dtype == up.dtype == out.dtype == torch.bfloat16 and Z.dtype == torch.float32, "lora_geglu: dtypes"
+    assert alpha_over_rank.dtype == torch.float32 and col_adapter.dtype == torch.int32 and alpha_over_rank.numel() == R == col_adapter.numel() == up.shape[1]
+    assert alpha_over_rank.is_contiguous() and col_adapter.is_contiguous() and X.shape[1] >= K and len(scales) == B
+    top = max(int(r) for r in rows_at) + rows
+    assert min(X.shape[0], Z.shape[0], out.shape[0]) >= top and Z.shape[1] >= N and out.shape[1] >= N // 2, "lora_geglu: a stream outside the tensors"
+    sc = [float(s[l]) if l < len(s) else 0.0 for s in scales for l in range(4)]
+    n = C.c_int(0)
+    with torch.cuda.device(out.device):
+        rc = lib.rt_op_lora_geglu(_ptr(X), int(X.stride(0)), _ptr(down), int(down.stride(0)), _ptr(up), int(up.stride(0)), _ptr(alpha_over_rank),
+                                  _ptr(col_adapter), _ptr(Z), int(Z.stride(0)), _ptr(out), int(out.stride(0)), (C.c_int * B)(*[int(v) for v in rows_at]),
+                                  (C.c_float * (4 * B))(*sc), B, int(rows), int(K), int(N), int(R), C.byref(n),
+                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
         if rc != 0:
             raise RtError(rc, lib.rt_op_last_error().decode())
         torch.cuda.synchronize()

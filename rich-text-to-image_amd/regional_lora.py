@@ -11,6 +11,9 @@ R <= MAX_RANK rank columns, every adapter's block zero-padded to the kernel's gr
 and a stream's factor of column j is scale[slot][col_adapter[j]] * alpha_over_rank[j], kept in fp32 next to bf16 factors (never baked in).
 Targets are the eight attention projections attn{1,2}.{to_q,to_k,to_v,to_out.0} of every BasicTransformerBlock - diffusers' LoRA training
 targets; a tensor on any other module is refused by name (the merge, lora_path=, handles those) or dropped under attention_only=True.
+targets="transformer" (opt-in) widens the set to every Linear / 1x1 convolution of Transformer2DModel - kohya's default network: also
+ff.net.0.proj (csrc/lora.hip, rt_op_lora_geglu), ff.net.2, proj_in and proj_out; resnets, 3x3 convolutions, time_emb_proj and the
+samplers stay refused.
 Key layouts: lora.py's (kohya, diffusers 0.18, diffusers >= 0.20, peft)."""
 import math
 import re
@@ -23,21 +26,42 @@ MAX_ADAPTERS = 4
 MAX_RANK = 128
 GRANULE = 16                       # rank columns per MFMA tile of lora_add_kernel
 PROJECTIONS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
+TRANSFORMER_MODULES = ("ff.net.0.proj", "ff.net.2", "proj_in", "proj_out")      # what targets="transformer" adds
+TARGETS = ("attention", "transformer")
 _TARGET = re.compile(r"\.transformer_blocks\.\d+\.attn[12]\.(to_q|to_k|to_v|to_out\.0)$")
+_WIDE = re.compile(r"\.transformer_blocks\.\d+\.ff\.net\.(0\.proj|2)$|\.attentions\.\d+\.proj_(in|out)$")
 
 
-def is_target(path):
-    return _TARGET.search(path) is not None
+def check_targets(targets):
+    if targets not in TARGETS:
+        raise ValueError(f"regional LoRA: targets must be one of {TARGETS}, got {targets!r}")
+    return targets
 
 
-def parse_adapter(unet_state_dict, lora_state_dict, attention_only=False):
+def is_target(path, targets="attention"):
+    return _TARGET.search(path) is not None or (targets == "transformer" and is_wide(path))
+
+
+def is_wide(path):
+    """One of the four modules targets="transformer" adds (an engine carries their slots only with lora_targets = 1)."""
+    return _WIDE.search(path) is not None
+
+
+def parse_adapter(unet_state_dict, lora_state_dict, attention_only=False, targets="attention"):
     """One checkpoint -> (modules, report): modules = module path -> (down [r, K] fp32, up [N, r] fp32, alpha), report = dict(applied=[paths],
-    dropped=[paths] (attention_only), text_encoder=[keys], alpha_default=[paths])."""
+    dropped=[paths] (attention_only), text_encoder=[keys], alpha_default=[paths]).  targets: "attention" = the eight attention projections,
+    "transformer" = also ff.net.0.proj, ff.net.2, proj_in and proj_out (linear or 1x1 convolution)."""
+    check_targets(targets)
     paths, groups, text_encoder = resolve_targets(unet_state_dict, lora_state_dict)
-    other = sorted(p for p in groups if not is_target(p))
+    other = sorted(p for p in groups if not is_target(p, targets))
+    if other and not attention_only and targets == "transformer":
+        raise ValueError(f"regional LoRA (targets=\"transformer\") applies to the attention projections {PROJECTIONS} and to {TRANSFORMER_MODULES} "
+                         f"of a transformer; this checkpoint also adapts {other}: load it merged instead (lora_path=, lora_scale=), or pass "
+                         "attention_only=True to drop those tensors")
     if other and not attention_only:
         raise ValueError(f"regional LoRA applies to the attention projections {PROJECTIONS} only; this checkpoint also adapts {other}: "
-                         "load it merged instead (lora_path=, lora_scale=), or pass attention_only=True to drop those tensors")
+                         "load it merged instead (lora_path=, lora_scale=), or pass attention_only=True to drop those tensors "
+                         "(targets=\"transformer\" also takes feed-forward, proj_in and proj_out adapters)")
     modules, report = {}, dict(applied=[], dropped=other, text_encoder=text_encoder, alpha_default=[])
     for path, g in groups.items():
         if path in other:
@@ -234,17 +258,20 @@ class RegionalLoraMixin:
     def _rl_unet(self):
         return getattr(self, "unet", self)
 
-    def load_regional_loras(self, named, attention_only=False):
+    def load_regional_loras(self, named, attention_only=False, targets="attention"):
         """named: {name: path or state dict}, 1 .. 4 adapters whose padded ranks add up to at most 128.  Engines are built with the adapters
         from now on (existing ones are rebuilt on their next use); every scale starts at 0.  On a rank whose UNet weights arrive by
-        broadcast, load BEFORE the first engine exists.  Returns {name: report} (applied / dropped / text_encoder / alpha_default)."""
+        broadcast, load BEFORE the first engine exists.  targets="transformer" also takes adapters on ff.net.0.proj, ff.net.2, proj_in and
+        proj_out; the engines carry those modules only when some loaded adapter has a tensor there, so a file of attention tensors runs
+        the same path and bits under either value.  Returns {name: report} (applied / dropped / text_encoder / alpha_default)."""
+        check_targets(targets)
         u = self._rl_unet()
         if not isinstance(named, dict) or not named:
             raise ValueError("load_regional_loras: a dict {name: path or state dict} with at least one adapter")
         shapes = u._state_dict if isinstance(u._state_dict, dict) else unet_shapes(u.config_dict)
         adapters, reports = {}, {}
         for name, src in named.items():
-            adapters[str(name)], reports[str(name)] = parse_adapter(shapes, _read_checkpoint(src), attention_only)
+            adapters[str(name)], reports[str(name)] = parse_adapter(shapes, _read_checkpoint(src), attention_only, targets)
         rank_layout(adapters)                                         # more than 4 adapters / 128 rank columns: a ValueError naming the numbers
         u.install_regional_loras(adapters)
         self.regional_loras, self.lora_request = adapters, None

@@ -500,7 +500,8 @@ def build_model(a, rank=0, local_rank=0, world=1):
                 raise SystemExit(f"sample: --controlnet: {e}")
         if getattr(a, 'region_lora_files', None):    # --region_lora: every rank reads the files itself (the column map is per engine; the factors travel in the arena)
             try:
-                m.load_regional_loras(a.region_lora_files, attention_only=bool(getattr(a, 'region_lora_attention_only', False)))
+                m.load_regional_loras(a.region_lora_files, attention_only=bool(getattr(a, 'region_lora_attention_only', False)),
+                                      targets=getattr(a, 'region_lora_targets', None) or 'attention')
             except (ValueError, KeyError) as e:
                 raise SystemExit(f"sample: --region_lora: {e}")
         return m
@@ -664,6 +665,10 @@ def build_parser():
                         'in all; the same file may be named with several targets.  (load_components(lora_path=) merges ONE adapter into the weights instead)')
     p.add_argument('--region_lora_attention_only', action='store_true',
                    help='with --region_lora: drop a checkpoint\'s tensors on other modules (feed-forward, proj_in / proj_out, resnets) instead of refusing it')
+    p.add_argument('--region_lora_targets', choices=('attention', 'transformer'), default='attention',
+                   help='with --region_lora: the modules an adapter may sit on - attention: the eight attention projections (default); '
+                        'transformer: also ff.net.0.proj, ff.net.2, proj_in and proj_out, kohya\'s default network.  Adapters are loaded once '
+                        'per run, so a --requests run uses this value for every line')
     p.add_argument('--pag_scale', type=str, nargs='+', default=None, metavar='S|TARGET:S',
                    help='perturbed-attention guidance in both passes: a bare S is the scale of the base prompt and of every rich-text region, '
                         'TARGET is base or a region number.  A prompt with scale 0 gets no perturbed stream.  Needs classifier-free guidance; '

@@ -8,7 +8,7 @@ from .engine import Engine
 from .controlnet import ControlNetMixin
 from .pag import PagMixin
 from .ip_adapter import IPAdapterMixin
-from .regional_lora import RegionalLoraMixin, rank_layout
+from .regional_lora import RegionalLoraMixin, is_wide, rank_layout
 
 
 class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin, PagMixin):
@@ -30,6 +30,7 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin
         self.ip_tokens, self._ip_weights = 0, None # install_ip_adapter: image tokens per prompt slot (0 = no adapter) and the adapter's layer weights
         self._cn_config, self._cn_weights = None, None   # install_controlnet: Engine's controlnet= argument (None = no ControlNet) and the ControlNet's weights
         self.lora_rank, self._rl_adapters = 0, None      # install_regional_loras: Engine's lora_rank= argument (0 = none) and the parsed adapters
+        self.lora_targets = 0                            # ... and its lora_targets=: 1 when an adapter sits on ff.net.0.proj / ff.net.2 / proj_in / proj_out
 
     def install_regional_loras(self, adapters):
         """adapters: {name: modules} (regional_lora.parse_adapter) or None = remove them.  As install_ip_adapter: the weight table changes,
@@ -38,6 +39,7 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin
             raise RuntimeError("HipUNet2DConditionModel: the weights of this model arrived by broadcast and live in its engines only; "
                                "load / unload regional LoRA adapters before the first engine is built")
         self.lora_rank, self._rl_adapters = (rank_layout(adapters)[3], adapters) if adapters else (0, None)
+        self.lora_targets = int(any(is_wide(p) for m in (adapters or {}).values() for p in m))
         for e in self._engines.values():
             e.close()
         self._engines = {}
@@ -119,7 +121,7 @@ class HipUNet2DConditionModel(IPAdapterMixin, ControlNetMixin, RegionalLoraMixin
             try:
                 e = Engine(self.config_dict, h, w, device=self.device_index, max_streams=self.max_streams,
                            max_prompts=self.max_prompts, max_keys=self.max_keys, ip_tokens=self.ip_tokens, controlnet=self._cn_config,
-                           lora_rank=self.lora_rank)
+                           lora_rank=self.lora_rank, lora_targets=self.lora_targets)
                 try:
                     if empty:
                         if donor is not None:
